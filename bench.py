@@ -12,7 +12,10 @@ RCCL broadcast inside the timed region).  Weak scaling: per-GPU work is fixed.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how roofline / cpu_baseline are obtained).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for how roofline / cpu_baseline are obtained).  A plain run sets
+up, warms up, times the K steps and prints the headline fields; `--full` adds everything that takes runs of its own:
+per-UNet-step ms, the per-family roofline, the CPU baseline and (N = 1, headline config) the other BASELINE configs.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; DIR/<name>_rank<r>.npy at N > 1).
 """
 import argparse
 import json
@@ -316,10 +319,15 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="sd2_512", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure per-UNet-step ms, the per-family roofline, the CPU baseline and the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="headline line only (the default N = 1 run also times BASELINE configs[2..4], see OTHER_CONFIGS)")
+                    help="with --full: headline line only (the N = 1 --full run also times BASELINE configs[2..4], see "
+                         "OTHER_CONFIGS)")
     args = ap.parse_args()
 
     from minddiffusion_amd import distributed as D
@@ -332,14 +340,15 @@ def main():
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
     result = run_config(args.config, args, rank, world, device, args.steps, args.warmup,
-                        cpu=(world == 1 and not args.no_cpu_baseline and args.config == "sd2_512"))
-    if rank == 0 and world == 1 and args.config == "sd2_512" and not args.no_other_configs:
+                        cpu=(world == 1 and not args.no_cpu_baseline and args.config == "sd2_512"), full=args.full,
+                        dump_dir=args.dump_outputs)
+    if args.full and rank == 0 and world == 1 and args.config == "sd2_512" and not args.no_other_configs:
         # The other BASELINE configs' per-GPU shares, timed by the SAME command the driver runs: >= 3 timed
         # units each after one warm-up; the headline fields above are untouched.
         result["other_configs"] = {}
         for name in OTHER_CONFIGS:
             torch.cuda.empty_cache()
-            r = run_config(name, args, rank, world, device, 3, 1, cpu=False)
+            r = run_config(name, args, rank, world, device, 3, 1, cpu=False, full=True)
             result["other_configs"][name] = {
                 "metric": r["metric"], "value": r["value"], "unit": r["unit"], "steps": r["steps"], "warmup": r["warmup"],
                 "ms_per_step": r["ms_per_step"], "per_unet_step_ms": r.get("per_unet_step_ms"),
@@ -357,9 +366,26 @@ def main():
 OTHER_CONFIGS = ("wukong_512_plms", "sd2_768", "glide_256")
 
 
-def run_config(config, args, rank, world, device, steps, warmup, cpu):
-    """Build the models of one CONFIGS entry, time `steps` units after `warmup`, profile the plan's kernel families.  Returns
-    the result dict on rank 0 (None elsewhere)."""
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dump_dir, arrays, rank, world):
+    """--dump-outputs: the arrays the last timed step returned, as float32 DIR/<name>.npy (at N > 1 every rank writes its own
+    shard as DIR/<name>_rank<r>.npy).  An array above its share of the 64 MB budget is replaced by a fixed, seeded sample of
+    its flattened elements (sorted indices)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dump_dir, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
+
+
+def run_config(config, args, rank, world, device, steps, warmup, cpu, full=True, dump_dir=None):
+    """Build the models of one CONFIGS entry, time `steps` units after `warmup`; with `full`, also profile the plan's kernel
+    families (and the CPU baseline if `cpu`).  Returns the result dict on rank 0 (None elsewhere)."""
     from minddiffusion_amd import distributed as D
     from minddiffusion_amd.pipeline import DiffusionPipeline
     cfg = CONFIGS[config]
@@ -410,6 +436,7 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
                             decode=True)
             return pipe(c=c, uc=uc, x_T=x_T, H=8 * h, W=8 * w, steps=cfg["steps"], scale=cfg["scale"], eta=0.0,
                         decode=bool(cfg.get("vae")), batch_size=Bg)
+        out_name = "images" if cfg.get("vae") else "latents"
     else:
         # Taichu-GLIDE/src/txt2img.py:113-126 through the library's sharded pipeline: rank 0 holds the prompts of the
         # global batch; ONE packed broadcast carries them, the per-step unconditional token ids (identical on every rank,
@@ -426,6 +453,7 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
 
         def one_step():
             return gp(tokens=tok, mask=msk, seed=42)
+        out_name = "images"
 
     def barrier():
         if world > 1:
@@ -463,6 +491,8 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
                      "broadcast_ms": round(cs["ms"] / max(cs["broadcasts"], 1), 4),
                      "per_rank_units_per_s": {"min": round(float(lo.item()), 4), "max": round(float(hi.item()), 4)}}
     assert torch.isfinite(out).all()
+    if dump_dir is not None:
+        dump_outputs(dump_dir, {out_name: out}, rank, world)
 
     ms_per_step = elapsed / steps * 1e3
     units_per_s = Bg * steps / elapsed
@@ -476,13 +506,23 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
                        "hip_graph": None, **dist_info},
         }
         if cfg["family"] == "ldm":
-            # per-UNet-step ms: HIP events around apply_model (CFG batch = 2 x per-GPU batch), median of 20 warm calls
             nb = 2 * batch
+            result["config"].update(ddim_steps=cfg["steps"], cfg_scale=cfg["scale"], unet_batch_per_gpu=nb,
+                                    sampler=cfg["sampler"])
+            Pl = model.unet._plan(nb, h, w)
+            # what actually ran in the timed region: a captured hipGraph replay, or (capture failed / --no-graph) eager launches
+            result["config"]["hip_graph"] = Pl.graph is not None or getattr(Pl, "dup_graph", None) is not None
+            # (round 6) a guidance batch of >= ops option unet_cfg_dup rows runs conv_in .. the first self-attention on one half
+            # (UNetModel._dup_body): what the sampler's guidance call ran, and the op list its graph was captured from
+            dup = getattr(Pl, "dup_graph", None) is not None
+            result["config"]["cfg_dup_prefix"] = dup
+            if not full:        # a plain run ends here: everything below takes runs of its own
+                return result
+            # per-UNet-step ms: HIP events around apply_model (CFG batch = 2 x per-GPU batch), median of 20 warm calls
             ctx = torch.randn(nb, 77, cfg["ctx_dim"], device=device, dtype=torch.float16)
             xs = torch.randn(nb, model.unet.in_channels, h, w, device=device)     # (9 channels for the inpainting UNet)
             tsv = torch.full((nb,), 501.0, device=device)
-            # (round 6) what the sampler's guidance call ran: the guidance-duplicate prefix from ops option unet_cfg_dup rows on
-            dupkw = {"cfg_dup": True} if getattr(model.unet._plan(nb, h, w), "dup_graph", None) is not None else {}
+            dupkw = {"cfg_dup": True} if dup else {}
             if dupkw:
                 xs[batch:] = xs[:batch]
             for _ in range(3):
@@ -496,20 +536,11 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
                 evs.append((e0, e1))
             torch.cuda.synchronize()
             result["per_unet_step_ms"] = round(float(np.median([a.elapsed_time(b) for a, b in evs])), 3)
-            result["config"].update(ddim_steps=cfg["steps"], cfg_scale=cfg["scale"], unet_batch_per_gpu=nb,
-                                    sampler=cfg["sampler"])
             from minddiffusion_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
             # (the reference's uniform grid has range(0, 1000, 1000 // S) points: 50 for S = 50, 31 for S = 30)
             n_grid = len(make_ddim_timesteps("uniform", cfg["steps"], 1000, verbose=False)) if cfg["sampler"] != "dpm_solver" else cfg["steps"]
             n_evals = n_grid + (1 if cfg["sampler"] == "plms" else 0)
             tflop_per_unit = cfg["tflop_per_row"] * 2 * n_evals + cfg.get("vae_tflop", 0.0)   # CFG doubles the rows
-            Pl = model.unet._plan(nb, h, w)
-            # what actually ran in the timed region: a captured hipGraph replay, or (capture failed / --no-graph) eager launches
-            result["config"]["hip_graph"] = Pl.graph is not None or getattr(Pl, "dup_graph", None) is not None
-            # (round 6) a guidance batch of >= ops option unet_cfg_dup rows runs conv_in .. the first self-attention on one half
-            # (UNetModel._dup_body): profile the op list the sampler's graph was captured from
-            dup = getattr(Pl, "dup_graph", None) is not None
-            result["config"]["cfg_dup_prefix"] = dup
             fams = family_profile(Pl, Pl.dup_body, meta=Pl.dup_meta) if dup else family_profile(Pl, Pl.main[Pl.temb_ops:])
             roof = roofline_from_families(family_fractions(fams), f"one UNet evaluation at batch {nb}")
             gemm_launches = fams["gemm"]["launches"]
@@ -546,9 +577,11 @@ def run_config(config, args, rank, world, device, steps, warmup, cpu):
         else:
             # Taichu-GLIDE: one image = 60 guided base evaluations (UNet batch 2P) + 27 super-resolution evaluations (batch P);
             # profile both plans and weight them by their evaluation counts
-            tflop_per_unit = cfg["tflop_per_image"]
             Pb, Ps = dm.model._plan(2 * batch, 64, 64), sr.model._plan(batch, 256, 256)
             result["config"]["hip_graph"] = Pb.graph is not None and Ps.graph is not None
+            if not full:        # a plain run ends here: everything below takes runs of its own
+                return result
+            tflop_per_unit = cfg["tflop_per_image"]
             # (round 6) a step runs the plan's BODY only: the text transformer, the encoder_kv projections and the time-embedding
             # chain of all steps run once per loop (Text2ImUNet.begin_loop) and are timed below as `loop_prefix_ms`, not folded
             # into the per-family figures

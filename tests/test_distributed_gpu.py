@@ -148,14 +148,16 @@ def test_bench_two_ranks_contract():
     """bench.py's own N > 1 path (the driver launches it through torch.distributed.run on an 8-GPU node, which this box does
     not have): two ranks share the one GPU over gloo (MDX_DIST_BACKEND / MDX_BENCH_SHARE_GPU are test-only switches) and run
     the headline config for one timed trajectory each.  Checked: rank 0 prints exactly one JSON line, n_gpus = 2, the value is
-    the whole-job rate (global batch 2 per step over the max-over-ranks time), weak scaling, no CPU baseline at N > 1."""
+    the whole-job rate (global batch 2 per step over the max-over-ranks time), weak scaling, no CPU baseline at N > 1 (the
+    roofline checked here is part of the --full line)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MDX_DIST_BACKEND="gloo", MDX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -170,3 +172,28 @@ def test_bench_two_ranks_contract():
     assert c["dist_backend"] == "gloo" and c["rccl_world_size"] == 2 and c["broadcasts_per_step"] == 1
     assert c["broadcast_bytes"] > 2 * 77 * 1024 * 2 and c["broadcast_ms"] > 0
     assert 0 < c["per_rank_units_per_s"]["min"] <= c["per_rank_units_per_s"]["max"]
+
+
+def test_bench_plain_run_contract(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W`: exactly K timed steps, the headline fields only (per-UNet-step ms,
+    roofline, CPU baseline and the other configs take runs of their own and belong to --full), and --dump-outputs writes the
+    latents the last timed step returned, float32."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "512x512 txt2img latents/sec (50-step DDIM)" and d["unit"] == "latents/s" and d["higher_is_better"]
+    assert d["dtype"] == "f16" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 1 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+    assert d["config"]["hip_graph"] is True
+    assert not {"per_unet_step_ms", "roofline", "cpu_baseline", "other_configs"} & set(d)
+    assert sorted(os.listdir(tmp_path)) == ["latents.npy"]
+    a = np.load(tmp_path / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 4, 64, 64) and np.isfinite(a).all() and a.std() > 0

@@ -1023,6 +1023,25 @@ def test_bench_uses_the_committed_pmc_passes_only_for_the_launch_mix_they_were_t
     assert "mfma_busy" not in roof2 and "stale" in roof2["mfma_busy_note"]
 
 
+def test_bench_dump_outputs_float32_and_fixed_sample_above_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: each array the timed path returned becomes <name>.npy in float32 (an fp16 array exactly); one
+    above its share of the budget becomes a fixed, seeded sample of its elements (the same indices run after run, so that two
+    builds compare element for element); at N > 1 every rank writes <name>_rank<r>.npy."""
+    import bench
+    x = torch.randn(2, 3, 4).to(torch.float16)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents": x}, 0, 1)
+    a = np.load(tmp_path / "a" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 4) and np.array_equal(a, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 256)
+    big = torch.randn(1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"images": big}, 1, 2)
+    assert os.listdir(tmp_path / "b") == ["images_rank1.npy"]
+    s1, s2 = np.load(tmp_path / "b" / "images_rank1.npy"), np.load(tmp_path / "c" / "images_rank1.npy")
+    assert s1.dtype == np.float32 and s1.nbytes <= 256 // 2 and s1.size == 32
+    assert np.array_equal(s1, s2) and np.isin(s1, big.numpy()).all()
+
+
 def test_subpixel_conv_weight_is_the_upsampled_conv():
     """ops.subpixel_conv_weight (mdx_gemm_desc.w_sub): nearest-2x followed by a 3 x 3 conv, pad 1 (Upsample.construct,
     openaimodel.py:57-60) equals, for each output parity (dy, dx), a 2 x 2 conv of the low-resolution tensor at rows

@@ -15,10 +15,10 @@ for stage in "$@"; do
       cp gpurun_out/parity_log.jsonl $OUT/parity.jsonl 2>/dev/null
       timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1; tail -2 $OUT/smoke.txt ;;
     bench)
-      timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json; tail -3 $OUT/bench.err ;;
+      timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json; tail -3 $OUT/bench.err ;;
     configs)
       for cfg in wukong_512_plms sd2_768 glide_256 sd2_512_e2e; do
-        timeout 400 python bench.py --config $cfg --no-cpu-baseline --steps 2 > $OUT/bench_$cfg.json 2>> $OUT/bench.err
+        timeout 400 python bench.py --config $cfg --full --no-cpu-baseline --steps 2 > $OUT/bench_$cfg.json 2>> $OUT/bench.err
         python - <<PY
 import json
 try:

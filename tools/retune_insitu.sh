@@ -13,6 +13,6 @@ OLD=$PWD/minddiffusion_amd/libmdx_old.so
 for c in wukong_512_plms sd2_768 sd2_512 glide_256; do
   for v in old new old new; do
     if [ $v = old ]; then L=$OLD; else L=$PWD/minddiffusion_amd/libmdx.so; fi
-    MDX_LIBRARY=$L timeout 200 python bench.py --config $c --no-cpu-baseline --steps 1 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$c $v', r['value'], r.get('per_unet_step_ms'))"
+    MDX_LIBRARY=$L timeout 200 python bench.py --config $c --full --no-cpu-baseline --steps 1 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$c $v', r['value'], r.get('per_unet_step_ms'))"
   done
 done
