@@ -74,6 +74,17 @@ int mdx_nchw_to_nhwc_f16(const float* x, void* y, int B, int C, int H, int W, in
 /* x [B][H*W][Cstride] fp16 -> y [B][C][H][W] fp32 (first C channels). */
 int mdx_nhwc_to_nchw_f32(const void* x, float* y, int B, int C, int H, int W, int Cstride, mdx_stream_t s);
 
+/* ---- SRGAN post-upscaler of Taichu-GLIDE (Taichu-GLIDE/model/glide_text2im/model/srgan.py:75-117): the two 9 x 9 convs at the
+ *      ends of the Generator (the 3 x 3 trunk and the sub-pixel layers run on mdx_gemm_f16 with MDX_EPI_PRELU / MDX_OUT_D2S2).
+ * conv_in  (srgan.py:83-85):   x fp32 NCHW [B][3][H][W] -> out = PReLU(conv9x9(x) + bias), NHWC fp16 [B][H][W][64];
+ *                              w fp16 [64][3][9][9] (reference layout), bias / slope fp32 [64].
+ * conv_out (srgan.py:115-116): x NHWC fp16 [B][H][W][64] -> out = tanh(conv9x9(x) + bias), fp32 NCHW [B][3][H][W];
+ *                              w fp16 [3][64][9][9], bias fp32 [3].
+ * Zero "same" padding (4), stride 1; the input is rounded to fp16 inside conv_in, accumulation is fp32. */
+int mdx_srgan_conv_in_f16(const float* x, const void* w, const float* bias, const float* slope, void* out, int B, int H, int W,
+                          mdx_stream_t s);
+int mdx_srgan_conv_out_f32(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, mdx_stream_t s);
+
 /* ---- nn.GroupNorm(32,C,eps) [+ SiLU]  (ldm/modules/diffusionmodules/util.py:87-108,
  *      openaimodel.py:136-137,159-160,521-523; attention.py:83-84 eps 1e-6)
  * Input is the channel-concatenation of x1 [B][HW][C1] and optional x2 [B][HW][C2]
@@ -241,6 +252,11 @@ typedef struct mdx_gemm_desc {
     int xattn_len;
     int xattn_cap;
     float xattn_scale;
+    /* MDX_EPI_PRELU (SRGAN, Taichu-GLIDE model/glide_text2im/model/srgan.py:41-72,83-96): per-channel slope of column n =
+     * act_slope[n % act_slope_n] (fp32; act_slope_n % 8 == 0, N % act_slope_n == 0).  out = prelu(acc + bias) (+ residual): the
+     * residual is added AFTER the activation (Generator.conv2 + conv1, srgan.py:113).  No rowbias. */
+    const float* act_slope;
+    int act_slope_n;
 } mdx_gemm_desc;
 
 #define MDX_GEMM_WS_HEAD 16384 /* reserved bytes at the head of mdx_gemm_desc.workspace (the arrival counters' former home; their size) */
@@ -249,8 +265,13 @@ typedef struct mdx_gemm_desc {
                            (attention.py:41-51) */
 #define MDX_EPI_GELU 2  /* out = gelu_tanh(acc + bias)  (GLIDE text-transformer MLP, xf.py:52-59; SDv2 text encoder MLP) */
 #define MDX_EPI_QUICKGELU 3 /* out = x * sigmoid(1.702 x), x = acc + bias  (Wukong text encoder, WK text_encoder.py:67-74) */
+#define MDX_EPI_PRELU 4 /* out = x > 0 ? x : act_slope[n % act_slope_n] * x, x = acc + bias  (SRGAN nn.PReLU, srgan.py:41-117) */
 #define MDX_OUT_ROWMAJOR 0   /* out[m * out_ld + n] */
 #define MDX_OUT_TRANSPOSED 1 /* out[(b * N + n) * out_ld + tok]: V^T for mdx_attention_f16 */
+#define MDX_OUT_D2S2 2       /* depth-to-space by 2 in DCR order (MindSpore ops.DepthToSpace(2), srgan.py:60-72): N = 4 C, and column n of
+                                output pixel (b, y, x) goes to out[((b * 2 Ho + 2 y + q / 2) * 2 Wo + 2 x + q % 2) * out_ld + n % C],
+                                q = n / C; out_ld >= C is the pixel stride of the [B][2 Ho][2 Wo][out_ld] output.  C % 8 == 0; plain or
+                                PReLU epilogue, no residual / out_bs / n_split / statistics.  Runs on the generic kernel. */
 
 int mdx_gemm_f16(const mdx_gemm_desc* d, mdx_stream_t s);
 /* Frees the library-owned split-K arrival counters (nothing may be in flight); later launches allocate them again.  Every hipGraph

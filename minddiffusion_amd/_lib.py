@@ -39,6 +39,7 @@ class GemmDesc(ctypes.Structure):
         ("skip_a", c_void_p), ("skip_a2", c_void_p), ("skip_c1", c_int), ("skip_c2", c_int), ("skip_w", c_void_p),
         ("w_frag", c_int), ("stages", c_int), ("w_sub", c_void_p),
         ("xattn_k", c_void_p), ("xattn_vt", c_void_p), ("xattn_len", c_int), ("xattn_cap", c_int), ("xattn_scale", c_float),
+        ("act_slope", c_void_p), ("act_slope_n", c_int),
     ]
 
 
@@ -63,8 +64,8 @@ class StHeadDesc(ctypes.Structure):
     ]
 
 
-EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU = 0, 1, 2, 3
-OUT_ROWMAJOR, OUT_TRANSPOSED = 0, 1
+EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU, EPI_PRELU = 0, 1, 2, 3, 4
+OUT_ROWMAJOR, OUT_TRANSPOSED, OUT_D2S2 = 0, 1, 2
 
 # name -> (restype, argtypes); also the list the CPU test checks against include/mdx.h
 SIGNATURES = {
@@ -127,6 +128,8 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_glide_kv_select_f16": (c_int, [c_void_p, c_int, c_long, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_pack_b_operand_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "mdx_srgan_conv_in_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_srgan_conv_out_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_vae_gaussian_sample_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_softmax_rows_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_void_p]),
     "mdx_probe_mfma_32x32x16_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -561,7 +561,7 @@ bool mdx_conv8p_eligible(const GemmParams& p) {
     if (p.cin % 64 != 0 || (p.c2 > 0 && p.c1 % 64 != 0) || p.cin < 64) return false;
     if (p.H % 16 != 0 || p.W % 16 != 0) return false;
     if (p.out_mode != MDX_OUT_ROWMAJOR || p.epilogue != MDX_EPI_NONE || p.n_split || p.ln_stats || p.stats_out || p.out_bs ||
-        p.gn_cs)
+        p.gn_cs || p.d2s_c)      // (PReLU / depth-to-space: the generic kernel)
         return false;
     if (p.N % 8 != 0 || p.N < 64) return false;
     return true;

@@ -56,7 +56,9 @@ namespace {
 // and every A fragment becomes ONE packed fma per two halves (v_pk_fma_f16, single rounding) right after its ds_read: the
 // normalised tensor is never written or read, and the GroupNorm launch disappears.  An M tile lies inside one sample
 // (tokens per sample %% BM == 0, checked on the host).
-template <int BM, int BN, int BK, int NS, bool SWAP, bool FASTK, int NW, bool GNA = false>
+// EXT: the instantiations that carry the SRGAN epilogues (MDX_EPI_PRELU, MDX_OUT_D2S2; launch_ext) -- kept apart so that the
+// register allocation of the instantiations every other launch uses does not pay for them.
+template <int BM, int BN, int BK, int NS, bool SWAP, bool FASTK, int NW, bool GNA = false, bool EXT = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_kernel(const GemmParams p) {
     // NW = 4 (2 x 2 waves) or 8 (4 x 2 waves, BM = 128 only).  The 8-wave form is for grids of at most one block per
     // CU: a wave's K-step is a serial chain (wait -> barrier -> DMA issue -> ds_read -> MFMA), so a lone 4-wave block
@@ -456,7 +458,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_kernel(const Ge
     __syncthreads();  // all waves done with the ring before the epilogue reuses it
     trace_mark(p, 3);
     if constexpr (SWAP) asm volatile("" ::"v"(touch_ln), "v"(touch_s));      // (the touches above stay loads issued up there)
-    gemm_epilogue<BM, BN, SWAP, NW>(p, acc, smem, LinearRows{m0}, n0, split, bpre, tile_m, tile_id);
+    gemm_epilogue<BM, BN, SWAP, NW, LinearRows, 0, 0, EXT>(p, acc, smem, LinearRows{m0}, n0, split, bpre, tile_m, tile_id);
     trace_mark(p, 4);
 }
 
@@ -1027,7 +1029,8 @@ __device__ __forceinline__ void splitk_sum8(const GemmParams& p, const float* ba
     }
 }
 
-// split-K reduce + fused epilogue: one thread per (m, 8 output columns)
+// split-K reduce + fused epilogue: one thread per (m, 8 output columns).  EXT: the instantiation for PReLU / depth-to-space launches.
+template <bool EXT = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) {
     mdx_kernarg_touch<sizeof(GemmParams)>();
     const bool geglu = p.epilogue == MDX_EPI_GEGLU;
@@ -1098,6 +1101,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
             } else if (p.epilogue == MDX_EPI_QUICKGELU) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) f[e] = quick_gelu_f(f[e]);
+            } else if constexpr (EXT) {
+                if (p.epilogue == MDX_EPI_PRELU) {
+                    const float* sp = p.act_slope + oc % p.act_slope_n;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : sp[e] * f[e];
+                }
             }
         }
         if (p.out_mode == MDX_OUT_TRANSPOSED) {
@@ -1112,7 +1121,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
 #pragma unroll
             for (int e = 0; e < 8; ++e) p.out2[((size_t)b * nv + (oc - p.n_split + e)) * p.out2_ld + tok] = (f16)f[e];
         } else {
-            const f16x8 o = epilogue_apply_row8(p, f, m, oc, xtra);
+            const f16x8 o = epilogue_apply_row8<EXT>(p, f, m, oc, xtra);
             if (p.stats_out) {   // producer side of the LayerNorm fold, as in gemm_epilogue
                 float su = 0.f, sq = 0.f;
 #pragma unroll
@@ -1241,8 +1250,33 @@ int fill_params(const mdx_gemm_desc* d, GemmParams& p) {
     p.epilogue = d->epilogue;
     p.out_mode = d->out_mode;
     MDX_REQUIRE(p.epilogue == MDX_EPI_NONE || p.epilogue == MDX_EPI_GEGLU || p.epilogue == MDX_EPI_GELU ||
-                    p.epilogue == MDX_EPI_QUICKGELU, "mdx_gemm_f16: bad epilogue");
-    MDX_REQUIRE(p.out_mode == MDX_OUT_ROWMAJOR || p.out_mode == MDX_OUT_TRANSPOSED, "mdx_gemm_f16: bad out_mode");
+                    p.epilogue == MDX_EPI_QUICKGELU || p.epilogue == MDX_EPI_PRELU, "mdx_gemm_f16: bad epilogue");
+    MDX_REQUIRE(p.out_mode == MDX_OUT_ROWMAJOR || p.out_mode == MDX_OUT_TRANSPOSED || p.out_mode == MDX_OUT_D2S2,
+                "mdx_gemm_f16: bad out_mode");
+    p.act_slope = d->act_slope;
+    p.act_slope_n = d->act_slope_n;
+    p.d2s_c = 0;
+    if (p.epilogue == MDX_EPI_PRELU) {
+        MDX_REQUIRE(p.act_slope && p.act_slope_n > 0 && p.act_slope_n % 8 == 0 && p.N % p.act_slope_n == 0,
+                    "mdx_gemm_f16: PReLU needs act_slope and act_slope_n > 0 with act_slope_n %% 8 == 0 and N %% act_slope_n == 0");
+        MDX_REQUIRE(p.out_mode != MDX_OUT_TRANSPOSED && !d->rowbias && !d->n_split && !d->xattn_k,
+                    "mdx_gemm_f16: PReLU takes a row-major or depth-to-space store with bias (and residual) only");
+    }
+    if (p.epilogue == MDX_EPI_PRELU || p.out_mode == MDX_OUT_D2S2) {      // the generic kernel's EXT instantiations (launch_ext)
+        MDX_REQUIRE(d->c2 == 0 && d->c1 % 64 == 0 && !d->gn_colstats && !d->skip_w && !d->w_frag && !d->upsample,
+                    "mdx_gemm_f16: PReLU / depth-to-space launches take one source with Cin %% 64 == 0 (no fused GroupNorm / skip, "
+                    "tile-major weights, no upsample)");
+    }
+    if (p.out_mode == MDX_OUT_D2S2) {
+        // (a row-major launch to the tile programs: only the store index of epilogue_apply_row8 differs)
+        MDX_REQUIRE(p.N % 32 == 0 && p.out_ld >= p.N / 4 && (p.epilogue == MDX_EPI_NONE || p.epilogue == MDX_EPI_PRELU),
+                    "mdx_gemm_f16: depth-to-space store needs N = 4 C with C %% 8 == 0, out_ld >= C and a plain or PReLU epilogue");
+        MDX_REQUIRE(!d->residual && !d->out_bs && !d->n_split && !d->stats_out && !d->colstats_out && !d->ln_stats && !d->xattn_k &&
+                        !d->skip_w && !d->defer_reduce,
+                    "mdx_gemm_f16: depth-to-space store takes bias / time-embedding row / PReLU only");
+        p.d2s_c = p.N / 4;
+        p.out_mode = MDX_OUT_ROWMAJOR;
+    }
     if (p.epilogue == MDX_EPI_GEGLU) {
         MDX_REQUIRE(p.N % 128 == 0, "mdx_gemm_f16: GEGLU needs N %% 128 == 0");
         MDX_REQUIRE(p.out_mode == MDX_OUT_ROWMAJOR, "mdx_gemm_f16: GEGLU is row-major only");
@@ -1374,9 +1408,11 @@ static const TunedEntry g_tuned[] = {
 
 // Launch variant of a descriptor (tools/tune_gemm.py computes the same number from the mdx_gemm_desc fields).
 int tuned_variant(const GemmParams& p) {
-    return (p.c2 > 0 ? 1 : 0) | (p.epilogue << 1) | (p.n_split ? 8 : 0) | (p.ln_stats ? 16 : 0) | (p.stats_out ? 32 : 0) |
+    // (epilogue in bits 1-2 for NONE .. QUICKGELU; PReLU = 4 would reach the n_split bit and has a bit of its own)
+    return (p.c2 > 0 ? 1 : 0) | (p.epilogue == MDX_EPI_PRELU ? 2048 : p.epilogue << 1) | (p.n_split ? 8 : 0) | (p.ln_stats ? 16 : 0) |
+           (p.stats_out ? 32 : 0) |
            (p.out_mode == MDX_OUT_TRANSPOSED ? 64 : 0) | (p.colstats_out ? 128 : 0) | (p.residual ? 256 : 0) |
-           (p.rowbias ? 512 : 0);
+           (p.rowbias ? 512 : 0) | (p.d2s_c ? 1024 : 0);
 }
 
 bool halo_eligible(const GemmParams& p, int bm);
@@ -1384,6 +1420,7 @@ bool halo_eligible(const GemmParams& p, int bm);
 const TunedEntry* lookup_tuned(const GemmParams& p) {
     const bool use_table = mdx_opt(MDX_OPT_GEMM_TUNED) && !mdx_opt(MDX_OPT_GEMM_BM) && !mdx_opt(MDX_OPT_GEMM_BN);
     if (!use_table || p.bn_hint || p.st_hint || p.stride != 1 || p.upsample) return nullptr;
+    if (p.epilogue == MDX_EPI_PRELU || p.d2s_c) return nullptr;      // (SRGAN launches: no measured rows; a var1 = 0 row says nothing)
     const int var1 = tuned_variant(p) + 1;
     const TunedEntry* any = nullptr;
     for (const TunedEntry* e = g_tuned; e->M; ++e)
@@ -1502,17 +1539,28 @@ Tiling choose_tiling(const GemmParams& p, int bn, int forced_ns, int forced_bm) 
     return best;
 }
 
-template <int BM, int BN, int BK, int NS, bool SWAP, bool FASTK, int NW>
+template <int BM, int BN, int BK, int NS, bool SWAP, bool FASTK, int NW, bool EXT = false>
 void launch_one(const GemmParams& p, dim3 grid, hipStream_t st) {
     constexpr size_t ring = (size_t)NS * (BM + BN) * BK * 2;
     constexpr size_t epi = (size_t)(BM > BN ? BM : BN) * ((BM > BN ? BN : BM) + 8) * 2 + 4096;  // staged C tile
     constexpr size_t lds = ring > epi ? ring : epi;
     static MdxPerDeviceOnce attr_once;
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, BK, NS, SWAP, FASTK, NW>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, BK, NS, SWAP, FASTK, NW, false, EXT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, NS, SWAP, FASTK, NW>), grid, dim3(NW * 64), lds, st, p);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, NS, SWAP, FASTK, NW, false, EXT>), grid, dim3(NW * 64), lds, st, p);
+}
+
+// SRGAN launches (PReLU / depth-to-space; fill_params: single source, Cin % 64 == 0): the EXT instantiations, four waves, ring depth
+// 2 | 3 (a deeper ring or the eight-wave form of the tile table / overrides runs at depth 3 on four waves: same tile program, same bits)
+template <int BM, int BN>
+void launch_ext(const GemmCfg& c, const GemmParams& p, bool swap, dim3 grid, hipStream_t st) {
+    if (c.ns >= 3) {
+        if (swap) launch_one<BM, BN, 64, 3, true, true, 4, true>(p, grid, st); else launch_one<BM, BN, 64, 3, false, true, 4, true>(p, grid, st);
+    } else {
+        if (swap) launch_one<BM, BN, 64, 2, true, true, 4, true>(p, grid, st); else launch_one<BM, BN, 64, 2, false, true, 4, true>(p, grid, st);
+    }
 }
 
 // GNA form (GroupNorm of the input on the A fragments): four waves, ring depth 2 | 3, K-contiguous (dense) launches only
@@ -1620,10 +1668,20 @@ bool halo8_eligible(const GemmParams& p) {
     return p.H == 8 && p.W == 8;
 }
 
+// Epilogues the HALO kernel's store loop implements.  The batched patch loops (HALO_EMODE 2) carry the plain and GEGLU stores only:
+// a GELU / QuickGELU / PReLU launch or a depth-to-space store must resolve to the generic kernel, which implements them, instead
+// of storing un-activated values.  The per-pass loops (HALO_EMODE 0) are the generic kernel's and implement GELU / QuickGELU.
+static bool halo_epilogue_ok(const GemmParams& p) {
+    if (p.epilogue == MDX_EPI_PRELU || p.d2s_c) return false;      // (the generic kernel's EXT instantiations only)
+    if (HALO_EMODE == 0) return true;
+    return p.epilogue == MDX_EPI_NONE || p.epilogue == MDX_EPI_GEGLU;
+}
+
 // The HALO kernel applies to 3x3 / stride 1 / single-source convs whose image tiles into 8 x 16 (16 x 16) patches, or
 // whose images are 8 x 8 (bm = 128 only).
 bool halo_eligible(const GemmParams& p, int bm) {
     if (!mdx_opt(MDX_OPT_GEMM_HALO)) return false;
+    if (!halo_epilogue_ok(p)) return false;
     if (!(p.ksize == 3 && p.stride == 1 && !p.upsample && p.c2 == 0 && p.cin % 64 == 0 && p.out_mode == MDX_OUT_ROWMAJOR))
         return false;
     if (p.out_bs) return false;      // (no conv writes a strided-sample output; the patch epilogue does not carry the form)
@@ -1962,7 +2020,8 @@ static int mdx_internal_resolve_check(const mdx_gemm_desc* d, GemmParams& p) {
 // Rows per colstats_out row block this launch would produce (0 = it cannot): the M tile for a single-pass launch (a HALO
 // patch is one row block), CS_ROWS for a split-K launch; a row block never straddles two samples.
 static int colstats_rows(const GemmParams& p, const Resolved& r) {
-    if (p.out_mode != MDX_OUT_ROWMAJOR || p.epilogue != MDX_EPI_NONE || p.n_split || p.ln_stats || p.stats_out || p.out_bs)
+    if (p.out_mode != MDX_OUT_ROWMAJOR || p.epilogue != MDX_EPI_NONE || p.n_split || p.ln_stats || p.stats_out || p.out_bs ||
+        p.d2s_c)
         return 0;
     if (r.ns > 1 && !r.fixup) return p.HoWo % CS_ROWS == 0 ? CS_ROWS : 0;
     if (r.halo) return halo8_eligible(p) && r.c.bm == 128 ? 0 : r.c.bm;
@@ -1975,7 +2034,7 @@ static int colstats_rows(const GemmParams& p, const Resolved& r) {
 static bool lean_dense_eligible(const GemmParams& p, bool swap, bool fastk, bool nw8, int ntiles) {
     if (!mdx_opt(MDX_OPT_GEMM_LEAN_DENSE) || !p.dense_issue) return false;
     if (!(p.ksize == 1 && p.stride == 1 && !p.upsample && p.c2 == 0 && fastk && swap && !nw8)) return false;
-    if (p.gn_cs || p.rowbias || p.out_bs || p.skip_w) return false;
+    if (p.gn_cs || p.rowbias || p.out_bs || p.skip_w || p.d2s_c) return false;
     if (p.epilogue != MDX_EPI_NONE && p.epilogue != MDX_EPI_GEGLU) return false;
     // buffer descriptors of the epilogue prefetches: 32-bit offsets
     if ((size_t)p.M * (size_t)(p.residual ? p.residual_ld : 0) * 2 >= 0x80000000ull) return false;
@@ -2171,6 +2230,13 @@ extern "C" int mdx_gemm_f16(const mdx_gemm_desc* d, mdx_stream_t s) {
             if (bn == 128) launch_gna<128, 128>(p, gns, swap, grid, st); else launch_gna<128, 64>(p, gns, swap, grid, st);
         }
         ok = true;
+    } else if (p.epilogue == MDX_EPI_PRELU || p.d2s_c) {      // SRGAN epilogues: the EXT instantiations
+        if (cc.bm == 64) {
+            if (bn == 128) launch_ext<64, 128>(cc, p, swap, grid, st); else launch_ext<64, 64>(cc, p, swap, grid, st);
+        } else {
+            if (bn == 128) launch_ext<128, 128>(cc, p, swap, grid, st); else launch_ext<128, 64>(cc, p, swap, grid, st);
+        }
+        ok = true;
     } else if (lg.lean && mdx_dense_launch(p, cc.bm, bn, cc.ns, grid, st)) {
         ok = true;      // dense.hip: the same tile program with a division-free prologue and the epilogue's reads prefetched
     } else if (cc.bm == 64)
@@ -2187,8 +2253,10 @@ extern "C" int mdx_gemm_f16(const mdx_gemm_desc* d, mdx_stream_t s) {
         if (p.colstats_out)
             hipLaunchKernelGGL(splitk_reduce_colstats_kernel, dim3((p.N + 63) / 64, (p.M + CS_ROWS - 1) / CS_ROWS), dim3(256), 0,
                                st, p);
+        else if (p.epilogue == MDX_EPI_PRELU || p.d2s_c)
+            hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, p);
         else
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p);
+            hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, p);
         MDX_LAUNCH_CHECK("mdx_gemm_f16(splitk reduce)");
     }
     return MDX_OK;

@@ -70,6 +70,11 @@ struct GemmParams {
     const f16* xa_vt;        // [B][N][xa_cap]
     int xa_len, xa_cap;
     float xa_scale_log2;     // scale * log2(e)
+    // SRGAN (mdx_gemm_desc.act_slope, MDX_OUT_D2S2): PReLU slopes of the generic store loop; d2s_c = C of a depth-to-space output
+    // (0 = none; such a launch runs with out_mode ROWMAJOR and the store index of epilogue_apply_row8)
+    const float* act_slope;
+    int act_slope_n;
+    int d2s_c;
 };
 
 }  // namespace mdx_int
@@ -120,6 +125,9 @@ __device__ __forceinline__ Row8Extras epilogue_prefetch_row8(const GemmParams& p
     return x;
 }
 
+// EXT: the launch may carry the SRGAN store forms (MDX_OUT_D2S2).  Only the EXT instantiations of the generic kernel and of the split-K
+// reduce compile that branch, so the register allocation of every other kernel is untouched by it.
+template <bool EXT = false>
 __device__ __forceinline__ f16x8 epilogue_apply_row8(const GemmParams& p, float (&f)[8], int m, int n, const Row8Extras& x) {
     if (p.rowbias) {
         f[0] += x.r0.x; f[1] += x.r0.y; f[2] += x.r0.z; f[3] += x.r0.w;
@@ -136,6 +144,15 @@ __device__ __forceinline__ f16x8 epilogue_apply_row8(const GemmParams& p, float 
     if (p.out_bs) {
         const int b = m / p.HoWo;
         row = (size_t)b * p.out_bs + (size_t)(m - b * p.HoWo) * p.out_ld;
+    } else if constexpr (EXT) {
+        if (p.d2s_c) {      // MDX_OUT_D2S2: sub-pixel q = n / C of low-resolution pixel (b, y, x) -> (2 y + q / 2, 2 x + q % 2)
+            const int b = m / p.HoWo;
+            const int r = m - b * p.HoWo;
+            const int y = r / p.Wo, x = r - (r / p.Wo) * p.Wo;
+            const int q = n / p.d2s_c;
+            n -= q * p.d2s_c;
+            row = (((size_t)b * 2 * p.Ho + 2 * y + (q >> 1)) * (size_t)(2 * p.Wo) + 2 * x + (q & 1)) * p.out_ld;
+        }
     }
     *reinterpret_cast<f16x8*>(p.out + row + n) = o;
     return o;
@@ -335,7 +352,7 @@ __device__ __forceinline__ bool splitk_last_block_reduce(const GemmParams& p, f3
 // PW = 16: out_bs is excluded by halo_eligible, and every row of a patch lies in ONE sample, so the per-sample row bias -- the
 // time-embedding term of a ResBlock's first conv, openaimodel.py:188-190 -- is one row of 8 floats per thread for the whole tile
 // instead of a division and two loads per pass).
-template <int BM, int BN, bool SWAP, int NW, class RowMap, int NXPRE = 0, int EMODE = 0>
+template <int BM, int BN, bool SWAP, int NW, class RowMap, int NXPRE = 0, int EMODE = 0, bool EXT = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)[BM / (16 * NW)][BN / 64], char* smem,
                                               const RowMap rm, const int n0, const int split, const float (&bpre)[16],
                                               const int row_block = 0, const int tile_lin = 0, const float* ln_pre = nullptr,
@@ -730,8 +747,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
                         const f16x8 v = *reinterpret_cast<const f16x8*>(&stg[row * SLD + chunk * 8]);
                         float f[8];
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) f[e] = act((float)v[e] + bb[e]);
-                        const f16x8 o = epilogue_apply_row8(p, f, m, n, xa);
+                        for (int e = 0; e < 8; ++e) f[e] = act((float)v[e] + bb[e], e);
+                        const f16x8 o = epilogue_apply_row8<EXT>(p, f, m, n, xa);
                         if (colstats) {
 #pragma unroll
                             for (int e = 0; e < 8; ++e) {
@@ -764,11 +781,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
             if constexpr (!LEAN) {
                 const int epi = __builtin_amdgcn_readfirstlane(p.epilogue);
                 if (epi == MDX_EPI_NONE)
-                    store_rows([](float x) { return x; });
+                    store_rows([](float x, int) { return x; });
                 else if (epi == MDX_EPI_GELU)
-                    store_rows([](float x) { return gelu_tanh_f(x); });
-                else
-                    store_rows([](float x) { return quick_gelu_f(x); });
+                    store_rows([](float x, int) { return gelu_tanh_f(x); });
+                else if (!EXT || epi == MDX_EPI_QUICKGELU)
+                    store_rows([](float x, int) { return quick_gelu_f(x); });
+                else if constexpr (EXT) {      // MDX_EPI_PRELU: this thread's 8 columns share one slope row for every pass
+                    float sl[8];
+                    const float* sp = p.act_slope + (n < p.N ? n % p.act_slope_n : 0);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) sl[e] = sp[e];
+                    store_rows([&](float x, int e) { return x > 0.f ? x : sl[e] * x; });
+                }
             }
             if (colstats) {   // (block-uniform) fold the RPP row lanes of every column in a fixed order: deterministic
                 __syncthreads();                                  // every thread is done reading the staged tile

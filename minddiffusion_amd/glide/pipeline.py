@@ -20,8 +20,11 @@ from .main_funcs import ddim_sample_loop, gaussian_p_sample_loop
 
 
 class GlidePipeline:
-    def __init__(self, diffusion_model, super_res_model, text_ctx=128, vocab_len=50001):
+    def __init__(self, diffusion_model, super_res_model, text_ctx=128, vocab_len=50001, srgan=None):
+        """srgan: optional post-upscaler (glide/model/srgan.py Generator, or srgan_util.SRGAN) run by __call__(upscale=True) --
+        the CLI's srgan.sr_handle(samples) (txt2img.py:129-130)."""
         self.dm, self.sr = diffusion_model, super_res_model
+        self.srgan = srgan
         self.text_ctx, self.vocab_len = int(text_ctx), int(vocab_len)
         self.device = diffusion_model.model.device
 
@@ -45,9 +48,13 @@ class GlidePipeline:
         return torch.stack(x0), torch.stack(per_step, 1).contiguous(), torch.stack(up0)
 
     def __call__(self, tokens=None, mask=None, seed=0, tokens_up=None, mask_up=None, uncond_tokens=None, gather=False,
-                 base_only=False):
+                 base_only=False, upscale=False):
         """tokens / mask [P_global, text_ctx] int (rank 0; None elsewhere).  Returns this rank's images
-        [P_local, 3, 256, 256] (or, with gather=True, all of them on rank 0 and None elsewhere)."""
+        [P_local, 3, 256, 256] (or, with gather=True, all of them on rank 0 and None elsewhere).  upscale=True (needs
+        `srgan`): the SRGAN output of those images instead, [P_local, 3, 4 S, 4 S] fp32 in tanh range; the up-sampler's images
+        of the same call stay on self.last_up256.  Each rank upscales its own images."""
+        if upscale and self.srgan is None:
+            raise ValueError("GlidePipeline: upscale=True needs an srgan post-upscaler")
         rank, n = D.world()
         P_local = int(self.dm.pics_generated)
         P = P_local * n
@@ -65,4 +72,8 @@ class GlidePipeline:
         out = base if base_only else ddim_sample_loop(self.sr, tuple(up0.shape), base, tok_up, msk_up,
                                                       int(self.sr.num_timesteps), noise=up0)
         self.last_uncond_tokens = unc
+        if upscale:
+            self.last_up256 = out
+            # (SRGAN.sr_handle returns a fresh tensor; a bare Generator returns its plan's buffer)
+            out = self.srgan.sr_handle(out.contiguous()) if hasattr(self.srgan, "sr_handle") else self.srgan(out.contiguous()).clone()
         return D.gather_latents(out) if (gather and n > 1) else out

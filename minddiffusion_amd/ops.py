@@ -7,6 +7,7 @@ import torch
 
 from . import _lib
 from ._lib import GemmDesc, EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU, OUT_ROWMAJOR, OUT_TRANSPOSED  # noqa: F401
+from ._lib import EPI_PRELU, OUT_D2S2  # noqa: F401
 
 f16 = torch.float16
 f32 = torch.float32
@@ -396,7 +397,7 @@ def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, 
                    stats_out=None, ln_stats=None, ln_s=None, ln_eps=1e-5, tile_m=0, tile_n=0, colstats_out=None, stages=0,
                    w_frag=0, skip_a=None, skip_a2=None, skip_c1=0, skip_c2=0, skip_w=None, gn_colstats=None, gn_nrb=0,
                    gn_gamma=None, gn_beta=None, gn_eps=1e-5, gn_silu=1, w_sub=None, xattn_k=None, xattn_vt=None, xattn_len=0,
-                   xattn_cap=0, xattn_scale=0.0):
+                   xattn_cap=0, xattn_scale=0.0, act_slope=None):
     d = GemmDesc()
     d.a = a.data_ptr()
     d.a2 = 0 if a2 is None else a2.data_ptr()
@@ -438,6 +439,8 @@ def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, 
     if xattn_k is not None:      # cross-attention as the epilogue of the query projection (include/mdx.h)
         d.xattn_k, d.xattn_vt = xattn_k.data_ptr(), xattn_vt.data_ptr()
         d.xattn_len, d.xattn_cap, d.xattn_scale = int(xattn_len), int(xattn_cap), float(xattn_scale)
+    if act_slope is not None:    # MDX_EPI_PRELU: per-channel slopes, fp32 [C], column n uses act_slope[n % C]
+        d.act_slope, d.act_slope_n = act_slope.data_ptr(), int(act_slope.numel())
     return d
 
 
@@ -605,6 +608,9 @@ def gemm(a, w, N, B, H, W, c1, out=None, **kw):
         if out_mode == OUT_TRANSPOSED:
             ld = kw.pop("out_ld", Ho * Wo)
             out = torch.zeros((B, N, ld), dtype=f16, device=a.device)
+        elif out_mode == OUT_D2S2:
+            ld = kw.pop("out_ld", N // 4)
+            out = torch.empty((B, 2 * Ho, 2 * Wo, ld), dtype=f16, device=a.device)
         else:
             cols = N // 2 if epi == EPI_GEGLU else N
             ld = kw.pop("out_ld", cols)
@@ -716,6 +722,29 @@ def softmax_rows(x2d, scale):
     _lib.check(_lib.load().mdx_softmax_rows_f16(_ptr(x2d), x2d.stride(0), rows, cols, float(scale), _stream()),
                "mdx_softmax_rows_f16")
     return x2d
+
+
+def srgan_conv_in(x, w, bias, slope, out=None):
+    """SRGAN Generator.conv1 (srgan.py:83-85): fp32 NCHW image [B, 3, H, W] -> PReLU(conv9x9(x) + bias), NHWC fp16 [B, H, W, 64].
+    w: fp16 [64, 3, 9, 9] (reference layout), bias / slope fp32 [64]."""
+    _chk(x, f32, "x"); _chk(w, f16, "w"); _chk(bias, f32, "bias"); _chk(slope, f32, "slope")
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, 64), dtype=f16, device=x.device)
+    _lib.check(_lib.load().mdx_srgan_conv_in_f16(_ptr(x), _ptr(w), _ptr(bias), _ptr(slope), _ptr(out), B, H, W, _stream()),
+               "mdx_srgan_conv_in_f16")
+    return out
+
+
+def srgan_conv_out(x, w, bias, B, H, W, out=None):
+    """SRGAN Generator.conv3 + tanh (srgan.py:115-116): NHWC fp16 [B, H, W, 64] -> tanh(conv9x9(x) + bias), fp32 NCHW [B, 3, H, W].
+    w: fp16 [3, 64, 9, 9] (reference layout), bias fp32 [3]."""
+    _chk(x, f16, "x"); _chk(w, f16, "w"); _chk(bias, f32, "bias")
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=f32, device=x.device)
+    _lib.check(_lib.load().mdx_srgan_conv_out_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(out), B, H, W, _stream()),
+               "mdx_srgan_conv_out_f32")
+    return out
 
 
 def vae_gaussian_sample(moments, zc, noise, out):

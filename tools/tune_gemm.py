@@ -28,9 +28,9 @@ NS_CANDIDATES = [1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 20]
 
 def variant(d):
     """Launch variant of a descriptor: gemm.hip tuned_variant()."""
-    return ((1 if d.c2 > 0 else 0) | (d.epilogue << 1) | (8 if d.n_split else 0) | (16 if d.ln_stats else 0)
+    return ((1 if d.c2 > 0 else 0) | (2048 if d.epilogue == 4 else d.epilogue << 1) | (8 if d.n_split else 0) | (16 if d.ln_stats else 0)
             | (32 if d.stats_out else 0) | (64 if d.out_mode == 1 else 0) | (128 if d.colstats_out else 0)
-            | (256 if d.residual else 0) | (512 if d.rowbias else 0))
+            | (256 if d.residual else 0) | (512 if d.rowbias else 0) | (1024 if d.out_mode == 2 else 0))
 
 
 def time_desc(ops, d, flush, reps, pre=()):
