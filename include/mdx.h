@@ -193,7 +193,10 @@ typedef struct mdx_gemm_desc {
                              reuses the workspace).  mdx_gemm_f16 fails if the launch does not split. */
     int tile_m;           /* 0 = auto (tuned table, then the cost model); 64 | 128 forces the M tile.  For tools/tune_gemm.py,
                              which measures the (tile_m, splitk) candidates of every UNet shape on the device. */
-    int tile_n;           /* 0 = auto; 64 | 128 forces the N tile (same purpose; GEGLU always uses 128) */
+    int tile_n;           /* 0 = auto; 64 | 128 forces the N tile (same purpose; GEGLU uses 128 with geglu_unit 0 / 64).  160 with
+                             tile_m = 128: the 128 x 160 tile of the lean dense kernel (four waves 4 x 1) -- dense row-major launches
+                             with bias / residual / GEGLU (geglu_unit = 80) / LayerNorm-fold consumer, unsplit; anything else is
+                             refused with tile_n = 160 */
     /* nn.GroupNorm(32) [+ SiLU] of the conv's INPUT applied inside the conv (openaimodel.py:136-138, 159-163: GroupNorm -> SiLU ->
      * Conv2d): gn_colstats = the column partials the input's producer emitted (mdx_gemm_desc.colstats_out /
      * mdx_st_tail_desc.colstats_out: [B * gn_nrb][Cin][2]), gn_gamma / gn_beta fp32 [Cin].  Every block folds its sample's
@@ -257,12 +260,17 @@ typedef struct mdx_gemm_desc {
      * residual is added AFTER the activation (Generator.conv2 + conv1, srgan.py:113).  No rowbias. */
     const float* act_slope;
     int act_slope_n;
+    /* MDX_EPI_GEGLU only: the packing unit of `w` / `bias` / `ln_s` -- every 2 * unit consecutive packed columns are `unit` 'a' columns
+     * followed by their `unit` gate columns.  0 (= 64): the 128-column tiles; 80: the 128 x 160 tile of the lean dense kernel
+     * (N %% 160 == 0).  The unit must be the one of the tile that runs: a descriptor whose unit does not match the resolved tile_n is
+     * refused (MDX_E_INVALID) by mdx_gemm_check / mdx_gemm_query / mdx_gemm_f16 -- a mismatch would pair the wrong columns silently. */
+    int geglu_unit;
 } mdx_gemm_desc;
 
 #define MDX_GEMM_WS_HEAD 16384 /* reserved bytes at the head of mdx_gemm_desc.workspace (the arrival counters' former home; their size) */
 #define MDX_EPI_NONE 0
 #define MDX_EPI_GEGLU 1 /* out[m][j] = a * gelu_tanh(g); packed so that each 128-wide N tile = 64 'a' | 64 'gate' cols
-                           (attention.py:41-51) */
+                           (attention.py:41-51); mdx_gemm_desc.geglu_unit = 80: 80 'a' | 80 'gate' per 160-wide tile */
 #define MDX_EPI_GELU 2  /* out = gelu_tanh(acc + bias)  (GLIDE text-transformer MLP, xf.py:52-59; SDv2 text encoder MLP) */
 #define MDX_EPI_QUICKGELU 3 /* out = x * sigmoid(1.702 x), x = acc + bias  (Wukong text encoder, WK text_encoder.py:67-74) */
 #define MDX_EPI_PRELU 4 /* out = x > 0 ? x : act_slope[n % act_slope_n] * x, x = acc + bias  (SRGAN nn.PReLU, srgan.py:41-117) */
@@ -295,7 +303,8 @@ size_t mdx_gemm_workspace_bytes(const mdx_gemm_desc* d);
 int mdx_gemm_check(const mdx_gemm_desc* d);
 /* What mdx_gemm_f16 WOULD launch for this descriptor (host only, nothing is launched):
  * out7 = {tile_m, tile_n, splitk, kernel (0 = generic implicit GEMM, 1 = HALO 3x3 conv, 2 = the lean dense kernel), 1 if the choice came from the
- * measured tile table csrc/gemm_tuned.inc, rows per colstats_out row block (0 = this launch cannot produce column
+ * measured tile table csrc/gemm_tuned.inc (0 for a row of csrc/gemm_tuned160.inc, the table of the 128 x 160 tile: tile_n = 160
+ * says so), rows per colstats_out row block (0 = this launch cannot produce column
  * statistics), 1 if a split launch reduces in the kernel (no reduce launch follows)}.  The parity tests assert with it that
  * the table rows are hit at the benchmarked shapes. */
 int mdx_gemm_query(const mdx_gemm_desc* d, int* out7);

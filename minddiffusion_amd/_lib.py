@@ -40,6 +40,7 @@ class GemmDesc(ctypes.Structure):
         ("w_frag", c_int), ("stages", c_int), ("w_sub", c_void_p),
         ("xattn_k", c_void_p), ("xattn_vt", c_void_p), ("xattn_len", c_int), ("xattn_cap", c_int), ("xattn_scale", c_float),
         ("act_slope", c_void_p), ("act_slope_n", c_int),
+        ("geglu_unit", c_int),
     ]
 
 

@@ -17,7 +17,9 @@
 //     after the K loop in the partials' order, so the statistics keep their bits) and S[n] -- so that the epilogue of a lone block is
 //     staging + arithmetic + stores.
 // Launch forms covered: row-major output, unsplit or in-kernel split-K reduce (tickets), bias / residual / GEGLU / row statistics /
-// column statistics / LayerNorm-fold consumer / the q|k row-major + V^T split store.  Everything else (per-sample row bias, out_bs,
+// column statistics / LayerNorm-fold consumer / the q|k row-major + V^T split store.  The 128 x 160 tile (four waves 4 x 1, epilogue_w41
+// below; round 7) cuts M = 512 x N = 10240 and M = 2048 x N = 5120 into exactly 256 / 512 equal blocks: bias / residual / GEGLU /
+// LayerNorm-fold consumer, unsplit.  Everything else (per-sample row bias, out_bs,
 // GELU activations, transposed output, slab split-K, the GroupNorm-on-A form, eight waves) stays on the generic kernel.
 #include "mdx_common.h"
 #include "gemm_internal.h"
@@ -161,13 +163,156 @@ __device__ __forceinline__ void xattn_tile_epilogue(const GemmParams& p, char* s
     }
 }
 
+// Epilogue of the 128 x 160 tile (four waves 4 x 1: wave w owns rows 32 w .. 32 w + 31 of the tile and all BN columns, five 32 x 32
+// accumulator tiles).  The arithmetic is gemm_epilogue's EMODE 1 -- LayerNorm-fold correction in fp32 in the accumulator registers, fp16
+// staging, then per 8 columns  fp16(float(staged) + bias [+ residual])  or the GEGLU product -- on the same values in the same order:
+// a launch on this tile gives the bits of the 64- / 128-column tiles (tests/test_dense_tile160_gpu.py).  What differs is the index
+// work: BN / 8 = 20 (GEGLU: 10) chunks per row do not divide 256 threads, so the store loops run over the flat item index
+// tid + 256 * pass (BM * BN / 8 / 256 = 10 passes, GEGLU 5: no idle lane, consecutive lanes on consecutive 16-byte chunks of a row)
+// and the chunk of a thread changes from pass to pass -- the tile's bias columns therefore go through LDS (one dword per thread,
+// fetched before the K loop together with the column's S[n] of the LayerNorm fold) instead of 16 registers.  GEGLU pairs column j with column j + BN / 2 of the tile (mdx_gemm_desc.geglu_unit
+// = 80).  Not carried (the resolver keeps such launches on the other tiles): split-K tickets, row / column statistics, the q|k + V^T
+// split store, the cross-attention epilogue.
+template <int BM, int BN>
+__device__ __forceinline__ void epilogue_w41(const GemmParams& p, f32x16 (&acc)[BN / 32], char* smem, const int m0, const int n0,
+                                             const float bias_pre, const float lns_pre) {
+    constexpr int NT = 256, TN = BN / 32, SLD = BN + 8;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hi = lane >> 5, l31 = lane & 31;
+    f16* stg = reinterpret_cast<f16*>(smem);
+    float* lnrow = reinterpret_cast<float*>(smem + (size_t)BM * SLD * 2);      // [BM][2] mean, rstd
+    float* lns = lnrow + 2 * BM;                                               // [BN] S[n]
+    float* bs = lns + BN;                                                      // [BN] bias (zeros when the launch has none)
+    if (tid < BN) bs[tid] = bias_pre;
+    const int m_l = wave * 32 + l31;
+    if (p.ln_stats) {
+        for (int r = tid; r < BM; r += NT) {
+            float mr[2];
+            gemm_ln_row_fold(p, m0 + r, mr);
+            lnrow[2 * r] = mr[0];
+            lnrow[2 * r + 1] = mr[1];
+        }
+        if (tid < BN) lns[tid] = lns_pre;      // S[n0 + tid], fetched before the K loop (zero past N)
+        __syncthreads();
+        const float mean = lnrow[2 * m_l], rstd = lnrow[2 * m_l + 1];
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int n_l = j * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
+                acc[j][r] = rstd * (acc[j][r] - mean * lns[n_l]);
+            }
+    }
+    const bool geglu = p.epilogue == MDX_EPI_GEGLU;
+    // plain store: the residual rows of ALL the thread's passes requested in front of the staging pass, through a descriptor that
+    // answers zero when there is no residual (GEGLU with a residual is not a shape of the models: fetched in its loop)
+    constexpr int CH = BN / 8, PASSES = BM * CH / NT;
+    static_assert(BM * CH % NT == 0 && BM * (CH / 2) % NT == 0, "store loops: whole passes");
+    const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(p.residual, (p.residual && !geglu) ? p.res_bytes : 0u);
+    f16x8 lres[PASSES];
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+        const int idx = tid + pass * NT;
+        const int row = idx / CH, c = idx - row * CH;
+        const int m = m0 + row, n = n0 + c * 8;
+        const unsigned off = (m < p.M && n < p.N) ? ((unsigned)m * (unsigned)p.residual_ld + (unsigned)n) * 2u : MDX_OOB;
+        lres[pass] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n_l = j * 32 + 8 * g + 4 * hi;
+            *reinterpret_cast<f16x4*>(&stg[m_l * SLD + n_l]) =
+                cvt4(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]);
+        }
+    __syncthreads();
+    trace_mark(p, 5);
+    if (geglu) {
+        // tile = BN / 2 'a' columns | BN / 2 gate columns -> BN / 2 outputs at column n0 / 2
+        constexpr int U = BN / 2, GCH = U / 8, GP = BM * GCH / NT;
+        const bool has_res = p.residual != nullptr;      // uniform
+        f16x8 va[GP], vg[GP];
+        f32x4 ba[GP][2], bg[GP][2];
+#pragma unroll
+        for (int pass = 0; pass < GP; ++pass) {
+            const int idx = tid + pass * NT;
+            const int row = idx / GCH, c = idx - row * GCH;
+            va[pass] = *reinterpret_cast<const f16x8*>(&stg[row * SLD + c * 8]);
+            vg[pass] = *reinterpret_cast<const f16x8*>(&stg[row * SLD + U + c * 8]);
+            ba[pass][0] = *reinterpret_cast<const f32x4*>(&bs[c * 8]);
+            ba[pass][1] = *reinterpret_cast<const f32x4*>(&bs[c * 8 + 4]);
+            bg[pass][0] = *reinterpret_cast<const f32x4*>(&bs[U + c * 8]);
+            bg[pass][1] = *reinterpret_cast<const f32x4*>(&bs[U + c * 8 + 4]);
+        }
+#pragma unroll
+        for (int pass = 0; pass < GP; ++pass) {
+            const int idx = tid + pass * NT;
+            const int row = idx / GCH, c = idx - row * GCH;
+            const int m = m0 + row;
+            const int pn = n0 + c * 8;              // packed column of the 'a' part
+            const int on = (n0 >> 1) + c * 8;       // output column
+            if (m < p.M && pn < p.N) {
+                float f[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    f[e] = ((float)va[pass][e] + ba[pass][e >> 2][e & 3]) * gelu_tanh_f((float)vg[pass][e] + bg[pass][e >> 2][e & 3]);
+                if (has_res) {
+                    const f16x8 rr = *reinterpret_cast<const f16x8*>(p.residual + (size_t)m * p.residual_ld + on);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) f[e] += (float)rr[e];
+                }
+                f16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (f16)f[e];
+                *reinterpret_cast<f16x8*>(p.out + (size_t)m * p.out_ld + on) = o;
+            }
+        }
+        return;
+    }
+    const bool has_res = p.residual != nullptr;      // uniform
+    f16x8 sv[PASSES];
+    f32x4 bb[PASSES][2];
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+        const int idx = tid + pass * NT;
+        const int row = idx / CH, c = idx - row * CH;
+        sv[pass] = *reinterpret_cast<const f16x8*>(&stg[row * SLD + c * 8]);
+        bb[pass][0] = *reinterpret_cast<const f32x4*>(&bs[c * 8]);
+        bb[pass][1] = *reinterpret_cast<const f32x4*>(&bs[c * 8 + 4]);
+    }
+#pragma unroll
+    for (int pass = 0; pass < PASSES; ++pass) {
+        const int idx = tid + pass * NT;
+        const int row = idx / CH, c = idx - row * CH;
+        const int m = m0 + row, n = n0 + c * 8;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = (float)sv[pass][e] + bb[pass][e >> 2][e & 3];
+        if (has_res) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] += (float)lres[pass][e];
+        }
+        f16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (f16)f[e];
+        if (m < p.M && n < p.N) *reinterpret_cast<f16x8*>(p.out + (size_t)m * p.out_ld + n) = o;
+    }
+}
+
 template <int BM, int BN, int NS, int PF, bool XA = false>
 __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
     mdx_kernarg_touch<sizeof(GemmParams)>();
     constexpr int NW = 4;
-    constexpr int WROWS = BM / 2;            // rows per wave row (waves are 2 x 2)
+    // Wave layout, chosen by the tile: BN a multiple of 64 -> four waves 2 x 2, a wave's tile is BM / 2 x BN / 2; otherwise (BN = 160: 80
+    // columns are no whole number of 32 x 32 MFMA tiles) four waves 4 x 1, a wave's tile is BM / 4 = 32 rows x BN columns: one A fragment
+    // and BN / 32 = 5 B fragments for five MFMAs per 16-deep k-step (1.2 KB of LDS reads per MFMA; the 128 x 64 tile reads 1.5 KB).
+    constexpr bool W41 = BN % 64 != 0;
+    static_assert(!W41 || (BM == 128 && BN % 32 == 0 && !XA && PF <= 1), "4 x 1 wave layout: 128-row tiles, prefetch level 0 / 1");
+    constexpr int WROWS = W41 ? BM / 4 : BM / 2;      // rows per wave row
     constexpr int TM = WROWS / 32;
-    constexpr int TN = BN / 64;
+    constexpr int TN = W41 ? BN / 32 : BN / 64;
     constexpr int ROWB = 128;                // bytes per LDS row
     constexpr int KS = 4;                    // MFMA k-steps per K tile
     constexpr int A_BYTES = BM * ROWB;
@@ -181,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = W41 ? wave : wave >> 1, wn = W41 ? 0 : wave & 1;
     const int hi = lane >> 5;
     const int l31 = lane & 31;
 
@@ -222,8 +367,16 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
 #pragma unroll
     for (int j = 0; j < BJ; ++j) {
         const int row = (wave * BJ + j) * 8 + lrow;
-        const int panel = (n0 >> 6) + (row >> 6);
-        b_off[j] = (unsigned)panel * (unsigned)p.kt64 * 8192u + (unsigned)(((row & 63) * 8 + lchk) * 16);
+        if constexpr (W41) {
+            // n0 = 160 tile_n is no panel boundary: the packed row is that of the GLOBAL weight row n0 + row.  n0 % 32 == 0, so the 8 rows of
+            // one DMA stay inside a panel and (tile row >> 1) & 7 == (panel row >> 1) & 7: the pre-swizzled chunks land where the fragment
+            // reads (swz from the tile-local row) expect them.  Rows past the padded N lie past w_bytes: the descriptor answers zero.
+            const int grow = n0 + row;
+            b_off[j] = (unsigned)(grow >> 6) * (unsigned)p.kt64 * 8192u + (unsigned)(((grow & 63) * 8 + lchk) * 16);
+        } else {
+            const int panel = (n0 >> 6) + (row >> 6);
+            b_off[j] = (unsigned)panel * (unsigned)p.kt64 * 8192u + (unsigned)(((row & 63) * 8 + lchk) * 16);
+        }
     }
     auto stage_tile = [&](int kt, int buf) {
         char* sbase = smem + buf * STAGE;
@@ -245,10 +398,11 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
     // of this kernel: s_waitcnt vmcnt(0) right behind the bias load, a full miss in front of the loop) -- and the SAME number of
     // loads in every wave, so that the first wait of the loop can count them (E below).
     constexpr int CPR = BN / 8, RPP = 256 / CPR, PASSES = BM / RPP;
-    constexpr int NX = PF >= 2 ? (PASSES < 4 ? PASSES : 4) : 0;
+    constexpr int NX = (PF >= 2 && !W41) ? (PASSES < 4 ? PASSES : 4) : 0;
     constexpr int LNR = PF >= 3 ? LNR_MAX : 0;
     constexpr int NT = PF == 1 || PF == 2 ? 2 : 0;       // touches (LayerNorm statistics lines, S[n] lines)
-    constexpr int NB = BN == 128 ? 4 : 2;      // bias loads: 8 columns, + the 8 GEGLU gate columns on 128-column tiles
+    constexpr int NB = BN == 128 ? 4 : 2;      // bias loads: 8 columns, + the 8 GEGLU gate columns on 128-column tiles; 4 x 1 layout: two
+                                               // dwords, bias and S[n] of column n0 + tid (epilogue_w41 shares them through LDS)
     constexpr int E = NB + NX + LNR + (PF >= 2 ? 1 : 0) + NT;       // bias + residual rows + LayerNorm partials + S[n] + touches: EXACTLY the loads issued below (every
                                                // one is kept alive behind the loop; the first wait of the loop counts them)
     const bool geglu = p.epilogue == MDX_EPI_GEGLU;
@@ -259,7 +413,11 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
     const __amdgpu_buffer_rsrc_t rs_ln = make_rsrc(p.ln_stats, p.ln_stats ? (unsigned)p.M * (unsigned)p.ln_nt * 8u : 0u);
     const __amdgpu_buffer_rsrc_t rs_lns = make_rsrc(p.ln_s, p.ln_stats ? (unsigned)p.N * 4u : 0u);
     u32x4 braw[4] = {};
-    {
+    if constexpr (W41) {
+        const unsigned off = (tid < BN && n0 + tid < p.N) ? (unsigned)(n0 + tid) * 4u : MDX_OOB;
+        braw[0][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_bias, off, 0, 0);
+        braw[1][0] = __builtin_amdgcn_raw_buffer_load_b32(rs_lns, off, 0, 0);      // (zero without a LayerNorm fold)
+    } else {
         const int n = n0 + (geglu ? (tid & 7) : (tid % CPR)) * 8;
         const unsigned off = n < p.N ? (unsigned)n * 4u : MDX_OOB;
         braw[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_bias, off, 0, 0);
@@ -465,6 +623,8 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();      // K / V^T of every wave's DMAs landed (the staged q tile was ordered by the epilogue's own barrier)
         xattn_tile_epilogue<BM>(p, smem, xs, m0, n0);
+    } else if constexpr (W41) {
+        epilogue_w41<BM, BN>(p, acc[0], smem, m0, n0, bpre[0], bpre[4]);
     } else {
         gemm_epilogue<BM, BN, true, NW, LinearRows, NX, LEAN_EPI ? 1 : 0>(p, acc, smem, LinearRows{m0}, n0, split, bpre, tile_m, tile_id, ln_pre,
                                                                   &lns_pre, xpre, ln_regs, lns_regs);
@@ -539,5 +699,9 @@ bool mdx_dense_launch(const GemmParams& p, int bm, int bn, int ns, dim3 grid, hi
     if (bm == 64 && bn == 128) return launch_dense_ns<64, 128>(p, ns, pf, g, st);
     if (bm == 128 && bn == 64) return launch_dense_ns<128, 64>(p, ns, pf, g, st);
     if (bm == 128 && bn == 128) return launch_dense_ns<128, 128>(p, ns, pf, g, st);
+    if (bm == 128 && bn == 160) {      // four waves 4 x 1; what its epilogue does not carry is refused by the resolver (gemm.hip tile160_ok)
+        if (p.tickets || p.stats_out || p.colstats_out || p.n_split) return false;
+        return launch_dense_ns<128, 160>(p, ns, pf, g, st);
+    }
     return false;
 }

@@ -1277,8 +1277,12 @@ int fill_params(const mdx_gemm_desc* d, GemmParams& p) {
         p.d2s_c = p.N / 4;
         p.out_mode = MDX_OUT_ROWMAJOR;
     }
+    p.geglu_unit = 0;
+    MDX_REQUIRE(d->geglu_unit == 0 || p.epilogue == MDX_EPI_GEGLU, "mdx_gemm_f16: geglu_unit belongs to the GEGLU epilogue");
     if (p.epilogue == MDX_EPI_GEGLU) {
-        MDX_REQUIRE(p.N % 128 == 0, "mdx_gemm_f16: GEGLU needs N %% 128 == 0");
+        MDX_REQUIRE(d->geglu_unit == 0 || d->geglu_unit == 64 || d->geglu_unit == 80, "mdx_gemm_f16: geglu_unit must be 0 (= 64), 64 or 80");
+        p.geglu_unit = d->geglu_unit == 80 ? 80 : 64;
+        MDX_REQUIRE(p.N % (2 * p.geglu_unit) == 0, "mdx_gemm_f16: GEGLU needs N %% %d == 0 (geglu_unit %d)", 2 * p.geglu_unit, p.geglu_unit);
         MDX_REQUIRE(p.out_mode == MDX_OUT_ROWMAJOR, "mdx_gemm_f16: GEGLU is row-major only");
     }
     if (p.out_mode == MDX_OUT_TRANSPOSED) {
@@ -1299,7 +1303,7 @@ int fill_params(const mdx_gemm_desc* d, GemmParams& p) {
     }
     if (p.ln_stats) {
         MDX_REQUIRE(p.ln_s && p.ln_nt * 64 == p.K && p.ksize == 1 && p.c2 == 0 && p.stride == 1 && !p.upsample &&
-                        p.out_mode == MDX_OUT_ROWMAJOR && p.N % (p.epilogue == MDX_EPI_GEGLU ? 128 : 64) == 0,
+                        p.out_mode == MDX_OUT_ROWMAJOR && p.N % (p.epilogue == MDX_EPI_GEGLU ? 2 * p.geglu_unit : 64) == 0,
                     "mdx_gemm_f16: LayerNorm fold needs ln_s, ln_nt == K / 64, N %% 64 == 0 and a dense row-major GEMM");
     }
     if (p.stats_out)
@@ -1405,6 +1409,11 @@ struct TunedEntry {
 static const TunedEntry g_tuned[] = {
 #include "gemm_tuned.inc"
     {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+// Rows of the 128 x 160 tile of the lean dense kernel (same fields, same tool): a table of their own, consulted FIRST.  A row the launch
+// cannot take -- in particular a GEGLU descriptor whose weights are packed at 64 -- is passed over and the main table decides as before.
+static const TunedEntry g_tuned160[] = {
+#include "gemm_tuned160.inc"
+    {0, 0, 0, 0, 0, 0, 0, 0, 0}};
 
 // Launch variant of a descriptor (tools/tune_gemm.py computes the same number from the mdx_gemm_desc fields).
 int tuned_variant(const GemmParams& p) {
@@ -1417,11 +1426,24 @@ int tuned_variant(const GemmParams& p) {
 
 bool halo_eligible(const GemmParams& p, int bm);
 
+// Launches the 128 x 160 tile of the lean dense kernel carries (dense.hip, epilogue_w41): dense row-major, one source, whole 64-channel
+// K tiles, bias / residual / GEGLU packed at 80 / LayerNorm-fold consumer; no split-K, no statistics, no split store, no fused norms.
+bool tile160_ok(const GemmParams& p) {
+    if (!mdx_opt(MDX_OPT_GEMM_LEAN_DENSE) || !p.dense_issue) return false;
+    if (!(p.ksize == 1 && p.stride == 1 && !p.upsample && p.c2 == 0 && p.cin % 64 == 0 && p.out_mode == MDX_OUT_ROWMAJOR)) return false;
+    if (p.gn_cs || p.rowbias || p.out_bs || p.skip_w || p.d2s_c || p.stats_out || p.colstats_out || p.n_split || p.xa_k) return false;
+    if (p.epilogue == MDX_EPI_GEGLU) return p.geglu_unit == 80;
+    return p.epilogue == MDX_EPI_NONE;
+}
+
 const TunedEntry* lookup_tuned(const GemmParams& p) {
     const bool use_table = mdx_opt(MDX_OPT_GEMM_TUNED) && !mdx_opt(MDX_OPT_GEMM_BM) && !mdx_opt(MDX_OPT_GEMM_BN);
     if (!use_table || p.bn_hint || p.st_hint || p.stride != 1 || p.upsample) return nullptr;
     if (p.epilogue == MDX_EPI_PRELU || p.d2s_c) return nullptr;      // (SRGAN launches: no measured rows; a var1 = 0 row says nothing)
     const int var1 = tuned_variant(p) + 1;
+    if (tile160_ok(p))
+        for (const TunedEntry* e = g_tuned160; e->M; ++e)
+            if (e->M == p.M && e->N == p.N && e->K == p.K && e->ksize == p.ksize && e->var1 == var1 && e->bn == 160) return e;
     const TunedEntry* any = nullptr;
     for (const TunedEntry* e = g_tuned; e->M; ++e)
         if (e->M == p.M && e->N == p.N && e->K == p.K && e->ksize == p.ksize) {
@@ -1441,8 +1463,14 @@ const TunedEntry* lookup_tuned(const GemmParams& p) {
 }
 
 int pick_bn(const GemmParams& p) {
-    if (p.epilogue == MDX_EPI_GEGLU) return 128;
-    if (p.bn_hint == 64 || p.bn_hint == 128) return p.bn_hint;
+    if (p.epilogue == MDX_EPI_GEGLU) {      // 128, or 160 where the descriptor forces it / the table has it (resolve_launch checks the packing unit)
+        if (p.bn_hint == 160) return 160;
+        if (!p.bn_hint)
+            if (const TunedEntry* e = lookup_tuned(p))
+                if (e->bn == 160) return 160;
+        return 128;
+    }
+    if (p.bn_hint == 64 || p.bn_hint == 128 || p.bn_hint == 160) return p.bn_hint;
     if (const TunedEntry* e = lookup_tuned(p))
         if (e->bn) return e->bn;
     const int optbn = mdx_opt(MDX_OPT_GEMM_BN);
@@ -1973,6 +2001,20 @@ static int resolve_launch(const mdx_gemm_desc* d, GemmParams& p, Resolved& r) {
         }
     }
     r.halo = r.c.bm >= 128 && halo_eligible(p, r.c.bm);
+    if (bn == 160) {
+        if (!tile160_ok(p) || r.c.bm != 128 || ns != 1 || r.halo) {
+            mdx_set_error("mdx_gemm_f16: tile_n = 160 runs with tile_m = 128, unsplit, on dense row-major launches with bias / residual / "
+                          "GEGLU (geglu_unit = 80) / LayerNorm-fold consumer only (got tile_m %d, %d splits, geglu_unit %d)",
+                          r.c.bm, ns, p.geglu_unit);
+            return MDX_E_INVALID;
+        }
+    }
+    if (p.epilogue == MDX_EPI_GEGLU && 2 * p.geglu_unit != bn) {
+        // the epilogue pairs column j with column j + tile_n / 2 of a tile: weights packed for another tile would give wrong numbers silently
+        mdx_set_error("mdx_gemm_f16: GEGLU weights packed with unit %d need tile_n = %d, this launch resolves to tile_n = %d", p.geglu_unit,
+                      2 * p.geglu_unit, bn);
+        return MDX_E_INVALID;
+    }
     if (r.c.bm == 256 && !r.halo) {      // 256-row tiles exist for the HALO conv only (forced tile_m = 256 on another launch)
         mdx_set_error("mdx_gemm_f16: tile_m = 256 needs a launch the 16 x 16-patch HALO conv applies to (3x3, stride 1, H %% 16 == 0, "
                       "W %% 16 == 0, Cin %% 64 == 0)");
@@ -2012,9 +2054,13 @@ static int resolve_launch(const mdx_gemm_desc* d, GemmParams& p, Resolved& r) {
     return MDX_OK;
 }
 
+struct LaunchGeom;
+static int launch_geometry_check(GemmParams& p, const Resolved& rs);
 static int mdx_internal_resolve_check(const mdx_gemm_desc* d, GemmParams& p) {
     Resolved r;
-    return resolve_launch(d, p, r);
+    const int rc = resolve_launch(d, p, r);
+    if (rc != MDX_OK || r.c8 || r.halo) return rc;
+    return launch_geometry_check(p, r);      // (the kernel form: a tile that exists in one kernel only must get that kernel)
 }
 
 // Rows per colstats_out row block this launch would produce (0 = it cannot): the M tile for a single-pass launch (a HALO
@@ -2054,6 +2100,7 @@ static bool lean_dense_has(int bm, int bn, int ring) {      // the instantiation
     if (ring < 2) return false;
     if (bm == 64) return ring <= 6;
     if (bm == 128 && bn == 64) return ring <= 4;
+    if (bm == 128 && bn == 160) return ring <= 3;
     return bm == 128 && bn == 128 && ring <= 3;
 }
 
@@ -2086,7 +2133,14 @@ static int launch_geometry(GemmParams& p, const Resolved& rs, LaunchGeom& g) {
     }
     g.swap = (ns == 1 || rs.fixup) && (p.out_mode == MDX_OUT_ROWMAJOR);
     g.lean = !rs.halo && lean_dense_eligible(p, g.swap, g.fastk, g.nw8, g.ntiles) && lean_dense_has(c.bm, bn, g.ring);
+    MDX_REQUIRE(bn != 160 || g.lean, "mdx_gemm_f16: the 128 x 160 tile exists in the lean dense kernel only (ring depth 2 | 3, four waves; got stages %d)",
+                rs.stages);
     return MDX_OK;
+}
+
+static int launch_geometry_check(GemmParams& p, const Resolved& rs) {
+    LaunchGeom lg;
+    return launch_geometry(p, rs, lg);
 }
 
 // What mdx_gemm_f16 would launch for this descriptor (no launch): out7 = {tile_m, tile_n, splitk, kernel (0 generic implicit
@@ -2111,7 +2165,7 @@ extern "C" int mdx_gemm_query(const mdx_gemm_desc* d, int* out7) {
         if (lg.lean) form = 2;
     }
     out7[3] = form;
-    out7[4] = r.tuned ? 1 : 0;
+    out7[4] = (r.tuned && r.bn != 160) ? 1 : 0;      // (a row of gemm_tuned.inc; the 128 x 160 tile's rows are a table of their own)
     out7[5] = colstats_rows(p, r);
     out7[6] = r.fixup ? 1 : 0;
     return MDX_OK;

@@ -75,6 +75,7 @@ struct GemmParams {
     const float* act_slope;
     int act_slope_n;
     int d2s_c;
+    int geglu_unit;          // mdx_gemm_desc.geglu_unit, normalised: 64 | 80 ('a' | gate columns per packed tile; GEGLU launches only)
 };
 
 }  // namespace mdx_int

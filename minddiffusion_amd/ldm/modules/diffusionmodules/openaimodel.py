@@ -392,6 +392,7 @@ class UNetModel:
             w["out.cb"] = self._pad_vec(P["id_predictor.1.conv.bias"], self.cout_pad)
         self.w = w
         self._frag_w = {}
+        self._geglu80 = {}
         self._plans = {}
         self._ctx_key = None
         self._ctx_ref = None
@@ -460,6 +461,34 @@ class UNetModel:
                 meta[-1]["desc"] = d        # launches / split are filled in by ops.account_gemm_launches below
             else:
                 oplist.append(fn)
+
+        def geglu_tile160(d, t, inner):
+            """The GEGLU projection of block `t` on the 128 x 160 tile where the library would run it there (tile table): that tile pairs
+            column j with column j + 80, so the launch needs w / bias / S[n] packed at unit 80 (mdx_gemm_desc.geglu_unit).  The second
+            packing is a row permutation of the first, made once per weight on first need and kept for every later plan."""
+            if (8 * inner) % 160 or inner % 64:
+                return
+            d.geglu_unit = 80
+            ok = ops.gemm_check(d) and ops.gemm_query(d)[1] == 160
+            if not ok:
+                d.geglu_unit = 0
+                return
+            names = [k for k in ("ff1.w", "ff1.b", "ff1.s", "ff1.cb") if (t + k) in w]
+            for k in names:
+                if (t + k) not in self._geglu80:
+                    src = w[t + k]
+                    if k == "ff1.w":
+                        src = ops.pack_gemm_weight(ops.geglu_repack(ops.unpack_gemm_weight(src, 8 * inner, inner), 64, 80))
+                    else:
+                        src = ops.geglu_repack(src, 64, 80)
+                    self._geglu80[t + k] = src
+            g80 = self._geglu80
+            d.w = g80[t + "ff1.w"].data_ptr()
+            d._w_tensor = g80[t + "ff1.w"]
+            if d.ln_stats:
+                d.bias, d.ln_s = g80[t + "ff1.cb"].data_ptr(), g80[t + "ff1.s"].data_ptr()
+            else:
+                d.bias = g80[t + "ff1.b"].data_ptr()
 
         gn_calls = []
 
@@ -886,6 +915,7 @@ class UNetModel:
                     g = dense(main, ln, B, n, inner, 8 * inner, w[t + "ff1.w"], bias=w[t + "ff1.b"], epilogue=ops.EPI_GEGLU)
                 else:
                     g = dense(main, tok3, B, n, inner, 8 * inner, w[t + "ff1.w"], epilogue=ops.EPI_GEGLU, **consumer(t + "ff1"))
+                geglu_tile160(descs[-1], t, inner)
                 # the next block's norm1 reads its row statistics from this block's last producer
                 tok = dense(main, g, B, n, 4 * inner, inner, w[t + "ff2.w"], bias=w[t + "ff2.b"], residual=tok3,
                             stats_out=st if (fold1 and not last) else None)

@@ -391,13 +391,36 @@ def unpack_gemm_weight(packed, N, K):
     return torch.gather(t, 3, idx).permute(0, 2, 1, 3, 4).reshape(Np, Kp)[:N, :K].contiguous()
 
 
+def geglu_interleave(a, g, unit=64):
+    """GEGLU packing of mdx_gemm_f16 (include/mdx.h, MDX_EPI_GEGLU / mdx_gemm_desc.geglu_unit): the 'a' rows and the gate rows of the
+    projection ([half, ...] each: weight rows, bias or S[n] entries) -> [2 half, ...] with `unit` 'a' rows followed by their `unit` gate
+    rows per 2 * unit-wide N tile.  unit 64: the 128-column tiles; 80: the 128 x 160 tile."""
+    half = a.shape[0]
+    assert g.shape == a.shape and half % unit == 0
+    nt = half // unit
+    return torch.stack([a.reshape(nt, unit, *a.shape[1:]), g.reshape(nt, unit, *a.shape[1:])], 1).reshape(2 * half, *a.shape[1:]).contiguous()
+
+
+def geglu_deinterleave(t, unit=64):
+    """Inverse of geglu_interleave: ([half, ...] 'a' rows, [half, ...] gate rows)."""
+    half = t.shape[0] // 2
+    assert t.shape[0] % (2 * unit) == 0
+    x = t.reshape(half // unit, 2, unit, *t.shape[1:])
+    return x[:, 0].reshape(half, *t.shape[1:]).contiguous(), x[:, 1].reshape(half, *t.shape[1:]).contiguous()
+
+
+def geglu_repack(t, unit_from, unit_to):
+    """A GEGLU-interleaved tensor (rows of the weight, bias, S[n]) from one packing unit to another: a row permutation, done once."""
+    return geglu_interleave(*geglu_deinterleave(t, unit_from), unit_to)
+
+
 def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, rowbias=None, rowbias_ld=0,
                    residual=None, residual_ld=0, ksize=1, stride=1, upsample=0, epilogue=EPI_NONE,
                    out_mode=OUT_ROWMAJOR, splitk=0, workspace=None, out_bs=0, out2=None, out2_ld=0, n_split=0, asym_pad=0,
                    stats_out=None, ln_stats=None, ln_s=None, ln_eps=1e-5, tile_m=0, tile_n=0, colstats_out=None, stages=0,
                    w_frag=0, skip_a=None, skip_a2=None, skip_c1=0, skip_c2=0, skip_w=None, gn_colstats=None, gn_nrb=0,
                    gn_gamma=None, gn_beta=None, gn_eps=1e-5, gn_silu=1, w_sub=None, xattn_k=None, xattn_vt=None, xattn_len=0,
-                   xattn_cap=0, xattn_scale=0.0, act_slope=None):
+                   xattn_cap=0, xattn_scale=0.0, act_slope=None, geglu_unit=0):
     d = GemmDesc()
     d.a = a.data_ptr()
     d.a2 = 0 if a2 is None else a2.data_ptr()
@@ -441,6 +464,7 @@ def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, 
         d.xattn_len, d.xattn_cap, d.xattn_scale = int(xattn_len), int(xattn_cap), float(xattn_scale)
     if act_slope is not None:    # MDX_EPI_PRELU: per-channel slopes, fp32 [C], column n uses act_slope[n % C]
         d.act_slope, d.act_slope_n = act_slope.data_ptr(), int(act_slope.numel())
+    d.geglu_unit = int(geglu_unit)      # GEGLU: packing unit of w / bias / ln_s (0 = 64; 80 = the 128 x 160 tile)
     return d
 
 
@@ -478,6 +502,11 @@ def new_gemm_workspace(nbytes, device):
     # unbind when the workspace tensor object dies (the plans hold exactly this object; its storage cannot be freed earlier)
     weakref.finalize(ws, lib.mdx_gemm_release_workspace, ctypes.c_void_p(ws.data_ptr()))
     return ws
+
+
+def gemm_check(desc):
+    """True when mdx_gemm_f16 would accept this descriptor as it stands (mdx_gemm_check: validation + launch resolution, no launch)."""
+    return _lib.load().mdx_gemm_check(ctypes.byref(desc)) == 0
 
 
 def gemm_query(desc):
@@ -539,7 +568,7 @@ def tune_untuned(descs, reps=5):
     measured = 0
     for d in descs:
         if (d.colstats_out or d.defer_reduce or d.w_frag or d.skip_w or d.gn_gamma or d.tile_m or d.tile_n or d.splitk
-                or d.stages):
+                or d.stages or d.geglu_unit):      # (geglu_unit: weights packed for the 128 x 160 tile the tile table chose)
             continue
         key = gemm_shape_key(d)
         if key not in tune_cache:

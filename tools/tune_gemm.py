@@ -56,10 +56,13 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--gain", type=float, default=0.04)
     ap.add_argument("--out", default=os.path.join(ROOT, "minddiffusion_amd", "csrc", "gemm_tuned.inc"))
+    ap.add_argument("--out160", default=None, help="table of the 128 x 160 tile's rows (default: gemm_tuned160.inc beside --out)")
     ap.add_argument("--merge", action="store_true", help="keep the entries already in --out (other batches / models)")
     ap.add_argument("--log", default=None)
     ap.add_argument("--only-m", type=int, default=0, help="tune only the shapes with this M")
     ap.add_argument("--only-ks", type=int, default=0, help="tune only the shapes with this kernel size")
+    ap.add_argument("--tile160-only", action="store_true",
+                    help="dense shapes only, and only the 128 x 160 tile (ring 2 | 3) against the present choice: the A/B of that form")
     ap.add_argument("--insitu", type=int, default=2,
                     help="run this many of the plan's preceding ops between the flush and the timed launch (0 = all cold)")
     args = ap.parse_args()
@@ -110,6 +113,32 @@ def main():
                         pres[key] = list(P.main[max(0, i - args.insitu):i])
                         shapes[key] = dd
     big_ws = ops.new_gemm_workspace(256 << 20, dev)
+    # GEGLU weights are packed for ONE tile width (mdx_gemm_desc.geglu_unit): a candidate on the other width gets its own packing of
+    # the plan's w / bias / S[n] (row permutations, cached per weight)
+    ptr2t = {}
+    if args.model in ("sd2", "wukong"):
+        ptr2t = {t.data_ptr(): t for t in list(net.w.values()) + list(net._geglu80.values())}
+    repacked = {}
+
+    def set_geglu_unit(d, d0, unit):
+        have = 80 if d0.geglu_unit == 80 else 64
+        if unit == have:
+            return True
+        if d0.w not in ptr2t or (d0.bias and d0.bias not in ptr2t) or (d0.ln_s and d0.ln_s not in ptr2t):
+            return False
+        key = (d0.w, unit)
+        if key not in repacked:
+            N_, K_ = d0.N, d0.c1 + d0.c2
+            w2 = ops.pack_gemm_weight(ops.geglu_repack(ops.unpack_gemm_weight(ptr2t[d0.w], N_, K_), have, unit))
+            repacked[key] = (w2, ops.geglu_repack(ptr2t[d0.bias], have, unit) if d0.bias else None,
+                             ops.geglu_repack(ptr2t[d0.ln_s], have, unit) if d0.ln_s else None)
+        w2, b2, s2 = repacked[key]
+        d.w, d.geglu_unit = w2.data_ptr(), (80 if unit == 80 else 0)
+        if b2 is not None:
+            d.bias = b2.data_ptr()
+        if s2 is not None:
+            d.ln_s = s2.data_ptr()
+        return True
     lines, log = [], []
     for (M, N, K, ks, var), d0 in sorted(shapes.items()):
         if (args.only_m and M != args.only_m) or (args.only_ks and ks != args.only_ks):
@@ -127,6 +156,8 @@ def main():
             if d.colstats_out:      # the plan's buffer is sized for the plan's row blocks: candidates get one that fits 64-row blocks
                 d.colstats_out, d.colstats_cap = cs_scratch.data_ptr(), (M + 63) // 64
             d.workspace, d.workspace_bytes = big_ws.data_ptr(), big_ws.numel() * 4
+            if d.epilogue == ops.EPI_GEGLU and bn and not set_geglu_unit(d, d0, 80 if bn == 160 else 64):
+                raise RuntimeError("no tensors to repack the GEGLU weights from")
             return d
         pre = pres.get((M, N, K, ks, var), ())
         cs_scratch = torch.empty(((M + 63) // 64) * N * 2 + 16, dtype=torch.float32, device=dev) if d0.colstats_out else None
@@ -137,7 +168,23 @@ def main():
         halo256 = halo and d0.H % 16 == 0
         # 8x8 images take the two-samples-per-tile HALO kernel whenever they are eligible (gemm.hip lookup_tuned drops 64-row
         # rows for them), so 64-row generic tiles are not candidates there
+        # the 128 x 160 tile of the lean dense kernel (four waves 4 x 1): every dense shape is offered it, unsplit, ring 2 | 3; the
+        # library refuses the variants its epilogue does not carry (statistics, split stores, fused norms ...)
+        if ks == 1 and d0.c2 == 0 and N >= 160:
+            for st in (2, 3):
+                try:
+                    t = time_desc(ops, cand(128, 1, 160, st), flush, args.reps, pre)
+                except Exception as e:
+                    log.append(f"  skip M={M} N={N} K={K} bm=128 bn=160 ns=1 st={st}: {e}")
+                    continue
+                log.append(f"  M={M} N={N} K={K} v{var}: 128 x 160 ring {st}: {t:7.2f} us (present choice {t_auto:7.2f} us)")
+                if t < best[0]:
+                    best = (t, 128, 1, 160, st)
+        elif args.tile160_only:
+            continue
         for bm in (([128, 256] if halo256 else [128]) if (halo or halo8) else [128, 64]):
+            if args.tile160_only:
+                break
             for bn in bns:
                 for ns in NS_CANDIDATES:
                     if ns > 1 and (kt // ns < 2 or ns * M * N * 4 > big_ws.numel() * 4):
@@ -163,6 +210,28 @@ def main():
         log.append(msg)
         if keep:
             lines.append((M, N, K, ks, best[1], best[3], best[2], t_ref, best[0], var, best[4]))
+    # Rows of the 128 x 160 tile go to a table of their own (gemm_tuned160.inc, consulted first by gemm.hip lookup_tuned): the shape's
+    # row in the main table stays and serves the descriptors that tile does not carry (GEGLU weights packed at 64 ...)
+    lines160 = [l for l in lines if l[5] == 160]
+    lines = [l for l in lines if l[5] != 160]
+    out160 = args.out160 or os.path.join(os.path.dirname(args.out), "gemm_tuned160.inc")
+    old160 = []
+    if args.merge and os.path.exists(out160):
+        for ln in open(out160):
+            m = re.match(r"\s*\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\},", ln)
+            if m and tuple(int(m.group(i)) for i in (1, 2, 3, 4, 8)) not in {l[:4] + (l[9] + 1,) for l in lines160}:
+                old160.append(ln.rstrip("\n"))
+    if lines160 or not args.merge:
+        with open(out160, "w") as f:
+            f.write("// generated by tools/tune_gemm.py -- rows of the 128 x 160 tile of the lean dense kernel, fields as in gemm_tuned.inc: "
+                    "measured on MI355X, cold weights\n")
+            for ln in old160:
+                f.write(ln + "\n")
+            for M, N, K, ks, bm, bn, ns, t0, t1, var, st in lines160:
+                f.write(f"    {{{M}, {N}, {K}, {ks}, {bm}, {bn}, {ns}, {var + 1}, {st}}},   // {args.model} B={B} latent={h}: {t0:.1f} -> {t1:.1f} us\n")
+        print(f"{len(lines160)} rows of the 128 x 160 tile written to {out160} ({len(old160)} kept)")
+    if args.tile160_only:
+        return
     old = []
     if args.merge and os.path.exists(args.out):
         for ln in open(args.out):
