@@ -16,13 +16,15 @@
 //     thread's store passes, the LayerNorm-fold partials of the thread's row (up to 24 of them, held in registers: the adds run
 //     after the K loop in the partials' order, so the statistics keep their bits) and S[n] -- so that the epilogue of a lone block is
 //     staging + arithmetic + stores.
-// Launch forms covered: row-major output, unsplit or in-kernel split-K reduce (tickets), bias / residual / GEGLU / row statistics /
+// Launch forms covered (mdx_dense_takes below): row-major output, unsplit or in-kernel split-K reduce (tickets), bias / residual / GEGLU / row statistics /
 // column statistics / LayerNorm-fold consumer / the q|k row-major + V^T split store.  The 128 x 160 tile (four waves 4 x 1, epilogue_w41
 // below; round 7) cuts M = 512 x N = 10240 and M = 2048 x N = 5120 into exactly 256 / 512 equal blocks: bias / residual / GEGLU /
 // LayerNorm-fold consumer, unsplit.  Everything else (per-sample row bias, out_bs,
 // GELU activations, transposed output, slab split-K, the GroupNorm-on-A form, eight waves) stays on the generic kernel.
 #include "mdx_common.h"
 #include "gemm_internal.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -681,27 +683,59 @@ bool launch_dense_ns(const GemmParams& p, int ns, int pf, dim3 grid, hipStream_t
 
 }  // namespace
 
-// `grid` is what mdx_gemm_f16 computed for the generic kernel; the SPREAD order becomes a 2-D grid (tiles, splits) here.
+// THE statement of which launches this kernel takes (gemm_internal.h), in two steps; plan_gemm and the tile-table lookup ask nobody
+// else.  Step one, the descriptor alone -- what the tile-table lookup can know: dense (ksize 1, stride 1, one source, K tiles of whole
+// 64-channel chunks), row-major, plain / GEGLU epilogue, no per-sample row bias, no out_bs, not the GroupNorm-on-A form.
+bool mdx_dense_takes_desc(const GemmParams& p, int bn) {
+    if (!mdx_opt(MDX_OPT_GEMM_LEAN_DENSE) || !p.dense_issue) return false;
+    if (!(p.ksize == 1 && p.stride == 1 && !p.upsample && p.c2 == 0 && p.cin % 64 == 0 && p.out_mode == MDX_OUT_ROWMAJOR)) return false;
+    if (p.gn_cs || p.rowbias || p.out_bs || p.skip_w || p.d2s_c) return false;
+    if (p.epilogue != MDX_EPI_NONE && p.epilogue != MDX_EPI_GEGLU) return false;
+    if (p.xa_k && bn != 64) return false;      // cross-attention epilogue: one head per 64-column tile
+    if (bn == 160) {
+        // four waves 4 x 1 (epilogue_w41): bias / residual / GEGLU packed at 80 / LayerNorm-fold consumer; no statistics, no split
+        // store, no cross-attention
+        if (p.stats_out || p.colstats_out || p.n_split || p.xa_k) return false;
+        if (p.epilogue == MDX_EPI_GEGLU && p.geglu_unit != 80) return false;
+    }
+    return true;
+}
+
+// Step two, the planned launch: through the staged epilogue (unsplit or in-kernel reduce; the 160 tile unsplit only), four waves, a
+// (tile, ring depth) that is built (launch_dense_ns / launch_dense_xa), offsets and tile ids that fit.
+bool mdx_dense_takes(const GemmParams& p, int bm, int bn, int ring, int nsplit, bool fixup, bool nw8) {
+    if (!mdx_dense_takes_desc(p, bn)) return false;
+    if (!(nsplit == 1 || (fixup && bn != 160)) || nw8) return false;
+    int built = (bm == 64 && (bn == 64 || bn == 128)) ? 6 : (bm == 128 && bn == 64) ? 4 : (bm == 128 && (bn == 128 || bn == 160)) ? 3 : 0;
+    if (p.xa_k) built = std::min(built, 4);
+    if (ring < 2 || ring > built) return false;
+    // buffer descriptors of the epilogue prefetches: 32-bit offsets
+    if ((size_t)p.M * (size_t)(p.residual ? p.residual_ld : 0) * 2 >= 0x80000000ull) return false;
+    if (p.ln_stats && (size_t)p.M * (size_t)p.ln_nt * 8 >= 0x80000000ull) return false;
+    // tile ids must fit the multiply-high decode
+    return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) < 65536;
+}
+
+// pl.grid is the generic kernel's; the SPREAD order becomes a 2-D grid (tiles, splits) here.
 // Option gemm_lean_dense: 1 = prefetch level 1 (the product), 2 = level 0, 3 / 4 = levels 2 / 3 on launches of at most two blocks
 // per CU (beyond that the register-hungry levels would take a block per CU away: level 1).
-bool mdx_dense_launch(const GemmParams& p, int bm, int bn, int ns, dim3 grid, hipStream_t st) {
-    dim3 g = p.spread ? dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.nsplit) : grid;
+int mdx_dense_launch(const GemmParams& p, const GemmPlan& pl, hipStream_t st) {
+    const int bm = pl.bm, bn = pl.bn, ns = pl.ring;
+    const dim3 g = p.spread ? dim3((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.nsplit) : pl.grid;
     const int opt = mdx_opt(MDX_OPT_GEMM_LEAN_DENSE);
     const bool small = (long)g.x * g.y <= 512;
     const int pf = opt == 2 ? 0 : (opt == 3 && small ? 2 : (opt == 4 && small ? 3 : 1));
-    if (p.xa_k) {      // cross-attention epilogue (mdx_gemm_desc.xattn_k): 64-column tiles, ring depth 2 .. 4
-        if (bn != 64 || ns < 2 || ns > 4) return false;
-        if (bm == 64) { if (ns == 2) launch_dense_xa<64, 2>(p, g, st); else if (ns == 3) launch_dense_xa<64, 3>(p, g, st); else launch_dense_xa<64, 4>(p, g, st); return true; }
-        if (bm == 128) { if (ns == 2) launch_dense_xa<128, 2>(p, g, st); else if (ns == 3) launch_dense_xa<128, 3>(p, g, st); else launch_dense_xa<128, 4>(p, g, st); return true; }
-        return false;
+    bool ok = false;
+    if (pl.form == GEMM_LEAN_XA) {
+        ok = bn == 64 && ns >= 2 && ns <= 4 && (bm == 64 || bm == 128);
+        if (ok && bm == 64) { if (ns == 2) launch_dense_xa<64, 2>(p, g, st); else if (ns == 3) launch_dense_xa<64, 3>(p, g, st); else launch_dense_xa<64, 4>(p, g, st); }
+        if (ok && bm == 128) { if (ns == 2) launch_dense_xa<128, 2>(p, g, st); else if (ns == 3) launch_dense_xa<128, 3>(p, g, st); else launch_dense_xa<128, 4>(p, g, st); }
     }
-    if (bm == 64 && bn == 64) return launch_dense_ns<64, 64>(p, ns, pf, g, st);
-    if (bm == 64 && bn == 128) return launch_dense_ns<64, 128>(p, ns, pf, g, st);
-    if (bm == 128 && bn == 64) return launch_dense_ns<128, 64>(p, ns, pf, g, st);
-    if (bm == 128 && bn == 128) return launch_dense_ns<128, 128>(p, ns, pf, g, st);
-    if (bm == 128 && bn == 160) {      // four waves 4 x 1; what its epilogue does not carry is refused by the resolver (gemm.hip tile160_ok)
-        if (p.tickets || p.stats_out || p.colstats_out || p.n_split) return false;
-        return launch_dense_ns<128, 160>(p, ns, pf, g, st);
-    }
-    return false;
+    else if (bm == 64 && bn == 64) ok = launch_dense_ns<64, 64>(p, ns, pf, g, st);
+    else if (bm == 64 && bn == 128) ok = launch_dense_ns<64, 128>(p, ns, pf, g, st);
+    else if (bm == 128 && bn == 64) ok = launch_dense_ns<128, 64>(p, ns, pf, g, st);
+    else if (bm == 128 && bn == 128) ok = launch_dense_ns<128, 128>(p, ns, pf, g, st);
+    else if (bm == 128 && bn == 160) ok = launch_dense_ns<128, 160>(p, ns, pf, g, st);
+    MDX_REQUIRE(ok, "mdx_gemm_f16: internal error: the plan names a lean dense tile %d x %d at ring depth %d that is not built", bm, bn, ns);
+    return MDX_OK;
 }

@@ -1,5 +1,6 @@
-// Internals shared by the GEMM / conv translation units of libmdx (gemm.hip, conv8p.hip): the launch parameter block and the
-// row-wise epilogue helpers.  Everything sits in an anonymous namespace: each TU gets its own copy.
+// Internals shared by the GEMM / conv translation units of libmdx (gemm.hip, gemm_plan.hip, dense.hip, conv8p.hip): the launch
+// parameter block, the launch plan and the row-wise epilogue helpers.  The device helpers sit in an anonymous namespace: each TU
+// gets its own copy.
 #pragma once
 #include "mdx_common.h"
 
@@ -81,10 +82,46 @@ struct GemmParams {
 }  // namespace mdx_int
 using mdx_int::GemmParams;
 
-// 8-phase 256-pixel conv core (conv8p.hip): eligibility + launch, called from mdx_gemm_f16 / mdx_gemm_query (gemm.hip)
-// lean dense kernel (dense.hip): dense row-major launches of the benchmarked tile shapes; false = this (tile, ring) has no lean
-// instantiation and the caller launches the generic kernel
-bool mdx_dense_launch(const GemmParams& p, int bm, int bn, int ns, dim3 grid, hipStream_t st);
+// ---- host side: everything decided before a launch.  plan_gemm (gemm_plan.hip) fills a GemmPlan from the descriptor, once;
+// mdx_gemm_launch_plan (gemm.hip) launches it.  A new launch form = a GemmForm value, its rule in plan_gemm, its case in the switch.
+enum GemmForm {
+    GEMM_GENERIC,           // gemm_kernel, four waves
+    GEMM_GENERIC_NW8,       // gemm_kernel, eight waves on a 128-row tile (ring depth 2 | 3)
+    GEMM_GNA,               // gemm_kernel with the GroupNorm of the input on the A fragments (ring depth 2 | 3)
+    GEMM_EXT,               // gemm_kernel with the SRGAN epilogues: PReLU, depth-to-space (ring depth 2 | 3)
+    GEMM_LEAN,              // dense_kernel (dense.hip)
+    GEMM_LEAN_XA,           // dense_kernel with the cross-attention epilogue
+    GEMM_HALO,              // conv3x3_halo_kernel, weights through an LDS ring
+    GEMM_HALO_FRAG,         // conv3x3_halo_kernel, fragment-major weights streamed into registers (128-row tiles)
+    GEMM_HALO_FRAG_W4,      // the same with the four wave pairs side by side along N (128 x 128 tiles, slab split-K)
+    GEMM_CONV8P             // the eight-wave 256-pixel conv core (conv8p.hip)
+};
+enum GemmReduce { GEMM_REDUCE_NONE, GEMM_REDUCE_PLAIN, GEMM_REDUCE_EXT, GEMM_REDUCE_COLSTATS, GEMM_REDUCE_DEFERRED };
+struct TunedEntry;
+struct GemmPlan {
+    GemmForm form;
+    int bm, bn;
+    int ring;               // LDS ring depth launched (HALO: depth of the weight ring; 0 = the form has none)
+    int pw;                 // HALO patch width: 16, or 8 (8 x 8 images, two samples per 128-row tile)
+    int nsplit;
+    bool fixup;             // split-K reduced by the last block of each tile (arrival counters, no reduce launch)
+    bool swap, fastk;
+    dim3 grid;
+    const TunedEntry* tuned;    // the tile-table row that chose tile and split (null: descriptor overrides / cost model)
+    int colstats_rows;      // rows per colstats_out row block this launch can produce (0 = it cannot)
+    GemmReduce reduce;      // the launch that follows a slab split-K (DEFERRED: the consumer sums the slabs)
+    size_t ws_head, ws_per_split;   // workspace the split needs: ws_head + nsplit * ws_per_split (conv8p: all of it in ws_head)
+};
+// launches the kernel of a filled plan and the reduce kernel behind it
+int mdx_gemm_launch_plan(const GemmParams& p, const GemmPlan& pl, hipStream_t st);
+
+// lean dense kernel (dense.hip): THE statement of which launches it takes, in two steps.  mdx_dense_takes_desc: the descriptor alone
+// (what the tile-table lookup can know); mdx_dense_takes: that plus the planned tile, ring depth and split.
+// mdx_dense_launch launches a plan whose form is GEMM_LEAN / GEMM_LEAN_XA; one it has no instantiation for is an error.
+bool mdx_dense_takes_desc(const GemmParams& p, int bn);
+bool mdx_dense_takes(const GemmParams& p, int bm, int bn, int ring, int nsplit, bool fixup, bool nw8);
+int mdx_dense_launch(const GemmParams& p, const GemmPlan& pl, hipStream_t st);
+// 8-phase 256-pixel conv core (conv8p.hip): eligibility + launch
 bool mdx_conv8p_eligible(const GemmParams& p);
 int mdx_conv8p_pick_bn(const GemmParams& p, int bn_hint);
 int mdx_conv8p_tiles(const GemmParams& p);
@@ -261,6 +298,7 @@ __device__ __forceinline__ void gemm_ln_row_fold(const GemmParams& p, const int 
 // line of its CU's L1 or its XCD's L2.  No placement assumption: a tile's splits may run on any CUs of any XCDs.
 // The counter is reset by the last arriver, so a tile's counter is zero whenever no launch is in flight on its workspace.
 constexpr int MDX_TICKET_SLOTS = MDX_GEMM_WS_HEAD / 4;      // tiles per launch that can take tickets
+constexpr int CS_ROWS = 64;     // rows per colstats row block of a split-K launch (mdx_gemm_query reports it)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int BM, int BN, int NW>
@@ -343,7 +381,7 @@ __device__ __forceinline__ bool splitk_last_block_reduce(const GemmParams& p, f3
 // Optional prefetches of the lean dense kernel (dense.hip), all issued BEFORE the K loop so that the epilogue of a lone block opens
 // with no global round trip: ln_pre = {mean, rstd} of this thread's row (tid < BM), lns_pre = S[n0 + tid] (tid < BN), xpre = the
 // residual (/ time-embedding) rows of this thread's first NXPRE store passes.
-// LEAN (the lean dense kernel, dense.hip; round 6): the launch has no per-sample row bias and no out_bs (lean_dense_eligible), and
+// LEAN (the lean dense kernel, dense.hip; round 6): the launch has no per-sample row bias and no out_bs (mdx_dense_takes), and
 // the store loops are written in BATCHES -- every staged row / residual row of the thread's passes requested first, then the
 // arithmetic, then the stores back to back, statistics last -- instead of one pass at a time behind the generic per-pass feature
 // branches (row bias and out_bs cost an integer division per pass; ~450 instructions per pass in the ISA of round 5, one pass

@@ -36,7 +36,7 @@ void mdx_set_error(const char* fmt, ...);
     } while (0)
 
 // What a consumer that sums a producer's split-K slabs itself (mdx_groupnorm_from_splitk_f16) needs to know about that
-// producer: filled by gemm.hip from the producer's descriptor with the SAME decision path as mdx_gemm_f16.
+// producer: filled by gemm_plan.hip from the producer's descriptor through the SAME plan_gemm call as mdx_gemm_f16.
 struct MdxSplitInfo {
     const float* ws;          // [nsplit][M][N] fp32 slabs
     int nsplit, M, N, HoWo, B;

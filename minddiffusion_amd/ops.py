@@ -536,7 +536,7 @@ _tune_flush = {}
 
 
 def gemm_shape_key(d):
-    """What a launch form depends on: problem shape + launch variant (the tile table's key, gemm.hip tuned_variant())."""
+    """What a launch form depends on: problem shape + launch variant (the tile table's key, gemm_plan.hip tuned_variant())."""
     var = ((1 if d.c2 > 0 else 0) | (d.epilogue << 1) | (8 if d.n_split else 0) | (16 if d.ln_stats else 0)
            | (32 if d.stats_out else 0) | (64 if d.out_mode == 1 else 0) | (128 if d.colstats_out else 0)
            | (256 if d.residual else 0) | (512 if d.rowbias else 0) | (1024 if d.skip_w else 0) | (2048 if d.gn_gamma else 0)

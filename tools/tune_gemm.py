@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Measure the (tile_m, splitk) candidates of every GEMM / conv shape of a UNet plan on the device and write the ones
-that beat the cost model (gemm.hip choose_tiling) into minddiffusion_amd/csrc/gemm_tuned.inc.
+that beat the cost model (gemm_plan.hip cost_model_tiling) into minddiffusion_amd/csrc/gemm_tuned.inc.
 
     python tools/tune_gemm.py --model sd2 --batch 2 --latent 64 [--merge] [--out minddiffusion_amd/csrc/gemm_tuned.inc]
 
@@ -27,7 +27,7 @@ NS_CANDIDATES = [1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 20]
 
 
 def variant(d):
-    """Launch variant of a descriptor: gemm.hip tuned_variant()."""
+    """Launch variant of a descriptor: gemm_plan.hip tuned_variant()."""
     return ((1 if d.c2 > 0 else 0) | (2048 if d.epilogue == 4 else d.epilogue << 1) | (8 if d.n_split else 0) | (16 if d.ln_stats else 0)
             | (32 if d.stats_out else 0) | (64 if d.out_mode == 1 else 0) | (128 if d.colstats_out else 0)
             | (256 if d.residual else 0) | (512 if d.rowbias else 0) | (1024 if d.out_mode == 2 else 0))
@@ -166,7 +166,7 @@ def main():
         best = (t_auto, 0, 0, 0, 0)
         bns = [128] if d0.epilogue == ops.EPI_GEGLU else ([64] if N < 128 else [128, 64])
         halo256 = halo and d0.H % 16 == 0
-        # 8x8 images take the two-samples-per-tile HALO kernel whenever they are eligible (gemm.hip lookup_tuned drops 64-row
+        # 8x8 images take the two-samples-per-tile HALO kernel whenever they are eligible (gemm_plan.hip lookup_tuned drops 64-row
         # rows for them), so 64-row generic tiles are not candidates there
         # the 128 x 160 tile of the lean dense kernel (four waves 4 x 1): every dense shape is offered it, unsplit, ring 2 | 3; the
         # library refuses the variants its epilogue does not carry (statistics, split stores, fused norms ...)
@@ -210,7 +210,7 @@ def main():
         log.append(msg)
         if keep:
             lines.append((M, N, K, ks, best[1], best[3], best[2], t_ref, best[0], var, best[4]))
-    # Rows of the 128 x 160 tile go to a table of their own (gemm_tuned160.inc, consulted first by gemm.hip lookup_tuned): the shape's
+    # Rows of the 128 x 160 tile go to a table of their own (gemm_tuned160.inc, consulted first by gemm_plan.hip lookup_tuned): the shape's
     # row in the main table stays and serves the descriptors that tile does not carry (GEGLU weights packed at 64 ...)
     lines160 = [l for l in lines if l[5] == 160]
     lines = [l for l in lines if l[5] != 160]
