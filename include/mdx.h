@@ -95,6 +95,15 @@ size_t mdx_groupnorm_ws_floats(int B, int HW, int C, int groups);
 int mdx_groupnorm_f16(const void* x1, int C1, const void* x2, int C2, const float* gamma, const float* beta,
                       void* y, int B, int HW, int groups, float eps, int silu, float* ws, mdx_stream_t s);
 
+/* Which launch form mdx_groupnorm_f16 / mdx_groupnorm_scaleshift_f16 (colstats_nrb == 0) or mdx_groupnorm_colstats_f16
+ * (colstats_nrb > 0: row blocks per sample of the column partials) resolves to for this shape under the current library options
+ * (host only, no launch; the launch and this query share one decision function).
+ * out6 = { form, cw (16-byte chunk columns per block), ncb (column blocks), nblk (pixel slabs per sample), pix (pixels per slab),
+ *          threads per block };  form: 0 two launches (statistics + apply), 1 one launch that reads the tensor twice,
+ * 2 one launch that keeps its pixels in registers, 3 one launch with 256-thread blocks, 4 apply with column statistics.
+ * (mdx_groupnorm_from_splitk_f16 has its own predicate, mdx_groupnorm_from_splitk_ok.) */
+int mdx_groupnorm_query(int C1, int C2, int B, int HW, int groups, int colstats_nrb, int* out6);
+
 /* GroupNorm whose statistics come from its producers' column partials (mdx_gemm_desc.colstats_out) instead of a reduction
  * pass over the tensor: ONE launch (normalise + affine [+ SiLU]) and one read of x instead of two launches and two reads.
  * cs1 / cs2: the producers' colstats buffers of x1 / x2 ([B * nrb][C][2] fp32), nrb1 / nrb2 = row blocks per sample

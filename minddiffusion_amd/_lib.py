@@ -79,6 +79,7 @@ SIGNATURES = {
     "mdx_groupnorm_ws_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mdx_groupnorm_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_int, c_float, c_int, c_void_p, c_void_p]),
+    "mdx_groupnorm_query": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "mdx_groupnorm_colstats_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float,
                                            c_int, c_void_p]),

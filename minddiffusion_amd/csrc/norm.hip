@@ -768,26 +768,16 @@ extern "C" size_t mdx_groupnorm_ws_floats(int B, int HW, int C, int groups) {
     return (size_t)B * (HW >= 16384 ? GN_MAX_NBLK : 64) * groups * 2;   // slab cap of gn_geometry
 }
 
-static int groupnorm_impl(const void* x1, int C1, const void* x2, int C2, const float* gamma, const float* beta,
-                          const float* scale, const float* shift, int mod_ld, void* y, int B, int HW, int groups,
-                          float eps, int silu, float* ws, mdx_stream_t s, const float* cs1 = nullptr, int nrb1 = 0,
-                          const float* cs2 = nullptr, int nrb2 = 0) {
-    MDX_REQUIRE(x1 && gamma && beta && y && (ws || cs1), "mdx_groupnorm_f16: null pointer");
-    MDX_REQUIRE((C2 == 0) == (x2 == nullptr), "mdx_groupnorm_f16: x2/C2 mismatch");
-    MDX_REQUIRE((scale == nullptr) == (shift == nullptr), "mdx_groupnorm_scaleshift_f16: scale/shift mismatch");
+// Launch forms of GroupNorm on a tensor (mdx_groupnorm_query reports them with these codes).
+enum GnForm { GN_FORM_TWO_LAUNCH = 0, GN_FORM_FUSED = 1, GN_FORM_FUSED_ONE_PASS = 2, GN_FORM_FUSED_256 = 3, GN_FORM_COLSTATS = 4 };
+
+// Shape checks and the shape part of the parameters: shared by the launch and by mdx_groupnorm_query.
+static int gn_shape(GnParams& p, int C1, int C2, int B, int HW, int groups) {
     const int C = C1 + C2;
-    MDX_REQUIRE(C1 > 0 && C1 % 8 == 0 && C2 % 8 == 0, "mdx_groupnorm_f16: channels must be multiples of 8");
+    MDX_REQUIRE(C1 > 0 && C1 % 8 == 0 && C2 >= 0 && C2 % 8 == 0, "mdx_groupnorm_f16: channels must be multiples of 8");
     MDX_REQUIRE(groups > 0 && groups <= 32 && C % groups == 0, "mdx_groupnorm_f16: C=%d not divisible by groups=%d (<= 32)", C, groups);
     MDX_REQUIRE(C <= GN_MAX_C, "mdx_groupnorm_f16: C=%d exceeds %d", C, GN_MAX_C);
     MDX_REQUIRE(B > 0 && HW > 0 && B <= 65535, "mdx_groupnorm_f16: bad extents");
-    MDX_REQUIRE(!scale || mod_ld >= C, "mdx_groupnorm_scaleshift_f16: mod_ld < C");
-    GnParams p{};
-    p.x1 = (const f16*)x1;
-    p.x2 = (const f16*)x2;
-    p.gamma = gamma;
-    p.beta = beta;
-    p.y = (f16*)y;
-    p.ws = ws;
     p.C1 = C1;
     p.C2 = C2;
     p.C = C;
@@ -797,23 +787,21 @@ static int groupnorm_impl(const void* x1, int C1, const void* x2, int C2, const 
     p.HW = HW;
     p.groups = groups;
     p.cpg = C / groups;
-    p.eps = eps;
-    p.silu = silu;
-    p.scale = scale;
-    p.shift = shift;
-    p.mod_ld = mod_ld;
-    p.cs1 = cs1;
-    p.cs2 = cs2;
-    p.nrb1 = nrb1;
-    p.nrb2 = nrb2;
     p.pre = mdx_opt(MDX_OPT_GN_PREFETCH) ? 1 : 0;
-    hipStream_t st = (hipStream_t)s;
-    if (cs1) {
+    return MDX_OK;
+}
+
+// THE decision: which form a GroupNorm of this shape launches (colstats: statistics from the producers' column partials) under the
+// current library options, its geometry (p.cw / ncb / nblk / pix) and its threads per block.  groupnorm_impl launches what this
+// returns and mdx_groupnorm_query reports it, so the two cannot drift.
+static int gn_plan(GnParams& p, bool colstats, int* form, int* threads) {
+    const int B = p.B, HW = p.HW;
+    const int lcm = p.cpg / gcd_i(p.cpg, 8) * 8;   // channels spanned by a whole number of groups AND of chunks
+    const int L = lcm / 8;                          // ... in chunk columns
+    *threads = 256;
+    if (colstats) {
         // one launch: gn_apply with its statistics folded from the producers' column partials.  Minimal column blocks
         // (whole groups AND whole 16-byte chunks) keep the fold short: chs * nrb float2 loads per block.
-        MDX_REQUIRE(nrb1 > 0 && (C2 == 0 || (cs2 && nrb2 > 0)), "mdx_groupnorm_colstats_f16: missing column statistics");
-        const int lcm = p.cpg / gcd_i(p.cpg, 8) * 8;
-        const int L = lcm / 8;
         MDX_REQUIRE(L <= 64, "mdx_groupnorm_colstats_f16: %d channels per group is not supported", p.cpg);
         int minc = mdx_opt(MDX_OPT_GN_COL_CHUNKS);
         if (minc < 1) minc = 1;
@@ -831,7 +819,7 @@ static int groupnorm_impl(const void* x1, int C1, const void* x2, int C2, const 
         // the slabs from gn_boost_mb on (tools/exp/r04k_gn_bench.py, profiles/r04_gn_bench.txt: 64 x 64 x 640 at batch 16 60.8 -> 41.8 us,
         // 32 x 32 x 1280 36.2 -> 25.8, 64 x 64 x 320 28.4 -> 25.9; the batch-2 tensors, 10 MB, lose 3 us and stay below the threshold)
         const int boost_mb = mdx_opt(MDX_OPT_GN_BOOST_MB);
-        if (boost_mb > 0 && (size_t)B * HW * C * 2 >= ((size_t)boost_mb << 20)) target = 4 * GN_TARGET_BLOCKS;
+        if (boost_mb > 0 && (size_t)B * HW * p.C * 2 >= ((size_t)boost_mb << 20)) target = 4 * GN_TARGET_BLOCKS;
         if (wide_rows > 0 && (long)B * HW >= wide_rows) {
             const int cap = p.CC < 64 ? p.CC : 64;
             const int l8 = L / gcd_i(L, 8) * 8;          // whole groups AND whole 128-byte lines
@@ -848,65 +836,132 @@ static int groupnorm_impl(const void* x1, int C1, const void* x2, int C2, const 
         if (nblk < 1) nblk = 1;
         p.pix = (HW + nblk - 1) / nblk;
         p.nblk = (HW + p.pix - 1) / p.pix;
-        dim3 grid(p.nblk, p.ncb, B);
-        hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(256), ((size_t)cw * 8 * 2 + 64 + (size_t)cw * 8 * 2) * sizeof(float), st, p);
-        MDX_LAUNCH_CHECK("mdx_groupnorm_colstats_f16");
+        *form = GN_FORM_COLSTATS;
         return MDX_OK;
     }
-    {
-        // fused single-launch path when one block can walk all pixels of its column block quickly: <= 64 KiB per block,
-        // i.e. the 16x16 and 8x8 latent levels (measured per shape: 8.7 vs 12.4 us at HW = 256, 7.5 vs 10.7 at HW = 64;
-        // at HW >= 1024 the few, long blocks lose to the two-launch slab scheme)
-        const int lcm = p.cpg / gcd_i(p.cpg, 8) * 8;
-        const int L = lcm / 8;
-        if (mdx_opt(MDX_OPT_GN_FUSED) && L <= 64 && (size_t)HW * L * 16 <= (64u << 10)) {
-            p.cw = L > p.CC ? p.CC : L;
-            p.ncb = (p.CC + p.cw - 1) / p.cw;
-            p.nblk = 1;
-            p.pix = HW;
-            constexpr size_t lds = ((size_t)GNF_THREADS * 8 * 2 + (size_t)GNF_FOLD * 512 * 2 + 512 * 2 + 64 * 2 + 512 * 2) * sizeof(float);
-            if (mdx_opt(MDX_OPT_GN_FUSED_SMALL) && p.ncb * B >= 512 && p.cw <= 32) {     // the grid fills the chip: 256-thread blocks
-                constexpr size_t lds4 = ((size_t)256 * 8 * 2 + (size_t)GNF_FOLD * 512 * 2 + 512 * 2 + 64 * 2 + 512 * 2) * sizeof(float);
-                static MdxPerDeviceOnce attr4_once;
-                if (attr4_once.first()) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false, 256>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-                }
-                hipLaunchKernelGGL((gn_fused_kernel<false, 256>), dim3(p.ncb, B), dim3(256), lds4, st, p, MdxSplitInfo{});
-                MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused, 256 threads)");
-                return MDX_OK;
-            }
+    // fused single-launch path when one block can walk all pixels of its column block quickly: <= 64 KiB per block,
+    // i.e. the 16x16 and 8x8 latent levels (measured per shape: 8.7 vs 12.4 us at HW = 256, 7.5 vs 10.7 at HW = 64;
+    // at HW >= 1024 the few, long blocks lose to the two-launch slab scheme)
+    if (mdx_opt(MDX_OPT_GN_FUSED) && L <= 64 && (size_t)HW * L * 16 <= (64u << 10)) {
+        p.cw = L > p.CC ? p.CC : L;
+        p.ncb = (p.CC + p.cw - 1) / p.cw;
+        p.nblk = 1;
+        p.pix = HW;
+        *threads = GNF_THREADS;
+        if (mdx_opt(MDX_OPT_GN_FUSED_SMALL) && p.ncb * B >= 512 && p.cw <= 32) {     // the grid fills the chip: 256-thread blocks
+            *threads = 256;
+            *form = GN_FORM_FUSED_256;
+        } else if (p.pre && (HW + GNF_THREADS / p.cw - 1) / (GNF_THREADS / p.cw) <= GNF_KEEPN) {
             // every thread's pixels fit its registers (HW <= 8 rows of threads: the 8 x 8 ... 32 x 32 levels): one pass of loads
-            if (p.pre && (HW + GNF_THREADS / p.cw - 1) / (GNF_THREADS / p.cw) <= GNF_KEEPN) {
-                static MdxPerDeviceOnce attrk_once;
-                if (attrk_once.first()) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false, GNF_THREADS, GNF_KEEPN>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                }
-                hipLaunchKernelGGL((gn_fused_kernel<false, GNF_THREADS, GNF_KEEPN>), dim3(p.ncb, B), dim3(GNF_THREADS), lds, st, p,
-                                   MdxSplitInfo{});
-                MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused, one pass)");
-                return MDX_OK;
-            }
-            static MdxPerDeviceOnce attr_once;
-            if (attr_once.first()) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            }
-            hipLaunchKernelGGL(gn_fused_kernel<false>, dim3(p.ncb, B), dim3(GNF_THREADS), lds, st, p, MdxSplitInfo{});
-            MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused)");
-            return MDX_OK;
+            *form = GN_FORM_FUSED_ONE_PASS;
+        } else {
+            *form = GN_FORM_FUSED;
         }
+        return MDX_OK;
     }
     gn_geometry(p);
     MDX_REQUIRE((p.cw * 8) % p.cpg == 0 || p.ncb == 1, "mdx_groupnorm_f16: internal geometry error");
-    dim3 grid(p.nblk, p.ncb, B);
     MDX_REQUIRE(p.cw <= 64, "mdx_groupnorm_f16: %d channels per group is not supported", p.cpg);
-    const int cols = p.cw;
+    *form = GN_FORM_TWO_LAUNCH;
+    return MDX_OK;
+}
+
+extern "C" int mdx_groupnorm_query(int C1, int C2, int B, int HW, int groups, int colstats_nrb, int* out6) {
+    MDX_REQUIRE(out6 && colstats_nrb >= 0, "mdx_groupnorm_query: bad arguments");
+    GnParams p{};
+    int rc = gn_shape(p, C1, C2, B, HW, groups);
+    if (rc != MDX_OK) return rc;
+    int form = 0, threads = 0;
+    rc = gn_plan(p, colstats_nrb > 0, &form, &threads);
+    if (rc != MDX_OK) return rc;
+    out6[0] = form;
+    out6[1] = p.cw;
+    out6[2] = p.ncb;
+    out6[3] = p.nblk;
+    out6[4] = p.pix;
+    out6[5] = threads;
+    return MDX_OK;
+}
+
+static int groupnorm_impl(const void* x1, int C1, const void* x2, int C2, const float* gamma, const float* beta,
+                          const float* scale, const float* shift, int mod_ld, void* y, int B, int HW, int groups,
+                          float eps, int silu, float* ws, mdx_stream_t s, const float* cs1 = nullptr, int nrb1 = 0,
+                          const float* cs2 = nullptr, int nrb2 = 0) {
+    MDX_REQUIRE(x1 && gamma && beta && y && (ws || cs1), "mdx_groupnorm_f16: null pointer");
+    MDX_REQUIRE((C2 == 0) == (x2 == nullptr), "mdx_groupnorm_f16: x2/C2 mismatch");
+    MDX_REQUIRE((scale == nullptr) == (shift == nullptr), "mdx_groupnorm_scaleshift_f16: scale/shift mismatch");
+    GnParams p{};
+    int rc = gn_shape(p, C1, C2, B, HW, groups);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(!scale || mod_ld >= p.C, "mdx_groupnorm_scaleshift_f16: mod_ld < C");
+    MDX_REQUIRE(!cs1 || (nrb1 > 0 && (C2 == 0 || (cs2 && nrb2 > 0))), "mdx_groupnorm_colstats_f16: missing column statistics");
+    p.x1 = (const f16*)x1;
+    p.x2 = (const f16*)x2;
+    p.gamma = gamma;
+    p.beta = beta;
+    p.y = (f16*)y;
+    p.ws = ws;
+    p.eps = eps;
+    p.silu = silu;
+    p.scale = scale;
+    p.shift = shift;
+    p.mod_ld = mod_ld;
+    p.cs1 = cs1;
+    p.cs2 = cs2;
+    p.nrb1 = nrb1;
+    p.nrb2 = nrb2;
+    int form = 0, threads = 0;
+    rc = gn_plan(p, cs1 != nullptr, &form, &threads);
+    if (rc != MDX_OK) return rc;
+    hipStream_t st = (hipStream_t)s;
+    constexpr size_t lds = ((size_t)GNF_THREADS * 8 * 2 + (size_t)GNF_FOLD * 512 * 2 + 512 * 2 + 64 * 2 + 512 * 2) * sizeof(float);
+    switch (form) {
+    case GN_FORM_COLSTATS: {
+        dim3 grid(p.nblk, p.ncb, B);
+        hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(256), ((size_t)p.cw * 8 * 2 + 64 + (size_t)p.cw * 8 * 2) * sizeof(float), st, p);
+        MDX_LAUNCH_CHECK("mdx_groupnorm_colstats_f16");
+        return MDX_OK;
+    }
+    case GN_FORM_FUSED_256: {
+        constexpr size_t lds4 = ((size_t)256 * 8 * 2 + (size_t)GNF_FOLD * 512 * 2 + 512 * 2 + 64 * 2 + 512 * 2) * sizeof(float);
+        static MdxPerDeviceOnce attr4_once;
+        if (attr4_once.first()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false, 256>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+        }
+        hipLaunchKernelGGL((gn_fused_kernel<false, 256>), dim3(p.ncb, B), dim3(256), lds4, st, p, MdxSplitInfo{});
+        MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused, 256 threads)");
+        return MDX_OK;
+    }
+    case GN_FORM_FUSED_ONE_PASS: {
+        static MdxPerDeviceOnce attrk_once;
+        if (attrk_once.first()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false, GNF_THREADS, GNF_KEEPN>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+        hipLaunchKernelGGL((gn_fused_kernel<false, GNF_THREADS, GNF_KEEPN>), dim3(p.ncb, B), dim3(GNF_THREADS), lds, st, p,
+                           MdxSplitInfo{});
+        MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused, one pass)");
+        return MDX_OK;
+    }
+    case GN_FORM_FUSED: {
+        static MdxPerDeviceOnce attr_once;
+        if (attr_once.first()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+        hipLaunchKernelGGL(gn_fused_kernel<false>, dim3(p.ncb, B), dim3(GNF_THREADS), lds, st, p, MdxSplitInfo{});
+        MDX_LAUNCH_CHECK("mdx_groupnorm_f16(fused)");
+        return MDX_OK;
+    }
+    default:
+        break;
+    }
+    dim3 grid(p.nblk, p.ncb, B);
     // stats LDS: [trows][cols*8][2] floats with trows*cols <= 256 for every (possibly narrower, last) column block
     hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(256), ((size_t)256 * 8 * 2 + 512 * 2) * sizeof(float), st, p);
     MDX_LAUNCH_CHECK("mdx_groupnorm_f16(stats)");
-    hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(256), ((size_t)cols * 8 * 2 + 64) * sizeof(float), st, p);
+    hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(256), ((size_t)p.cw * 8 * 2 + 64) * sizeof(float), st, p);
     MDX_LAUNCH_CHECK("mdx_groupnorm_f16(apply)");
     return MDX_OK;
 }

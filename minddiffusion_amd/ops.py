@@ -166,6 +166,18 @@ def groupnorm(x1, x2, gamma, beta, eps, silu, ws=None, out=None, groups=32):
     return out
 
 
+GN_FORMS = ("two_launch", "fused", "fused_one_pass", "fused_256", "colstats")
+
+
+def groupnorm_query(C1, C2, B, HW, groups=32, colstats_nrb=0):
+    """The launch form a GroupNorm of this shape resolves to under the current library options (mdx_groupnorm_query; host only):
+    form is one of GN_FORMS; colstats_nrb > 0 asks about groupnorm_colstats."""
+    out = (ctypes.c_int * 6)()
+    _lib.check(_lib.load().mdx_groupnorm_query(int(C1), int(C2), int(B), int(HW), int(groups), int(colstats_nrb), out),
+               "mdx_groupnorm_query")
+    return dict(form=GN_FORMS[out[0]], cw=out[1], ncb=out[2], nblk=out[3], pix=out[4], threads=out[5])
+
+
 class FoldedColStats:
     """Column partials with more than 64 row blocks per sample (include/mdx.h: mdx_colstats_fold_f32): `raw` [B * nrb, C, 2] is
     what the producer writes, `folded` [B * nrb2, C, 2] what the GroupNorm reads; groupnorm_colstats launches the fold."""
