@@ -539,6 +539,44 @@ int mdx_softmax_rows_f16(void* x, long ld, int rows, int cols, float scale, mdx_
 int mdx_vae_gaussian_sample_f32(const void* moments, int ld, const float* noise, float* out, int B, int zc, int HW,
                                 mdx_stream_t s);
 
+/* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
+ * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
+ *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)
+ *     W'[n][k] = fp16_rne(fmaf(scale, acc, base[n][k]))
+ * base fp32 [N][K] row-major, A fp32 [R][K], B fp32 [N][R] (A or B NULL, or R == 0: a pure re-pack, W' = fp16(base)), R <= 64,
+ * K % 8 == 0.  With gamma != NULL the LayerNorm fold of mdx_gemm_desc.ln_stats is applied to the MERGED matrix exactly as
+ * ops.fold_layernorm does from its fp16 input: the stored value is wg = fp16(fp32(double(W') double(gamma[k]))) (the exact product, through fp32 as that conversion goes),
+ * S[n] = fp32(sum_k double(wg)), cb[n] = fp32(sum_k double(W') double(beta[k]) + bias[n]) (bias may be NULL); S / cb point at
+ * this matrix's first entry.  Reductions are deterministic (no atomics).
+ * The matrix occupies rows [dst_n0, dst_n0 + N) of a destination of dst_N rows:
+ *   MDX_LORA_ROWMAJOR  fp16 [dst_N][ld];
+ *   MDX_LORA_TILED     the packed weight storage of mdx_gemm_f16: [ceil(dst_N/64)][ceil(K/64)][64][8][8], position q of row r
+ *                      holds logical chunk q ^ ((r >> 1) & 7); padding columns are written as zeros, and the matrix that ends
+ *                      the destination (dst_n0 + N == dst_N) also writes the zero padding rows;
+ *   MDX_LORA_FRAG      MFMA-fragment pieces [dst_N/32][piece_stride][512] (ops.pack_frag_weight); the matrix's K/16 k-steps are
+ *                      pieces [piece_offset, piece_offset + K/16) of every column tile (the per-wave streams of
+ *                      mdx_st_tail_f16 / mdx_st_head_f16).
+ * Bytes of dst outside that region are not touched. */
+enum { MDX_LORA_ROWMAJOR = 0, MDX_LORA_TILED = 1, MDX_LORA_FRAG = 2 };
+typedef struct mdx_lora_merge_desc {
+    const float* base;
+    const float* A;
+    const float* B;
+    int N, K, R;
+    float scale;
+    const float* gamma;
+    const float* beta;
+    const float* bias;
+    float* S;
+    float* cb;
+    void* dst;
+    int layout;
+    int ld;               /* ROWMAJOR: row stride in halves */
+    int dst_n0, dst_N;
+    int piece_stride, piece_offset;     /* FRAG */
+} mdx_lora_merge_desc;
+int mdx_lora_merge_f16(const mdx_lora_merge_desc* d, mdx_stream_t s);
+
 /* ---- probes used by tests to pin hardware layout assumptions (not on the hot path) */
 int mdx_probe_mfma_32x32x16_f16(const void* a, const void* b, float* c, mdx_stream_t s);
 /* Same for v_mfma_f32_16x16x32_f16 (the conv8p core): a, b = 64 lanes x 8 halves, c = 64 lanes x 4 floats. */

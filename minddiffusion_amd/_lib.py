@@ -65,8 +65,19 @@ class StHeadDesc(ctypes.Structure):
     ]
 
 
+class LoraMergeDesc(ctypes.Structure):
+    """struct mdx_lora_merge_desc (include/mdx.h)."""
+    _fields_ = [
+        ("base", c_void_p), ("A", c_void_p), ("B", c_void_p), ("N", c_int), ("K", c_int), ("R", c_int), ("scale", c_float),
+        ("gamma", c_void_p), ("beta", c_void_p), ("bias", c_void_p), ("S", c_void_p), ("cb", c_void_p),
+        ("dst", c_void_p), ("layout", c_int), ("ld", c_int), ("dst_n0", c_int), ("dst_N", c_int),
+        ("piece_stride", c_int), ("piece_offset", c_int),
+    ]
+
+
 EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU, EPI_PRELU = 0, 1, 2, 3, 4
 OUT_ROWMAJOR, OUT_TRANSPOSED, OUT_D2S2 = 0, 1, 2
+LORA_ROWMAJOR, LORA_TILED, LORA_FRAG = 0, 1, 2
 
 # name -> (restype, argtypes); also the list the CPU test checks against include/mdx.h
 SIGNATURES = {
@@ -115,6 +126,7 @@ SIGNATURES = {
     "mdx_st_tail_f16": (c_int, [ctypes.POINTER(StTailDesc), c_void_p]),
     "mdx_st_tail_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mdx_st_tail_stream_bytes": (c_size_t, [c_int]),
+    "mdx_lora_merge_f16": (c_int, [ctypes.POINTER(LoraMergeDesc), c_void_p]),
     "mdx_timestep_embedding_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "mdx_dense_small_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),

@@ -11,6 +11,9 @@ WUKONG_UNET = dict(image_size=32, in_channels=4, out_channels=4, model_channels=
                    num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_heads=8, use_spatial_transformer=True,
                    transformer_depth=1, context_dim=768, use_checkpoint=True, legacy=False, use_fp16=True)
 
+# vision/wukong-huahua/configs/v1-inference-chinese-lora.yaml:24-40: the same UNet with LoRA on the attention projections
+WUKONG_LORA_UNET = dict(WUKONG_UNET, enable_lora=True, lora_rank=4, lora_alpha=4)
+
 # vision/wukong-huahua/configs/wukong-huahua_inpaint_inference.yaml:20-36: the same UNet on 9 input channels
 # (4 latent + 1 resized mask + 4 masked-image latent), LatentInpaintDiffusion / conditioning_key 'hybrid'
 WUKONG_INPAINT_UNET = dict(WUKONG_UNET, in_channels=9)

@@ -95,6 +95,26 @@ class LatentDiffusion:
     def unet(self):
         return self.model.diffusion_model
 
+    # ---- LoRA (WK txt2img.py:222-225: base checkpoint, then `load_param_into_net(model, lora_ckpt)`); the UNet holds the adapter
+    def load_lora(self, params_or_path, strict=True):
+        """Apply a LoRA adapter to the UNet: a {name: array} dict (UNet names, with or without the "model.diffusion_model."
+        prefix of a LatentDiffusion checkpoint) or the path of an adapter .ckpt."""
+        from ....ms_checkpoint import UNET_PREFIX, load_lora_checkpoint
+        if isinstance(params_or_path, (str, bytes)) or hasattr(params_or_path, "__fspath__"):
+            params = load_lora_checkpoint(params_or_path)
+        else:
+            params = {(k[len(UNET_PREFIX):] if k.startswith(UNET_PREFIX) else k): v for k, v in params_or_path.items()}
+        self.unet.load_lora_state_dict(params, strict=strict)
+        return self
+
+    def set_lora_scale(self, m=1.0):
+        self.unet.set_lora_scale(m)
+        return self
+
+    def unload_lora(self):
+        self.unet.unload_lora()
+        return self
+
     # ---- ddpm.py:290-306 (positional cond) and WK ddpm.py:276-278 (keywords); dict = hybrid conditioning (inpaint.py:84)
     def _split_cond(self, cond, c_concat=None, c_crossattn=None):
         key = self.model.conditioning_key

@@ -21,6 +21,7 @@ import ctypes
 import math
 
 import os
+import re
 import weakref
 
 import numpy as np
@@ -31,6 +32,15 @@ from ...._lib import MdxError
 from ....weights import check_state_dict
 
 f16, f32 = torch.float16, torch.float32
+
+# parameter-name prefixes of the delta-tuning package's LoRADense (lora_a / lora_b); see UNetModel.lora_parameter_shapes
+LORA_PREFIXES = ("tk_delta_", "mindpet_delta_")
+_LORA_KEY = re.compile(r"^(.*)\.(" + "|".join(LORA_PREFIXES) + r")lora_([ab])$")
+_LORA_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
+
+
+def is_lora_key(name):
+    return _LORA_KEY.match(name) is not None
 
 
 def _round_up(x, m):
@@ -71,7 +81,12 @@ class UNetModel:
                  num_classes=None, use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1,
                  num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
                  use_new_attention_order=False, use_spatial_transformer=False, transformer_depth=1, context_dim=None,
-                 n_embed=None, legacy=True, use_linear_in_transformer=False, device="cuda:0"):
+                 n_embed=None, legacy=True, use_linear_in_transformer=False, enable_lora=False, lora_rank=4, lora_alpha=4,
+                 device="cuda:0"):
+        """enable_lora / lora_rank / lora_alpha (WK openaimodel.py:302-304): to_q, to_k, to_v and to_out.0 of every
+        CrossAttention become LoRA targets (WK attention.py:118-126).  The reference wires these keywords for Wukong only;
+        here they work for every configuration (SDv2 included).  The adapter is MERGED into the packed weights in place
+        (load_lora_state_dict), so the denoising loop is the code that runs without it."""
         # openaimodel.py:305-321 argument checks
         if use_spatial_transformer:
             assert context_dim is not None, "context_dim is required with use_spatial_transformer"
@@ -118,6 +133,15 @@ class UNetModel:
         self.use_graph = True
         self.max_context_len = 80  # 77 CLIP tokens rounded up to a multiple of 8 (V^T rows are 16-B chunked)
         self.last_launch_count = 0
+        self.enable_lora = bool(enable_lora)
+        self.lora_rank = int(lora_rank)
+        self.lora_alpha = float(lora_alpha)
+        if self.enable_lora and not (1 <= self.lora_rank <= 64 and self.lora_alpha != 0):
+            raise ValueError(f"UNetModel: lora_rank must be in [1, 64] and lora_alpha non-zero (got {lora_rank}, {lora_alpha})")
+        self._lora_base = {}      # target name -> fp32 device copy of the base matrix (enable_lora only)
+        self._lora_sites = {}     # target name -> the places the matrix lives in self.w (kwargs of ops.lora_merge)
+        self._lora = None         # target name -> (A [rank, in], B [out, rank]) fp32 on the device
+        self._lora_mult = 1.0
 
     # ------------------------------------------------------------------ structure (openaimodel.py:351-526)
     def _heads(self, ch, num_heads):
@@ -244,10 +268,41 @@ class UNetModel:
             s["id_predictor.1.conv.bias"] = (self.n_embed,)
         return s
 
+    def _lora_targets(self):
+        """(reference name of the Dense, out, in) of every LoRA target, in structure order."""
+        for pre, layer in self._named_layers():
+            if layer[0] != "st":
+                continue
+            inner = layer[2] * layer[3]
+            for k in range(self.transformer_depth):
+                t = pre + f"transformer_blocks.{k}."
+                for a, cd in (("attn1.", inner), ("attn2.", self.context_dim)):
+                    for n in _LORA_TARGETS:
+                        yield t + a + n, inner, (inner if n in ("to_q", "to_out.0") else cd)
+
+    def lora_parameter_shapes(self, prefix=LORA_PREFIXES[0]):
+        """name -> shape of the adapter parameters: for to_q / to_k / to_v / to_out.0 of attn1 and attn2 of every transformer
+        block, `<dense>.<prefix>lora_a` (rank, in) and `<dense>.<prefix>lora_b` (out, rank).  `prefix` is one of LORA_PREFIXES, the
+        two names the delta-tuning package has used; the reference tree does not contain that package, so these key names are
+        UNPINNED (DESIGN.md)."""
+        if prefix not in LORA_PREFIXES:
+            raise ValueError(f"lora_parameter_shapes: prefix must be one of {LORA_PREFIXES}")
+        s = {}
+        for name, nout, nin in self._lora_targets():
+            s[f"{name}.{prefix}lora_a"] = (self.lora_rank, nin)
+            s[f"{name}.{prefix}lora_b"] = (nout, self.lora_rank)
+        return s
+
     # ------------------------------------------------------------------ weights
     def _dev(self, a, dtype):
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _dev_own(self, a, dtype):
+        """_dev, but never the caller's own tensor: what the model keeps (the merge sources) must not change when the caller
+        reuses its buffer for the next checkpoint."""
+        t = self._dev(a, dtype)
+        return t.clone() if t is a else t
 
     def _pack_conv(self, wt, cin_pad=None, cout_pad=None):
         """[Cout,Cin,kh,kw] -> the packed GEMM weight storage (ops.pack_conv_weight, include/mdx.h)."""
@@ -270,8 +325,14 @@ class UNetModel:
         """params: name -> array/tensor keyed by the reference's parameter names.  Packs everything into
         the kernels' layouts on the device (fp16 weights, fp32 biases / norm affine)."""
         shapes = self.parameter_shapes()
+        lora_params = {}
+        if self.enable_lora:    # the adapter may ride in the same dict (one merged checkpoint) or come in a second call
+            lora_params = {k: v for k, v in params.items() if is_lora_key(k)}
+            params = {k: v for k, v in params.items() if k not in lora_params}
         # every owned parameter is needed to run: missing keys always raise; strict additionally rejects unexpected ones
         check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True, "UNetModel.load_state_dict")
+        if lora_params:
+            lora_params = self._check_lora(lora_params, strict, "UNetModel.load_state_dict")
         P = params
         w = {}
         w["te0.w"] = self._dev(P["time_embed.0.weight"], f16)
@@ -396,10 +457,136 @@ class UNetModel:
         self._plans = {}
         self._ctx_key = None
         self._ctx_ref = None
+        self._lora = None       # a new base load drops the adapter (it is merged again below when `params` carried one)
+        self._lora_base, self._lora_sites = {}, {}
+        if self.enable_lora:
+            for name, _, _ in self._lora_targets():
+                self._lora_base[name] = self._dev_own(P[name + ".weight"], f32)
+            self._lora_sites = self._find_lora_sites()
+            if lora_params:
+                self._set_lora(lora_params)
         return self
 
     def weight_bytes(self):
-        return sum(t.numel() * t.element_size() for t in self.w.values())
+        """Bytes of device memory the loaded weights hold; with enable_lora this includes the fp32 copies of the LoRA target
+        matrices (the merge source) and a loaded adapter."""
+        n = sum(t.numel() * t.element_size() for t in self.w.values())
+        n += sum(t.numel() * t.element_size() for t in self._lora_base.values())
+        if self._lora:
+            n += sum(a.numel() * 4 + b.numel() * 4 for a, b in self._lora.values())
+        return n
+
+    # ------------------------------------------------------------------ LoRA
+    def _find_lora_sites(self):
+        """Every place a LoRA target matrix lives in self.w, as keyword arguments of ops.lora_merge.  The plan-time copies
+        self._frag_w (3x3 conv weights in fragment-major form) and self._geglu80 (ff.net.0.proj re-packed at unit 80) hold no
+        LoRA target -- conv and feed-forward weights are not adapted (WK attention.py:118-126) -- so they are left alone."""
+        w = self.w
+        T, F = ops.LORA_TILED, ops.LORA_FRAG
+        sites = {}
+        for pre, layer in self._named_layers():
+            if layer[0] != "st":
+                continue
+            inner = layer[2] * layer[3]
+            ks = inner // 16
+            for k in range(self.transformer_depth):
+                t = pre + f"transformer_blocks.{k}."
+
+                def tiled(key, n0=0, dst_n=inner, norm=None):
+                    kw = dict(dst=w[key + ".w"], layout=T, dst_n0=n0, dst_N=dst_n)
+                    if norm is not None and (key + ".s") in w:      # LayerNorm-folded consumer (ops.fold_layernorm)
+                        kw.update(gamma=w[t + norm + ".g"], beta=w[t + norm + ".b"], S=w[key + ".s"][n0:], cb=w[key + ".cb"][n0:])
+                    return kw
+
+                def frag(key, slot, per_wave):
+                    return dict(dst=w[t + key], layout=F, dst_N=inner, piece_stride=per_wave * ks, piece_offset=slot * ks)
+                merged = (t + "attn1.qkv.w") in w
+                for i, n in enumerate("qkv"):
+                    if merged:
+                        here = [tiled(t + "attn1.qkv", i * inner, 3 * inner, "norm1")]
+                    elif n == "v":
+                        here = [tiled(t + "attn1.v")]
+                    else:
+                        here = [tiled(t + "attn1.qk", i * inner, 2 * inner)]
+                    if (t + "head.stream") in w:        # [proj_in | to_q | to_k | to_v] per wave (ops.pack_st_head)
+                        here.append(frag("head.stream", 1 + i, 4))
+                    sites[t + f"attn1.to_{n}"] = here
+                sites[t + "attn2.to_q"] = [tiled(t + "attn2.q", norm="norm2")]
+                sites[t + "attn2.to_k"] = [tiled(t + "attn2.k")]
+                sites[t + "attn2.to_v"] = [tiled(t + "attn2.v")]
+                sites[t + "attn1.to_out.0"] = [tiled(t + "attn1.o")]
+                sites[t + "attn2.to_out.0"] = [tiled(t + "attn2.o")]
+                if (t + "tail.stream") in w:            # [to_out1 | to_q2 | to_out2 | ...] per wave (ops.pack_st_tail)
+                    for slot, name in enumerate(("attn1.to_out.0", "attn2.to_q", "attn2.to_out.0")):
+                        sites[t + name].append(frag("tail.stream", slot, 16))
+        assert set(sites) == set(self._lora_base)
+        return sites
+
+    def _check_lora(self, params, strict, who):
+        """Validate an adapter dict (either key prefix, not both) -> {canonical-prefix name: value}.  Raises before anything
+        is written."""
+        found = {m.group(2) for m in map(_LORA_KEY.match, params) if m}
+        if len(found) > 1:
+            raise KeyError(f"{who}: adapter keys mix the prefixes {sorted(found)}")
+        prefix = found.pop() if found else LORA_PREFIXES[0]
+        shapes = self.lora_parameter_shapes(prefix)
+        check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True, who)
+        return {k.replace("." + prefix, "." + LORA_PREFIXES[0]): params[k] for k in shapes}
+
+    def _set_lora(self, checked):
+        p = LORA_PREFIXES[0]
+        self._lora = {name: (self._dev_own(checked[f"{name}.{p}lora_a"], f32), self._dev_own(checked[f"{name}.{p}lora_b"], f32))
+                      for name in self._lora_base}
+        self._merge_lora()
+
+    def _merge_lora(self):
+        """(Re)write every LoRA target from its fp32 base and the current adapter / scale: one ops.lora_merge launch per place
+        the matrix lives.  In place -- the tensors of self.w keep their addresses, so plans and captured graphs stay valid; only
+        the cached context projections (attn2.to_k / to_v of the text context) are stale and run again on the next call."""
+        scale = self._lora_mult * self.lora_alpha / self.lora_rank
+        for name, base in self._lora_base.items():
+            a, b = self._lora[name] if self._lora else (None, None)
+            for site in self._lora_sites[name]:
+                ops.lora_merge(base, A=a, B=b, scale=scale, **site)
+        self._ctx_key = None
+        self._ctx_ref = None
+
+    def _need_lora(self, who):
+        if not self.enable_lora:
+            raise MdxError(f"UNetModel.{who}: the model was built without enable_lora=True")
+        if self.w is None:
+            raise MdxError(f"UNetModel.{who}: load_state_dict() must be called first (the adapter is merged into the base weights)")
+
+    def load_lora_state_dict(self, params, strict=True):
+        """Apply a LoRA adapter ({name: array} keyed `<dense>.tk_delta_lora_a|b` or `<dense>.mindpet_delta_lora_a|b`): the
+        second call of the reference's flow (WK txt2img.py:222-225).  Missing adapter keys always raise; strict additionally
+        rejects unexpected ones.  Replaces a previously loaded adapter; buffers, plans and graphs are kept."""
+        self._need_lora("load_lora_state_dict")
+        self._set_lora(self._check_lora(dict(params), strict, "UNetModel.load_lora_state_dict"))
+        return self
+
+    def set_lora_scale(self, m=1.0):
+        """Adapter strength: the merged weights become W + m * (lora_alpha / lora_rank) * B A (m = 1: the reference's layer)."""
+        self._need_lora("set_lora_scale")
+        m = float(m)
+        if not math.isfinite(m):
+            raise ValueError("set_lora_scale: the multiplier must be finite")
+        self._lora_mult = m
+        if self._lora:
+            self._merge_lora()
+        return self
+
+    def unload_lora(self):
+        """Back to the base weights (bit for bit what load_state_dict packed)."""
+        self._need_lora("unload_lora")
+        if self._lora:
+            self._lora = None
+            self._merge_lora()
+        return self
+
+    @property
+    def lora_loaded(self):
+        return self._lora is not None
 
     # ------------------------------------------------------------------ planning
     class _Plan:

@@ -156,3 +156,14 @@ def load_latent_diffusion(path):
     allp = load_checkpoint(path)
     pick = lambda pre: {k[len(pre):]: v for k, v in allp.items() if k.startswith(pre)}
     return pick(UNET_PREFIX), pick(VAE_PREFIX), pick(TEXT_PREFIX)
+
+
+def load_lora_checkpoint(path):
+    """A LoRA adapter checkpoint (wukong-huahua/txt2img.py:222-225 `ms.load_checkpoint(lora_ckpt_path)`) -> the dict
+    UNetModel.load_lora_state_dict takes: only the UNet's `lora_a` / `lora_b` parameters, "model.diffusion_model." removed.
+    The trainer may have saved other trainable parameters next to them; they are dropped."""
+    from .ldm.modules.diffusionmodules.openaimodel import is_lora_key
+    out = {k: v for k, v in load_checkpoint(path, strip_prefix=UNET_PREFIX).items() if is_lora_key(k)}
+    if not out:
+        raise ValueError(f"{path}: no LoRA parameters (`{UNET_PREFIX}...lora_a` / `lora_b`) in this checkpoint")
+    return out

@@ -477,6 +477,12 @@ def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, 
     if act_slope is not None:    # MDX_EPI_PRELU: per-channel slopes, fp32 [C], column n uses act_slope[n % C]
         d.act_slope, d.act_slope_n = act_slope.data_ptr(), int(act_slope.numel())
     d.geglu_unit = int(geglu_unit)      # GEGLU: packing unit of w / bias / ln_s (0 = 64; 80 = the 128 x 160 tile)
+    # The C struct holds raw device pointers only.  The descriptor keeps its tensors alive (python-side attribute), so that an
+    # argument built in the call expression -- `bias=interleave(cb)` -- is not handed back to the caching allocator, and to
+    # whoever allocates next, between this call and the launch.
+    d._tensors = tuple(t for t in (a, a2, w, bias, rowbias, residual, out, workspace, out2, stats_out, ln_stats, ln_s,
+                                   colstats_out, skip_a, skip_a2, skip_w, gn_colstats, gn_gamma, gn_beta, w_sub, xattn_k,
+                                   xattn_vt, act_slope) if t is not None)
     return d
 
 
@@ -1024,3 +1030,51 @@ def make_st_head_desc(x, colstats, nrb, stream, vec, tok, qk, vt, vt_ld, B, toke
 
 def st_head_run(desc):
     _lib.check(_lib.load().mdx_st_head_f16(ctypes.byref(desc), _stream()), "mdx_st_head_f16")
+
+
+LORA_ROWMAJOR, LORA_TILED, LORA_FRAG = _lib.LORA_ROWMAJOR, _lib.LORA_TILED, _lib.LORA_FRAG
+
+
+def lora_merge(base, dst, layout, A=None, B=None, scale=1.0, gamma=None, beta=None, bias=None, S=None, cb=None, ld=0,
+               dst_n0=0, dst_N=None, piece_stride=0, piece_offset=0):
+    """mdx_lora_merge_f16 (include/mdx.h): W' = fp16(base + scale * B @ A) of one nn.Dense weight [N, K], written IN PLACE into
+    rows [dst_n0, dst_n0 + N) of `dst` in the layout a kernel reads -- LORA_ROWMAJOR ([dst_N, ld] fp16), LORA_TILED (the
+    pack_gemm_weight storage) or LORA_FRAG (pack_frag_weight pieces; k-steps [piece_offset, piece_offset + K/16) of
+    `piece_stride` pieces per column tile).  base fp32 [N, K]; A fp32 [R, K] and B fp32 [N, R] or None (a pure re-pack).
+    gamma / beta (/ bias): the LayerNorm fold of fold_layernorm computed from the merged matrix; S and cb ([>= N] fp32 views
+    that start at this matrix's first row) receive the row sums and the folded bias."""
+    _chk(base, f32, "base"); _chk(dst, f16, "dst")
+    N, K = base.shape
+    R = 0
+    if A is not None or B is not None:
+        if A is None or B is None:
+            raise _lib.MdxError("lora_merge: A and B go together")
+        _chk(A, f32, "A"); _chk(B, f32, "B")
+        R = A.shape[0]
+        if tuple(A.shape) != (R, K) or tuple(B.shape) != (N, R):
+            raise _lib.MdxError(f"lora_merge: A {tuple(A.shape)} / B {tuple(B.shape)} do not match base {(N, K)}")
+    dst_N = N + dst_n0 if dst_N is None else int(dst_N)
+    if layout == LORA_ROWMAJOR:
+        ld = int(ld) or K
+        need = (dst_N - 1) * ld + K
+    elif layout == LORA_TILED:
+        need = ((dst_N + 63) // 64 * 64) * ((K + 63) // 64 * 64)
+    elif layout == LORA_FRAG:
+        piece_stride = int(piece_stride) or K // 16
+        need = dst_N // 32 * piece_stride * 512
+    else:
+        raise _lib.MdxError(f"lora_merge: unknown layout {layout}")
+    if dst.numel() < need:
+        raise _lib.MdxError(f"lora_merge: dst holds {dst.numel()} halves, the destination needs {need}")
+    for name, v, n in (("gamma", gamma, K), ("beta", beta, K), ("bias", bias, N), ("S", S, N), ("cb", cb, N)):
+        _chk(v, f32, name)
+        if v is not None and v.numel() < n:
+            raise _lib.MdxError(f"lora_merge: {name} holds {v.numel()} values, needs {n}")
+    d = _lib.LoraMergeDesc()
+    d.base, d.A, d.B = base.data_ptr(), (A.data_ptr() if R else 0), (B.data_ptr() if R else 0)
+    d.N, d.K, d.R, d.scale = N, K, R, float(scale)
+    d.gamma, d.beta, d.bias, d.S, d.cb = (0 if v is None else v.data_ptr() for v in (gamma, beta, bias, S, cb))
+    d.dst, d.layout, d.ld, d.dst_n0, d.dst_N = dst.data_ptr(), int(layout), int(ld), int(dst_n0), dst_N
+    d.piece_stride, d.piece_offset = int(piece_stride), int(piece_offset)
+    _lib.check(_lib.load().mdx_lora_merge_f16(ctypes.byref(d), _stream()), "mdx_lora_merge_f16")
+    return dst
