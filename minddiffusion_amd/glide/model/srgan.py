@@ -20,7 +20,8 @@ import torch
 
 from ..._lib import MdxError
 from ... import ops
-from ...ldm.modules.diffusionmodules.model import _PlanBuilder, _run_plan
+from ...ldm.modules.diffusionmodules.model import _run_plan
+from ...planner import PlanBuilder
 
 f16, f32 = torch.float16, torch.float32
 
@@ -165,12 +166,11 @@ class Generator:
             raise MdxError("SRGAN Generator: load_state_dict() must be called first")
         dev, w = self.device, self.w
         P = Generator._Plan()
-        pb = _PlanBuilder(self, P, B)
-        A = pb.A
+        pb = PlanBuilder(dev, B)
         P.x_static = torch.zeros((B, 3, H, W), dtype=f32, device=dev)
-        c1 = A.get((B, H, W, CH))
+        c1 = pb.get((B, H, W, CH))
         pb.emit(lambda: ops.srgan_conv_in(P.x_static, w["in.w"], w["in.b"], w["in.a"], out=c1), "srgan_conv_in",
-                2 * B * H * W * CH * 243, f"9x9 3->64 {H}x{W}")
+                2 * B * H * W * CH * 243, 1, f"9x9 3->64 {H}x{W}")
 
         def conv(src, wt, bias, out, n, h, wd, **kw):
             pb.gemm(a=src, w=wt, N=n, B=B, H=h, W=wd, c1=CH, out=out, out_ld=CH, bias=bias, ksize=3, **kw)
@@ -178,30 +178,31 @@ class Generator:
         t = c1
         for i in range(TRUNK):                           # ResidualBlock.construct, srgan.py:50-57
             p = f"trunk.{i}."
-            u = A.get((B, H, W, CH))
+            u = pb.get((B, H, W, CH))
             conv(t, w[p + "conv1.w"], w[p + "conv1.b"], u, CH, H, W, epilogue=ops.EPI_PRELU, act_slope=w[p + "a"])
-            t2 = A.get((B, H, W, CH))
+            t2 = pb.get((B, H, W, CH))
             conv(u, w[p + "conv2.w"], w[p + "conv2.b"], t2, CH, H, W, residual=t, residual_ld=CH)
-            A.release(u)
+            pb.release(u)
             if t is not c1:
-                A.release(t)
+                pb.release(t)
             t = t2
-        s = A.get((B, H, W, CH))                         # out = conv1 + PReLU(conv2(trunk)), srgan.py:108-113
+        s = pb.get((B, H, W, CH))                         # out = conv1 + PReLU(conv2(trunk)), srgan.py:108-113
         conv(t, w["c2.w"], w["c2.b"], s, CH, H, W, epilogue=ops.EPI_PRELU, act_slope=w["c2.a"], residual=c1, residual_ld=CH)
-        A.release(t)
-        A.release(c1)
+        pb.release(t)
+        pb.release(c1)
         h, wd = H, W
         for j in range(self.n_sub):                      # SubpixelConvolutionLayer.construct, srgan.py:67-72
             p = f"subpixel_conv.{j}."
-            o = A.get((B, 2 * h, 2 * wd, CH))
+            o = pb.get((B, 2 * h, 2 * wd, CH))
             conv(s, w[p + "w"], w[p + "b"], o, 4 * CH, h, wd, epilogue=ops.EPI_PRELU, act_slope=w[p + "a"],
                  out_mode=ops.OUT_D2S2)
-            A.release(s)
+            pb.release(s)
             s, h, wd = o, 2 * h, 2 * wd
         P.out_nchw = torch.empty((B, 3, h, wd), dtype=f32, device=dev)
         pb.emit(lambda: ops.srgan_conv_out(s, w["out.w"], w["out.b"], B, h, wd, out=P.out_nchw), "srgan_conv_out",
-                2 * B * h * wd * 3 * CH * 81, f"9x9 64->3 {h}x{wd}")
-        pb.finish()
+                2 * B * h * wd * 3 * CH * 81, 1, f"9x9 64->3 {h}x{wd}")
+        pb.finish(P)
+        P.activation_bytes = pb.A.total
         P.out_hw = (h, wd)
         self._plans[key] = P
         return P

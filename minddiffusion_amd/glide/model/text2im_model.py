@@ -26,7 +26,7 @@ import torch
 from ... import ops
 from ..._lib import MdxError
 from ...weights import check_state_dict
-from ...ldm.modules.diffusionmodules.openaimodel import _Arena, _round_up
+from ...planner import PlanBuilder, capture_or_eager, round_up
 
 f16, f32 = torch.float16, torch.float32
 XF_LN_EPS = 1e-7   # MindSpore nn.LayerNorm default epsilon (xf.py:26-33 passes none)
@@ -55,8 +55,8 @@ class Text2ImUNet:
         self.image_size = image_size
         self.device = torch.device(device)
         self.time_embed_dim = 4 * model_channels
-        self.cin_pad = _round_up(in_channels, 8)
-        self.cout_pad = _round_up(out_channels, 8)
+        self.cin_pad = round_up(in_channels, 8)
+        self.cout_pad = round_up(out_channels, 8)
         self.input_blocks, self.middle_block, self.output_blocks = self._structure()
         self.w = None
         self._plans = {}
@@ -279,362 +279,38 @@ class Text2ImUNet:
         n_down = len(self.channel_mult) - 1
         if H % (1 << n_down) or W % (1 << n_down):
             raise MdxError(f"image {H}x{W} is not divisible by 2^{n_down}")
-        dev, w = self.device, self.w
-        P = Text2ImUNet._Plan()
-        A = _Arena(dev)
-        main, meta, descs = [], [], []
-        gn_need = [4]
-        ctx, xw, xh = self.text_ctx, self.xf_width, self.xf_heads
-        mc, ted = self.model_channels, self.time_embed_dim
-        P.B, P.H, P.W = B, H, W
-        P.x_static = torch.zeros((B, 3, H, W), dtype=f32, device=dev)
-        P.low_static = None
-        P.t_static = torch.zeros((B,), dtype=f32, device=dev)
-        P.tok_static = torch.zeros((B, ctx), dtype=torch.int32, device=dev)
-        P.mask_static = torch.ones((B, ctx), dtype=torch.int32, device=dev)
+        P = self._plans[key] = _GlidePlanner(self, B, H, W).build()
+        return P
 
-        text_mode = [False]      # True while the text-only prefix of the plan is being emitted (see forward_nhwc: text_epoch)
+    def _text_transformer(self, pb, S, R, alloc_out):
+        """The text transformer (text2im_model.py:88-99, xf.py:36-154) on the R prompt rows of S.tok_static / S.mask_static, emitted
+        into `pb`; returns xf_out [R, ctx, xw] (allocated by alloc_out()).  The step plan and the whole-loop tables (_text_plan)
+        both call this: one op sequence, so the same bits on the same prompt whatever pass computes it."""
+        w, ctx, xw, xh = self.w, self.text_ctx, self.xf_width, self.xf_heads
 
-        late_text = [False]      # True while an AttentionBlock emits its encoder_kv projections: text-only too, spliced into the prefix
-        late_main, late_meta = [], []
-
-        def emit(fn, kind, flops=0, launches=1, info=""):
-            if late_text[0]:
-                late_main.append(fn)
-                late_meta.append({"kind": kind, "flops": int(flops), "launches": launches, "info": info, "text": True})
-                return late_meta[-1]
-            main.append(fn)
-            meta.append({"kind": kind, "flops": int(flops), "launches": launches, "info": info, "text": text_mode[0]})
-            return meta[-1]
-
-        producer, gn_calls = {}, []     # tensor address -> the GEMM descriptor that wrote it last; GroupNorm calls
-        _arena_get = A.get
-
-        def _get(shape, dtype=f16):     # a buffer handed out again is no longer "the output of that GEMM" (pools, attention, ...)
-            t = _arena_get(shape, dtype)
-            producer.pop(t.data_ptr(), None)
-            return t
-        A.get = _get
-
-        def gemm(**kw):
-            d = ops.make_gemm_desc(**kw)
-            descs.append(d)
-            producer[kw["out"].data_ptr()] = d
-            ks, st, up = kw.get("ksize", 1), kw.get("stride", 1), kw.get("upsample", 0)
-            hs_, ws2 = (2 * kw["H"], 2 * kw["W"]) if up else (kw["H"], kw["W"])
-            pad = 1 if ks == 3 else 0
-            m_rows = kw["B"] * ((hs_ + 2 * pad - ks) // st + 1) * ((ws2 + 2 * pad - ks) // st + 1)
-            kdim = ks * ks * (kw["c1"] + kw.get("c2", 0))
-            mrec = emit(lambda d=d: ops.gemm_run(d), "gemm", 2 * m_rows * kw["N"] * kdim, 1, f"M={m_rows} N={kw['N']} K={kdim} k{ks}")
-            mrec["desc"] = d                # launches / split are filled in by ops.account_gemm_launches below
-
-        def gn(x1, x2, g, b, silu, out, scale=None, shift=None):
-            Bq, HW, C1 = x1.shape
-            C = C1 + (0 if x2 is None else x2.shape[2])
-            gn_need[0] = max(gn_need[0], ops.groupnorm_ws_floats(Bq, HW, C))
-            call = dict(x1=x1, x2=x2, cs=None, meta=len(meta), g=g, b=b, eps=1e-5,
-                        prod=(producer.get(x1.data_ptr()), None if x2 is None else producer.get(x2.data_ptr())))
-            producer.pop(out.data_ptr(), None)
-            gn_calls.append(call)
-
-            def run(c=call):
-                if c["cs"] is not None:      # statistics from the producers' epilogues (ops.wire_groupnorm_colstats)
-                    cs1, n1, cs2, n2 = c["cs"]
-                    return ops.groupnorm_colstats(x1, cs1, n1, x2, cs2, n2, g, b, 1e-5, silu, out=out, scale=scale,
-                                                  shift=shift, mod_ld=self._emb_total if scale is not None else 0)
-                if scale is None:
-                    return ops.groupnorm(x1, x2, g, b, 1e-5, silu, ws=P.gn_ws, out=out)
-                return ops.groupnorm_scaleshift(x1, x2, g, b, scale, shift, self._emb_total, 1e-5, silu, ws=P.gn_ws, out=out)
-            emit(run, "groupnorm", 0, 2, f"B={Bq} HW={HW} C={C}")
-
-        def dense(src, rows_b, tokens, cin, nout, wt, bias=None, residual=None, epilogue=ops.EPI_NONE, out=None,
-                  out_ld=None, out_mode=ops.OUT_ROWMAJOR, out_bs=0, src2=None, c2=0):
-            if out is None:
-                out = A.get((rows_b, tokens, nout))
-                out_ld = nout
-            # text-only launches never split K: their sums must not depend on how many prompt rows a pass carries (the whole-loop
-            # tables of begin_loop run the same GEMMs on other row counts and promise the same bits)
-            gemm(a=src, w=wt, N=nout, B=rows_b, H=tokens, W=1, c1=cin - c2, out=out, out_ld=out_ld, a2=src2, c2=c2,
-                 bias=bias, residual=residual, residual_ld=nout if residual is not None else 0, epilogue=epilogue,
-                 out_mode=out_mode, out_bs=out_bs, splitk=1 if (text_mode[0] or late_text[0]) else 0)
-            return out
-
-        def conv3(src, cin, cout, wt, bias, h, wd, upsample=0, residual=None, skip=None, wsub=None):
-            """skip = (x, x2, c1, c2, packed 1x1 weights): the ResBlock's skip_connection rides on this launch as extra K tiles
-            (mdx_gemm_desc.skip_w, as in the latent-diffusion planner); `bias` then holds the sum of both convs' biases."""
-            ho, wo = (2 * h, 2 * wd) if upsample else (h, wd)
-            out = A.get((B, ho * wo, cout))
-            kw = {}
-            if skip is not None:
-                kw = dict(skip_a=skip[0], skip_a2=skip[1], skip_c1=skip[2], skip_c2=skip[3], skip_w=skip[4])
-            if wsub is not None:
-                kw["w_sub"] = wsub
-            gemm(a=src, w=wt, N=cout, B=B, H=h, W=wd, c1=cin, out=out, out_ld=cout, bias=bias, residual=residual,
-                 residual_ld=cout if residual is not None else 0, ksize=3, upsample=upsample, **kw)
-            if skip is not None:
-                meta[-1]["flops"] += 2 * B * ho * wo * cout * (skip[2] + skip[3])
-                meta[-1]["info"] += f" +skip1x1 K={skip[2] + skip[3]}"
-            return out, ho, wo
-
-        def skip_fusable(a2, c1, c2, cout, ho, wo, wt):
-            """unet.py:214-218 `skip_connection(x) + h`: can the 1x1 conv ride on conv2 (whole 64-channel K tiles, HALO kernel)?"""
-            if not ops.get_option("unet_skip_fuse") or c1 % 64 or c2 % 64 or cout % 64:
-                return False
-            probe = ops.make_gemm_desc(a=a2, w=wt, N=cout, B=B, H=ho, W=wo, c1=cout, out=a2, out_ld=cout, ksize=3)
-            return ops.gemm_query(probe)[3] == 1
-
-        # ---- text transformer (text2im_model.py:88-99, xf.py:36-154) on all B rows.  It depends on the tokens alone, so it is the
-        # plan's PREFIX: a caller whose tokens do not change between calls (the super-resolution loop: 27 steps on one prompt;
-        # the base model's unconditional half is re-drawn every step, main_funcs.py:37) skips it (forward_nhwc text_epoch)
-        text_mode[0] = True
-        cat_in = torch.empty((B, ted + xw), dtype=f32, device=dev)      # [silu-free e1 | last text token]
-        x_tok = A.get((B, ctx, xw))
-        emit(lambda: ops.glide_text_embed(P.tok_static, P.mask_static, w["tok"], w["pos"], w["pad"], out=x_tok), "small")
-        ln = A.get((B, ctx, xw))
+        def layernorm(src, name, out):
+            pb.emit(lambda: ops.layernorm(src, w[name + ".g"], w[name + ".b"], XF_LN_EPS, out=out), "layernorm")
+        x_tok = pb.get((R, ctx, xw))
+        pb.emit(lambda: ops.glide_text_embed(S.tok_static, S.mask_static, w["tok"], w["pos"], w["pad"], out=x_tok), "small")
+        ln = pb.get((R, ctx, xw))
         for l in range(self.xf_layers):
             t = f"transformer.resblocks.{l}."
-            emit(lambda t=t, x_tok=x_tok: ops.layernorm(x_tok, w[t + "ln_1.g"], w[t + "ln_1.b"], XF_LN_EPS, out=ln), "layernorm")
-            qk = dense(ln, B, ctx, xw, 2 * xw, w[t + "qk.w"], bias=w[t + "qk.b"])
-            vt = A.get((B, xw, ctx))
-            dense(ln, B, ctx, xw, xw, w[t + "v.w"], bias=w[t + "v.b"], out=vt, out_ld=ctx, out_mode=ops.OUT_TRANSPOSED)
-            ao = A.get((B, ctx, xw))
-            emit(lambda qk=qk, vt=vt, ao=ao: ops.attention(
-                qk.data_ptr(), qk.data_ptr() + xw * 2, vt.data_ptr(), ao.data_ptr(), B, xh, 64, ctx, ctx, 64 ** -0.5,
-                ctx * 2 * xw, 2 * xw, ctx * 2 * xw, 2 * xw, xw * ctx, ctx, ctx * xw, xw),
-                "attention", 4 * B * xh * ctx * ctx * 64)
-            x2 = dense(ao, B, ctx, xw, xw, w[t + "proj.w"], bias=w[t + "proj.b"], residual=x_tok)
-            A.release(qk); A.release(vt); A.release(ao); A.release(x_tok)
-            emit(lambda t=t, x2=x2: ops.layernorm(x2, w[t + "ln_2.g"], w[t + "ln_2.b"], XF_LN_EPS, out=ln), "layernorm")
-            hfc = dense(ln, B, ctx, xw, 4 * xw, w[t + "fc.w"], bias=w[t + "fc.b"], epilogue=ops.EPI_GELU)
-            x_tok = dense(hfc, B, ctx, 4 * xw, xw, w[t + "fc2.w"], bias=w[t + "fc2.b"], residual=x2)
-            A.release(hfc); A.release(x2)
-        xf_out = A.get((B, ctx, xw))     # kept for every AttentionBlock's encoder_kv
-        emit(lambda x_tok=x_tok: ops.layernorm(x_tok, w["final_ln.g"], w["final_ln.b"], XF_LN_EPS, out=xf_out), "layernorm")
-        A.release(ln)
-        emit(lambda: cat_in[:, ted:].copy_(xf_out[:, -1]), "small")     # dtype-converting copy (plumbing); text-only too
-        text_mode[0] = False
-        P.n_text = len(main)      # ops [0, n_text) write xf_out and cat_in[:, ted:] -- both dedicated / never released
-
-        # ---- time embedding + xf_proj (text2im_model.py:102-105), then all emb_layers (unet.py:163-170) at once
-        t_emb = torch.empty((B, mc), dtype=f32, device=dev)
-        emb = torch.empty((B, ted), dtype=f32, device=dev)
-        P.emb_all = torch.empty((B, self._emb_total), dtype=f32, device=dev)
-        emit(lambda: ops.timestep_embedding(P.t_static, mc, out=t_emb), "small")
-        emit(lambda: ops.dense_small(t_emb, w["te0.w"], w["te0.b"], act_out=True, out=cat_in[:, :ted]), "small")
-        # (round 5) the SiLU in front of every emb_layer (unet.py:163-170) is applied ONCE, on the way out of the GEMV that produces
-        # emb -- `emb` feeds nothing else here -- instead of on the way into the emb_layers GEMV, where every one of its ~25 000
-        # output columns re-evaluated it on all B x 768 inputs (the 159 us "small" op of profiles/r05_glide_op_profile.txt, every
-        # step).  Same value either way: silu of the same fp32 number.
-        emit(lambda: ops.dense_small(cat_in, w["te2proj.w"], w["te2proj.b"], act_out=True, out=emb), "small")
-        emit(lambda: ops.dense_small(emb, w["emb.w"], w["emb.b"], out=P.emb_all), "small")
-        n_emb_mark = len(main)    # ops [n_text, n_emb) turn (timestep, last text token) into P.emb_all: a loop runs them once (begin_loop)
-
-        def resblock(pre, x, x2, cin, cout, mode, h, wd):
-            """unet.py:178-218 (scale-shift norm; up/down act on BOTH h and x)."""
-            hw = h * wd
-            a = A.get((B, hw, cin))
-            gn(x, x2, w[pre + "n1.g"], w[pre + "n1.b"], True, a)
-            if mode == "up":
-                assert x2 is None and cin == cout
-                hbuf, ho, wo = conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd, upsample=1,
-                                     wsub=w.get(pre + "conv1.wsub"))
-                xs = A.get((B, ho * wo, cin))
-                emit(lambda x=x, xs=xs: ops.upsample_nearest2x(x, B, h, wd, cin, out=xs), "small")
-            elif mode == "down":
-                assert x2 is None and cin == cout
-                ap = A.get((B, hw // 4, cin))
-                emit(lambda a=a, ap=ap: ops.avgpool2x2(a, B, h, wd, cin, out=ap), "small")
-                hbuf, ho, wo = conv3(ap, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h // 2, wd // 2)
-                A.release(ap)
-                xs = A.get((B, hw // 4, cin))
-                emit(lambda x=x, xs=xs: ops.avgpool2x2(x, B, h, wd, cin, out=xs), "small")
-            else:
-                hbuf, ho, wo = conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd)
-                xs = x
-            A.release(a)
-            eoff = self._emb_off[pre]
-            a2 = A.get((B, ho * wo, cout))
-            gn(hbuf, None, w[pre + "n2.g"], w[pre + "n2.b"], True, a2,
-               scale=P.emb_all[:, eoff:eoff + cout], shift=P.emb_all[:, eoff + cout:eoff + 2 * cout])
-            A.release(hbuf)
-            if cin != cout:
-                c2 = 0 if x2 is None else x2.shape[2]
-                if mode not in ("up", "down") and skip_fusable(a2, cin - c2, c2, cout, ho, wo, w[pre + "conv2.w"]):
-                    if (pre + "conv2skip.b") not in w:
-                        w[pre + "conv2skip.b"] = (w[pre + "conv2.b"] + w[pre + "skip.b"]).contiguous()
-                    out, _, _ = conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2skip.b"], ho, wo,
-                                      skip=(x, x2, cin - c2, c2, w[pre + "skip.w"]))
-                    A.release(a2)
-                    return out, ho, wo
-                skip = dense(x, B, hw, cin, cout, w[pre + "skip.w"], bias=w[pre + "skip.b"], src2=x2, c2=c2)
-            else:
-                assert x2 is None
-                skip = xs
-            out, _, _ = conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2.b"], ho, wo, residual=skip)
-            A.release(a2)
-            if skip is not x:
-                A.release(skip)
-            return out, ho, wo
-
-        kv_keep = []
-
-        def attnblock(pre, x, c, heads, h, wd):
-            """unet.py:254-310: q from the image, keys/values = [text (ctx) | image (T)]."""
-            T = h * wd
-            nk = ctx + T
-            a = A.get((B, T, c))
-            gn(x, None, w[pre + "norm.g"], w[pre + "norm.b"], False, a)
-            # keys / values = [text | image]: the text rows (encoder_kv of xf_out, unet.py:289-297) depend on the tokens alone, so
-            # they live in buffers of their own (not the arena: they must survive the step) and their two projections join the
-            # plan's text prefix; only the image rows are written per step
-            # Memory: these buffers are per (B, H, W) PLAN and are never arena-reused -- B * (text + image) * 3 c halves per
-            # AttentionBlock (base model at 16 rows: 22 blocks, 0.14 GB; up-sampler at 8 rows: 0.02 GB), plus a second captured
-            # graph (graph_main) per plan.  Whether the text rows are current is the CALLER's statement (text_epoch): nothing on the
-            # device re-checks tok_static, and forward_nhwc() without an epoch recomputes the prefix
-            vtb = torch.zeros((B, c, nk), dtype=f16, device=dev)
-            if ops.get_option("glide_qkv_merge") and T % 8 == 0:
-                # (round 6) q | k | v of the image tokens in ONE launch: q and k side by side in a [B, text + image, 2 c] buffer --
-                # rows [ctx, nk) written here (q | k), the k half of rows [0, ctx) by the text projection (its q half is never read)
-                # -- and V transposed into vtb; the attention kernel takes q and k as strided views of that buffer
-                qkb = torch.zeros((B, nk, 2 * c), dtype=f16, device=dev)
-                kbuf = qkb[:, :, c:]
-                kv_keep.append((kbuf, vtb, qkb))
-                gemm(a=a, w=w[pre + "qkv.w"], N=3 * c, B=B, H=T, W=1, c1=c, out=qkb[:, ctx:], out_ld=2 * c, bias=w[pre + "qkv.b"],
-                     out_bs=nk * 2 * c, out2=vtb[:, :, ctx:], out2_ld=nk, n_split=2 * c)
-                # AttentionBlock.norm has no activation (unet.py:267-272): the merged projection can apply it to its A fragments from
-                # the producer's column statistics (mdx_gemm_desc.gn_colstats on a dense launch, as the LDM planner's
-                # unet_gn_proj_fuse).  Decided when the statistics are wired; on success the GroupNorm op is dropped
-                if (ops.get_option("glide_gn_qkv_fuse") and T % 64 == 0 and c % 64 == 0 and c <= 2560
-                        and producer.get(x.data_ptr()) is not None):
-                    gn_calls[-1]["proj"] = dict(desc=descs[-1], meta=len(meta) - 1)
-                q_ptr, q_bs, q_ld = qkb[:, ctx:].data_ptr(), nk * 2 * c, 2 * c
-                k_ptr, k_bs, k_ld = kbuf.data_ptr(), nk * 2 * c, 2 * c
-                q = None
-            else:
-                q = dense(a, B, T, c, c, w[pre + "q.w"], bias=w[pre + "q.b"])
-                kbuf = torch.zeros((B, nk, c), dtype=f16, device=dev)
-                kv_keep.append((kbuf, vtb))
-                dense(a, B, T, c, c, w[pre + "k.w"], bias=w[pre + "k.b"], out=kbuf[:, ctx:], out_ld=c, out_bs=nk * c)
-                dense(a, B, T, c, c, w[pre + "v.w"], bias=w[pre + "v.b"], out=vtb[:, :, ctx:], out_ld=nk,
-                      out_mode=ops.OUT_TRANSPOSED)
-                q_ptr, q_bs, q_ld = q.data_ptr(), T * c, c
-                k_ptr, k_bs, k_ld = kbuf.data_ptr(), nk * c, c
-            late_text[0] = True
-            dense(xf_out, B, ctx, xw, c, w[pre + "ek.w"], bias=w[pre + "ek.b"], out=kbuf, out_ld=k_ld, out_bs=k_bs)
-            dense(xf_out, B, ctx, xw, c, w[pre + "ev.w"], bias=w[pre + "ev.b"], out=vtb, out_ld=nk,
-                  out_mode=ops.OUT_TRANSPOSED)
-            late_text[0] = False
-            o = a   # the normed input is dead after the projections
-            emit(lambda vtb=vtb, o=o, q_ptr=q_ptr, q_bs=q_bs, q_ld=q_ld, k_ptr=k_ptr, k_bs=k_bs, k_ld=k_ld: ops.attention(
-                q_ptr, k_ptr, vtb.data_ptr(), o.data_ptr(), B, heads, 64, T, nk, 64 ** -0.5,
-                q_bs, q_ld, k_bs, k_ld, c * nk, nk, T * c, c), "attention", 4 * B * heads * T * nk * 64)
-            out = dense(o, B, T, c, c, w[pre + "proj.w"], bias=w[pre + "proj.b"], residual=x)
-            if q is not None:
-                A.release(q)
-            A.release(a)
-            return out
-
-        # ---- UNet walk (text2im_model.py:106-123)
-        xin = A.get((B, H * W, self.cin_pad))
-        if self.super_res:
-            s_low = self.low_size
-            P.low_static = torch.zeros((B, 3, s_low, s_low), dtype=f32, device=dev)
-            emit(lambda: ops.glide_superres_input(P.x_static, P.low_static, out=xin), "small")
-        else:
-            emit(lambda: ops.nchw_to_nhwc(P.x_static, self.cin_pad, out=xin), "small")
-        h, wd = H, W
-        hs, cur = [], None
-        for i, blk in enumerate(self.input_blocks):
-            for j, layer in enumerate(blk):
-                pre = f"input_blocks.{i}.{j}."
-                if layer[0] == "conv":
-                    cur, h, wd = conv3(xin, self.cin_pad, layer[2], w[pre + "w"], w[pre + "b"], h, wd)
-                    A.release(xin)
-                elif layer[0] == "res":
-                    new, h2, w2 = resblock(pre, cur, None, layer[1], layer[2], layer[3], h, wd)
-                    if not any(cur is s_[0] for s_ in hs):
-                        A.release(cur)
-                    cur, h, wd = new, h2, w2
-                else:
-                    new = attnblock(pre, cur, layer[1], layer[2], h, wd)
-                    A.release(cur)
-                    cur = new
-            hs.append((cur, h, wd))
-        for j, layer in enumerate(self.middle_block):
-            pre = f"middle_block.{j}."
-            if layer[0] == "res":
-                new, _, _ = resblock(pre, cur, None, layer[1], layer[2], layer[3], h, wd)
-            else:
-                new = attnblock(pre, cur, layer[1], layer[2], h, wd)
-            if not any(cur is s_[0] for s_ in hs):
-                A.release(cur)
-            cur = new
-        for i, blk in enumerate(self.output_blocks):
-            skip, sh, sw = hs.pop()
-            assert (sh, sw) == (h, wd)
-            for j, layer in enumerate(blk):
-                pre = f"output_blocks.{i}.{j}."
-                if layer[0] == "res" and j == 0:
-                    new, _, _ = resblock(pre, cur, skip, layer[1], layer[2], layer[3], h, wd)
-                    A.release(cur); A.release(skip)
-                    cur = new
-                elif layer[0] == "res":
-                    new, h, wd = resblock(pre, cur, None, layer[1], layer[2], layer[3], h, wd)
-                    A.release(cur)
-                    cur = new
-                else:
-                    new = attnblock(pre, cur, layer[1], layer[2], h, wd)
-                    A.release(cur)
-                    cur = new
-        ch0 = int(self.channel_mult[0] * mc)
-        a = A.get((B, h * wd, ch0))
-        gn(cur, None, w["out.g"], w["out.b"], True, a)
-        P.out_nhwc = torch.empty((B, h * wd, self.cout_pad), dtype=f16, device=dev)
-        gemm(a=a, w=w["out2.w"], N=self.cout_pad, B=B, H=h, W=wd, c1=ch0, out=P.out_nhwc, out_ld=self.cout_pad,
-             bias=w["out2.b"], ksize=3)
-
-        need = max([ops.gemm_workspace_bytes(d) for d in descs] + [16])
-        P.gemm_ws = ops.new_gemm_workspace(need, dev)
-        for d in descs:
-            d.workspace = P.gemm_ws.data_ptr()
-            d.workspace_bytes = P.gemm_ws.numel() * 4
-        if late_main:       # the AttentionBlocks' encoder_kv projections join the text prefix (they read xf_out only)
-            nt = P.n_text
-            main[nt:nt] = late_main
-            meta[nt:nt] = late_meta
-            for c_ in gn_calls:
-                if c_["meta"] >= nt:
-                    c_["meta"] += len(late_main)
-            P.n_text = nt + len(late_main)
-            n_emb_mark += len(late_main)
-        P.n_emb = n_emb_mark
-        P.kv_keep = kv_keep
-        P.gn_ws = torch.empty(gn_need[0], dtype=f32, device=dev)
-        P.colstats = {}
-        import os
-        ops.wire_groupnorm_colstats(gn_calls if os.environ.get("MDX_UNET_GN_COLSTATS", "1") != "0" else [], meta, B, dev,
-                                    P.colstats)
-        # a wired producer may resolve to another tile-table row than the one the workspace was sized for: size it again
-        need2 = max([ops.gemm_workspace_bytes(d) for d in descs] + [16])
-        if need2 > P.gemm_ws.numel() * 4:
-            P.gemm_ws = ops.new_gemm_workspace(need2, dev)
-            for d in descs:
-                d.workspace = P.gemm_ws.data_ptr()
-                d.workspace_bytes = P.gemm_ws.numel() * 4
-        if any(m.get("dead") for m in meta):      # GroupNorm launches that moved into the GEMM behind them (all behind the emb chain)
-            keep = [i for i, m in enumerate(meta) if not m.get("dead")]
-            assert all(i >= P.n_emb for i, m in enumerate(meta) if m.get("dead"))
-            main[:] = [main[i] for i in keep]
-            meta[:] = [meta[i] for i in keep]
-        ops.check_colstats_wiring(descs)
-        ops.account_gemm_launches(meta)
-        P.main, P.meta, P.descs, P.arena = main, meta, descs, A
-        P.keep = (t_emb, cat_in, emb, xf_out)
-        P.graph, P.graph_main, P.graph_body, P.graph_failed = None, None, None, False
-        P.text_epoch = None       # what the text prefix was last run for (forward_nhwc)
-        P.loop_epoch = None       # the begin_loop() context whose text rows the key / value buffers hold
-        self._plans[key] = P
-        return P
+            layernorm(x_tok, t + "ln_1", ln)
+            qk = pb.dense(ln, R, ctx, xw, 2 * xw, w[t + "qk.w"], bias=w[t + "qk.b"])
+            vt = pb.get((R, xw, ctx))
+            pb.dense(ln, R, ctx, xw, xw, w[t + "v.w"], bias=w[t + "v.b"], out=vt, out_ld=ctx, out_mode=ops.OUT_TRANSPOSED)
+            ao = pb.get((R, ctx, xw))
+            pb.attention(qk, vt, ao, xh, 64)
+            x2 = pb.dense(ao, R, ctx, xw, xw, w[t + "proj.w"], bias=w[t + "proj.b"], residual=x_tok)
+            pb.release(qk, vt, ao, x_tok)
+            layernorm(x2, t + "ln_2", ln)
+            hfc = pb.dense(ln, R, ctx, xw, 4 * xw, w[t + "fc.w"], bias=w[t + "fc.b"], epilogue=ops.EPI_GELU)
+            x_tok = pb.dense(hfc, R, ctx, 4 * xw, xw, w[t + "fc2.w"], bias=w[t + "fc2.b"], residual=x2)
+            pb.release(hfc, x2)
+        xf_out = alloc_out()
+        layernorm(x_tok, "final_ln", xf_out)
+        pb.release(ln)
+        return xf_out
 
     # ------------------------------------------------------------------ execution
     def forward_nhwc(self, x, timesteps, tokens, mask, low_res=None, text_epoch=None):
@@ -676,17 +352,11 @@ class Text2ImUNet:
         whole step, the step without its text prefix (text_epoch), the step without text prefix AND time embedding (begin_loop)."""
         if P.graph is not None or P.graph_failed or not self.use_graph:
             return
-        try:
-            for op in P.main:
-                op()
-            torch.cuda.synchronize()
-            P.graph = ops.capture_graph(P.main)
-            P.graph_main = ops.capture_graph(P.main[P.n_text:])
-            P.graph_body = ops.capture_graph(P.main[P.n_emb:])
-        except Exception as e:  # pragma: no cover
-            P.graph, P.graph_main, P.graph_body, P.graph_failed = None, None, None, True
-            import warnings
-            warnings.warn(f"hipGraph capture failed, running eagerly: {e}")
+        graphs = capture_or_eager([P.main, P.main[P.n_text:], P.main[P.n_emb:]], warm=[P.main])
+        if graphs is None:
+            P.graph_failed = True
+        else:
+            P.graph, P.graph_main, P.graph_body = graphs
 
     # ------------------------------------------------------------------ whole-loop tables (round 6)
     # The sampling loops know every prompt and every timestep before their first step: main_funcs.py:21-44 draws the unconditional
@@ -717,62 +387,25 @@ class Text2ImUNet:
         if self.w is None:
             raise MdxError("load_state_dict() must be called before the first forward")
         dev, w = self.device, self.w
-        ctx, xw, xh = self.text_ctx, self.xf_width, self.xf_heads
+        ctx, xw = self.text_ctx, self.xf_width
         T = Text2ImUNet._TextPlan()
-        A = _Arena(dev)
-        main, descs = [], []
+        pb = PlanBuilder(dev, R)
+        pb.splitk = 1       # never split K: the same sums whatever the row count (see the block comment above)
         T.tok_static = torch.zeros((R, ctx), dtype=torch.int32, device=dev)
         T.mask_static = torch.ones((R, ctx), dtype=torch.int32, device=dev)
-
-        def dense(src, tokens, cin, nout, wt, bias=None, residual=None, epilogue=ops.EPI_NONE, out=None, out_ld=None,
-                  out_mode=ops.OUT_ROWMAJOR):
-            if out is None:
-                out = A.get((R, tokens, nout))
-                out_ld = nout
-            d = ops.make_gemm_desc(a=src, w=wt, N=nout, B=R, H=tokens, W=1, c1=cin, out=out, out_ld=out_ld, bias=bias,
-                                   residual=residual, residual_ld=nout if residual is not None else 0, epilogue=epilogue,
-                                   out_mode=out_mode, splitk=1)
-            descs.append(d)
-            main.append(lambda d=d: ops.gemm_run(d))
-            return out
-
-        x_tok = A.get((R, ctx, xw))
-        main.append(lambda: ops.glide_text_embed(T.tok_static, T.mask_static, w["tok"], w["pos"], w["pad"], out=x_tok))
-        ln = A.get((R, ctx, xw))
-        for l in range(self.xf_layers):
-            t = f"transformer.resblocks.{l}."
-            main.append(lambda t=t, x_tok=x_tok: ops.layernorm(x_tok, w[t + "ln_1.g"], w[t + "ln_1.b"], XF_LN_EPS, out=ln))
-            qk = dense(ln, ctx, xw, 2 * xw, w[t + "qk.w"], bias=w[t + "qk.b"])
-            vt = A.get((R, xw, ctx))
-            dense(ln, ctx, xw, xw, w[t + "v.w"], bias=w[t + "v.b"], out=vt, out_ld=ctx, out_mode=ops.OUT_TRANSPOSED)
-            ao = A.get((R, ctx, xw))
-            main.append(lambda qk=qk, vt=vt, ao=ao: ops.attention(
-                qk.data_ptr(), qk.data_ptr() + xw * 2, vt.data_ptr(), ao.data_ptr(), R, xh, 64, ctx, ctx, 64 ** -0.5,
-                ctx * 2 * xw, 2 * xw, ctx * 2 * xw, 2 * xw, xw * ctx, ctx, ctx * xw, xw))
-            x2 = dense(ao, ctx, xw, xw, w[t + "proj.w"], bias=w[t + "proj.b"], residual=x_tok)
-            A.release(qk); A.release(vt); A.release(ao); A.release(x_tok)
-            main.append(lambda t=t, x2=x2: ops.layernorm(x2, w[t + "ln_2.g"], w[t + "ln_2.b"], XF_LN_EPS, out=ln))
-            hfc = dense(ln, ctx, xw, 4 * xw, w[t + "fc.w"], bias=w[t + "fc.b"], epilogue=ops.EPI_GELU)
-            x_tok = dense(hfc, ctx, 4 * xw, xw, w[t + "fc2.w"], bias=w[t + "fc2.b"], residual=x2)
-            A.release(hfc); A.release(x2)
-        xf_out = torch.empty((R, ctx, xw), dtype=f16, device=dev)
-        main.append(lambda x_tok=x_tok: ops.layernorm(x_tok, w["final_ln.g"], w["final_ln.b"], XF_LN_EPS, out=xf_out))
+        xf_out = self._text_transformer(pb, T, R, lambda: torch.empty((R, ctx, xw), dtype=f16, device=dev))
         T.last = torch.empty((R, xw), dtype=f32, device=dev)
-        main.append(lambda: T.last.copy_(xf_out[:, -1]))
+        pb.emit(lambda: T.last.copy_(xf_out[:, -1]), "small")
         T.k, T.vt = [], []
         for pre, c in self._attn_layers():
             kb = torch.empty((R, ctx, c), dtype=f16, device=dev)
             vb = torch.empty((R, c, ctx), dtype=f16, device=dev)
-            dense(xf_out, ctx, xw, c, w[pre + "ek.w"], bias=w[pre + "ek.b"], out=kb, out_ld=c)
-            dense(xf_out, ctx, xw, c, w[pre + "ev.w"], bias=w[pre + "ev.b"], out=vb, out_ld=ctx, out_mode=ops.OUT_TRANSPOSED)
+            pb.dense(xf_out, R, ctx, xw, c, w[pre + "ek.w"], bias=w[pre + "ek.b"], out=kb, out_ld=c)
+            pb.dense(xf_out, R, ctx, xw, c, w[pre + "ev.w"], bias=w[pre + "ev.b"], out=vb, out_ld=ctx, out_mode=ops.OUT_TRANSPOSED)
             T.k.append(kb)
             T.vt.append(vb)
-        need = max([ops.gemm_workspace_bytes(d) for d in descs] + [16])
-        T.gemm_ws = ops.new_gemm_workspace(need, dev)
-        for d in descs:
-            d.workspace = T.gemm_ws.data_ptr()
-            d.workspace_bytes = T.gemm_ws.numel() * 4
-        T.main, T.descs, T.arena, T.xf_out, T.R = main, descs, A, xf_out, R
+        pb.finish(T)
+        T.xf_out, T.R = xf_out, R
         self._text_plans[R] = T
         return T
 
@@ -895,3 +528,234 @@ class SuperResText2ImUNet(Text2ImUNet):
         return ops.nhwc_to_nchw(out, self.out_channels, x.shape[2], x.shape[3])
 
     __call__ = construct
+
+
+class _GlidePlanner(PlanBuilder):
+    """One (B, H, W) plan of a Text2ImUNet on the shared plan builder.  What is GLIDE's own: ops that depend on the tokens alone
+    are marked (`text`), never split K and form the plan's prefix [0, n_text); the AttentionBlock over [text | image] keys; the
+    FiLM ResBlock; the n_text / n_emb marks."""
+
+    def __init__(self, net, B, H, W):
+        super().__init__(net.device, B, track_producers=True)
+        self.net, self.w, self.H, self.W = net, net.w, H, W
+        self.mod_ld = net._emb_total
+        self.tag = {"text": False}
+        self.late = ([], [])    # the AttentionBlocks' encoder_kv projections: text-only too, spliced into the prefix
+        self.kv_keep = []
+        self.P = Text2ImUNet._Plan()
+
+    def text_ops(self, on, late=False):
+        """Route what is emitted next: on = text-only launches (splitk = 1: their sums must not depend on how many prompt rows a
+        pass carries -- the whole-loop tables of begin_loop run the same GEMMs on other row counts and promise the same bits);
+        late = into the side list that build() splices in behind the text transformer."""
+        self.tag = {"text": on}
+        self.splitk = 1 if on else 0
+        self.into = self.late if late else (self.main, self.meta)
+
+    def build(self):
+        P, net, w, B, dev = self.P, self.net, self.w, self.B, self.dev
+        H, W = self.H, self.W
+        ctx, xw = net.text_ctx, net.xf_width
+        mc, ted = net.model_channels, net.time_embed_dim
+        P.B, P.H, P.W = B, H, W
+        P.x_static = torch.zeros((B, 3, H, W), dtype=f32, device=dev)
+        P.low_static = None
+        P.t_static = torch.zeros((B,), dtype=f32, device=dev)
+        P.tok_static = torch.zeros((B, ctx), dtype=torch.int32, device=dev)
+        P.mask_static = torch.ones((B, ctx), dtype=torch.int32, device=dev)
+        # ---- text transformer on all B rows.  It depends on the tokens alone, so it is the plan's PREFIX: a caller whose tokens
+        # do not change between calls (the super-resolution loop: 27 steps on one prompt; the base model's unconditional half is
+        # re-drawn every step, main_funcs.py:37) skips it (forward_nhwc text_epoch)
+        self.text_ops(True)
+        cat_in = torch.empty((B, ted + xw), dtype=f32, device=dev)      # [silu-free e1 | last text token]
+        xf_out = self.xf_out = net._text_transformer(self, P, B, lambda: self.get((B, ctx, xw)))   # kept for every encoder_kv
+        self.emit(lambda: cat_in[:, ted:].copy_(xf_out[:, -1]), "small")     # dtype-converting copy (plumbing); text-only too
+        self.text_ops(False)
+        n_text = len(self.main)      # ops [0, n_text) write xf_out and cat_in[:, ted:] -- both dedicated / never released
+        # ---- time embedding + xf_proj (text2im_model.py:102-105), then all emb_layers (unet.py:163-170) at once
+        t_emb = torch.empty((B, mc), dtype=f32, device=dev)
+        emb = torch.empty((B, ted), dtype=f32, device=dev)
+        P.emb_all = torch.empty((B, net._emb_total), dtype=f32, device=dev)
+        self.emit(lambda: ops.timestep_embedding(P.t_static, mc, out=t_emb), "small")
+        self.emit(lambda: ops.dense_small(t_emb, w["te0.w"], w["te0.b"], act_out=True, out=cat_in[:, :ted]), "small")
+        # (round 5) the SiLU in front of every emb_layer (unet.py:163-170) is applied ONCE, on the way out of the GEMV that produces
+        # emb -- `emb` feeds nothing else here -- instead of on the way into the emb_layers GEMV, where every one of its ~25 000
+        # output columns re-evaluated it on all B x 768 inputs (the 159 us "small" op of profiles/r05_glide_op_profile.txt, every
+        # step).  Same value either way: silu of the same fp32 number.
+        self.emit(lambda: ops.dense_small(cat_in, w["te2proj.w"], w["te2proj.b"], act_out=True, out=emb), "small")
+        self.emit(lambda: ops.dense_small(emb, w["emb.w"], w["emb.b"], out=P.emb_all), "small")
+        n_emb = len(self.main)    # ops [n_text, n_emb) turn (timestep, last text token) into P.emb_all: a loop runs them once (begin_loop)
+        self.walk()
+        late_main, late_meta = self.late
+        if late_main:       # the AttentionBlocks' encoder_kv projections join the text prefix (they read xf_out only)
+            self.main[n_text:n_text] = late_main
+            self.meta[n_text:n_text] = late_meta
+            for c in self.gn_calls:
+                if c["meta"] >= n_text:
+                    c["meta"] += len(late_main)
+        P.n_text, P.n_emb = n_text + len(late_main), n_emb + len(late_main)
+        self.finish(P)
+        P.kv_keep, P.colstats = self.kv_keep, self.colstats
+        P.keep = (t_emb, cat_in, emb, xf_out)
+        P.graph, P.graph_main, P.graph_body, P.graph_failed = None, None, None, False
+        P.text_epoch = None       # what the text prefix was last run for (forward_nhwc)
+        P.loop_epoch = None       # the begin_loop() context whose text rows the key / value buffers hold
+        return P
+
+    def after_wiring(self):     # GroupNorm launches that moved into the GEMM behind them are all behind the emb chain
+        assert all(i >= self.P.n_emb for i, m in enumerate(self.meta) if m.get("dead"))
+
+    def resblock(self, pre, x, x2, cin, cout, mode, h, wd):
+        """unet.py:178-218 (scale-shift norm; up/down act on BOTH h and x)."""
+        net, w, B, P = self.net, self.w, self.B, self.P
+        hw = h * wd
+        a = self.get((B, hw, cin))
+        self.gn(x, x2, w[pre + "n1.g"], w[pre + "n1.b"], 1e-5, True, a)
+        if mode == "up":
+            assert x2 is None and cin == cout
+            hbuf, ho, wo = self.conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd, upsample=1,
+                                      wsub=w.get(pre + "conv1.wsub"))
+            xs = self.get((B, ho * wo, cin))
+            self.emit(lambda: ops.upsample_nearest2x(x, B, h, wd, cin, out=xs), "small")
+        elif mode == "down":
+            assert x2 is None and cin == cout
+            ap = self.get((B, hw // 4, cin))
+            self.emit(lambda: ops.avgpool2x2(a, B, h, wd, cin, out=ap), "small")
+            hbuf, ho, wo = self.conv3(ap, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h // 2, wd // 2)
+            self.release(ap)
+            xs = self.get((B, hw // 4, cin))
+            self.emit(lambda: ops.avgpool2x2(x, B, h, wd, cin, out=xs), "small")
+        else:
+            hbuf, ho, wo = self.conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd)
+            xs = x
+        self.release(a)
+        eoff = net._emb_off[pre]
+        a2 = self.get((B, ho * wo, cout))
+        self.gn(hbuf, None, w[pre + "n2.g"], w[pre + "n2.b"], 1e-5, True, a2,
+                scale=P.emb_all[:, eoff:eoff + cout], shift=P.emb_all[:, eoff + cout:eoff + 2 * cout])
+        self.release(hbuf)
+        if cin != cout:
+            c2 = 0 if x2 is None else x2.shape[2]
+            if mode not in ("up", "down") and self.skip_fusable(a2, cin - c2, c2, cout, ho, wo, w[pre + "conv2.w"]):
+                # unet.py:214-218 `skip_connection(x) + h`: the 1x1 conv rides on conv2
+                if (pre + "conv2skip.b") not in w:
+                    w[pre + "conv2skip.b"] = (w[pre + "conv2.b"] + w[pre + "skip.b"]).contiguous()
+                out, _, _ = self.conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2skip.b"], ho, wo,
+                                       skip=(x, x2, cin - c2, c2, w[pre + "skip.w"]))
+                self.release(a2)
+                return out, ho, wo
+            skip = self.dense(x, B, hw, cin, cout, w[pre + "skip.w"], bias=w[pre + "skip.b"], src2=x2, c2=c2)
+        else:
+            assert x2 is None
+            skip = xs
+        out, _, _ = self.conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2.b"], ho, wo, residual=skip)
+        self.release(a2)
+        if skip is not x:
+            self.release(skip)
+        return out, ho, wo
+
+    def attnblock(self, pre, x, c, heads, h, wd):
+        """unet.py:254-310: q from the image, keys/values = [text (ctx) | image (T)]."""
+        net, w, B, dev, dense = self.net, self.w, self.B, self.dev, self.dense
+        ctx, xw = net.text_ctx, net.xf_width
+        T = h * wd
+        nk = ctx + T
+        a = self.get((B, T, c))
+        self.gn(x, None, w[pre + "norm.g"], w[pre + "norm.b"], 1e-5, False, a)
+        # keys / values = [text | image]: the text rows (encoder_kv of xf_out, unet.py:289-297) depend on the tokens alone, so
+        # they live in buffers of their own (not the arena: they must survive the step) and their two projections join the
+        # plan's text prefix; only the image rows are written per step
+        # Memory: these buffers are per (B, H, W) PLAN and are never arena-reused -- B * (text + image) * 3 c halves per
+        # AttentionBlock (base model at 16 rows: 22 blocks, 0.14 GB; up-sampler at 8 rows: 0.02 GB), plus a second captured
+        # graph (graph_main) per plan.  Whether the text rows are current is the CALLER's statement (text_epoch): nothing on the
+        # device re-checks tok_static, and forward_nhwc() without an epoch recomputes the prefix
+        vtb = torch.zeros((B, c, nk), dtype=f16, device=dev)
+        if ops.get_option("glide_qkv_merge") and T % 8 == 0:
+            # (round 6) q | k | v of the image tokens in ONE launch: q and k side by side in a [B, text + image, 2 c] buffer --
+            # rows [ctx, nk) written here (q | k), the k half of rows [0, ctx) by the text projection (its q half is never read)
+            # -- and V transposed into vtb; the attention kernel takes q and k as strided views of that buffer
+            qkb = torch.zeros((B, nk, 2 * c), dtype=f16, device=dev)
+            kbuf = qkb[:, :, c:]
+            self.kv_keep.append((kbuf, vtb, qkb))
+            self.gemm(a=a, w=w[pre + "qkv.w"], N=3 * c, B=B, H=T, W=1, c1=c, out=qkb[:, ctx:], out_ld=2 * c, bias=w[pre + "qkv.b"],
+                      out_bs=nk * 2 * c, out2=vtb[:, :, ctx:], out2_ld=nk, n_split=2 * c)
+            # AttentionBlock.norm has no activation (unet.py:267-272): the merged projection can apply it to its A fragments from
+            # the producer's column statistics (mdx_gemm_desc.gn_colstats on a dense launch, as the LDM planner's
+            # unet_gn_proj_fuse).  Decided when the statistics are wired; on success the GroupNorm op is dropped
+            if (ops.get_option("glide_gn_qkv_fuse") and T % 64 == 0 and c % 64 == 0 and c <= 2560
+                    and self.producer.get(x.data_ptr()) is not None):
+                self.gn_calls[-1]["proj"] = dict(desc=self.descs[-1], meta=len(self.meta) - 1)
+            q_ptr, q_bs, q_ld = qkb[:, ctx:].data_ptr(), nk * 2 * c, 2 * c
+            k_ptr, k_bs, k_ld = kbuf.data_ptr(), nk * 2 * c, 2 * c
+            q = None
+        else:
+            q = dense(a, B, T, c, c, w[pre + "q.w"], bias=w[pre + "q.b"])
+            kbuf = torch.zeros((B, nk, c), dtype=f16, device=dev)
+            self.kv_keep.append((kbuf, vtb))
+            dense(a, B, T, c, c, w[pre + "k.w"], bias=w[pre + "k.b"], out=kbuf[:, ctx:], out_ld=c, out_bs=nk * c)
+            dense(a, B, T, c, c, w[pre + "v.w"], bias=w[pre + "v.b"], out=vtb[:, :, ctx:], out_ld=nk,
+                  out_mode=ops.OUT_TRANSPOSED)
+            q_ptr, q_bs, q_ld = q.data_ptr(), T * c, c
+            k_ptr, k_bs, k_ld = kbuf.data_ptr(), nk * c, c
+        self.text_ops(True, late=True)
+        dense(self.xf_out, B, ctx, xw, c, w[pre + "ek.w"], bias=w[pre + "ek.b"], out=kbuf, out_ld=k_ld, out_bs=k_bs)
+        dense(self.xf_out, B, ctx, xw, c, w[pre + "ev.w"], bias=w[pre + "ev.b"], out=vtb, out_ld=nk,
+              out_mode=ops.OUT_TRANSPOSED)
+        self.text_ops(False)
+        o = a   # the normed input is dead after the projections
+        self.emit(lambda: ops.attention(q_ptr, k_ptr, vtb.data_ptr(), o.data_ptr(), B, heads, 64, T, nk, 64 ** -0.5,
+                                        q_bs, q_ld, k_bs, k_ld, c * nk, nk, T * c, c), "attention", 4 * B * heads * T * nk * 64)
+        out = dense(o, B, T, c, c, w[pre + "proj.w"], bias=w[pre + "proj.b"], residual=x)
+        if q is not None:
+            self.release(q)
+        self.release(a)
+        return out
+
+    def walk(self):
+        """The UNet (text2im_model.py:106-123)."""
+        P, net, w, B, dev = self.P, self.net, self.w, self.B, self.dev
+        h, wd = self.H, self.W
+        xin = self.get((B, h * wd, net.cin_pad))
+        if net.super_res:
+            P.low_static = torch.zeros((B, 3, net.low_size, net.low_size), dtype=f32, device=dev)
+            self.emit(lambda: ops.glide_superres_input(P.x_static, P.low_static, out=xin), "small")
+        else:
+            self.emit(lambda: ops.nchw_to_nhwc(P.x_static, net.cin_pad, out=xin), "small")
+        hs, cur = [], None
+
+        def layer_op(pre, layer, cur, skip, h, wd):
+            if layer[0] == "res":
+                return self.resblock(pre, cur, skip, layer[1], layer[2], layer[3], h, wd)
+            return self.attnblock(pre, cur, layer[1], layer[2], h, wd), h, wd
+        for i, blk in enumerate(net.input_blocks):
+            for j, layer in enumerate(blk):
+                pre = f"input_blocks.{i}.{j}."
+                if layer[0] == "conv":
+                    cur, h, wd = self.conv3(xin, net.cin_pad, layer[2], w[pre + "w"], w[pre + "b"], h, wd)
+                    self.release(xin)
+                    continue
+                new, h, wd = layer_op(pre, layer, cur, None, h, wd)
+                if not any(cur is s_[0] for s_ in hs):
+                    self.release(cur)
+                cur = new
+            hs.append((cur, h, wd))
+        for j, layer in enumerate(net.middle_block):
+            new, _, _ = layer_op(f"middle_block.{j}.", layer, cur, None, h, wd)
+            if not any(cur is s_[0] for s_ in hs):
+                self.release(cur)
+            cur = new
+        for i, blk in enumerate(net.output_blocks):
+            skip, sh, sw = hs.pop()
+            assert (sh, sw) == (h, wd)
+            for j, layer in enumerate(blk):
+                new, h, wd = layer_op(f"output_blocks.{i}.{j}.", layer, cur, skip if j == 0 else None, h, wd)
+                self.release(cur)
+                if j == 0:
+                    self.release(skip)
+                cur = new
+        ch0 = int(net.channel_mult[0] * net.model_channels)
+        a = self.get((B, h * wd, ch0))
+        self.gn(cur, None, w["out.g"], w["out.b"], 1e-5, True, a)
+        P.out_nhwc = torch.empty((B, h * wd, net.cout_pad), dtype=f16, device=dev)
+        self.gemm(a=a, w=w["out2.w"], N=net.cout_pad, B=B, H=h, W=wd, c1=ch0, out=P.out_nhwc, out_ld=net.cout_pad,
+                  bias=w["out2.b"], ksize=3)

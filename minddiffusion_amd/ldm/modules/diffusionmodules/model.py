@@ -14,7 +14,7 @@ import torch
 
 from ...._lib import MdxError
 from .... import ops
-from .openaimodel import _Arena
+from ....planner import PlanBuilder, capture_or_eager
 
 f16, f32 = torch.float16, torch.float32
 
@@ -23,15 +23,8 @@ def _run_plan(net, P):
     """Replay the plan as one hipGraph (captured on first use), or eagerly if capture is unavailable."""
     if net.use_graph and not P.graph_failed:
         if P.graph is None:
-            try:
-                for op in P.main:
-                    op()
-                torch.cuda.synchronize()
-                P.graph = ops.capture_graph(P.main)
-            except Exception as e:  # pragma: no cover - depends on the runtime
-                P.graph, P.graph_failed = None, True
-                import warnings
-                warnings.warn(f"hipGraph capture failed, running eagerly: {e}")
+            graphs = capture_or_eager([P.main])
+            P.graph, P.graph_failed = (None, True) if graphs is None else (graphs[0], False)
         if P.graph is not None:
             P.graph.replay()
             return
@@ -39,84 +32,49 @@ def _run_plan(net, P):
         op()
 
 
-class _PlanBuilder:
-    """Emits the C-ABI call list of a VAE net on arena buffers (shared by Decoder and Encoder)."""
+class _PlanBuilder(PlanBuilder):
+    """The VAE's blocks on the shared plan builder (Decoder and Encoder): GroupNorm eps 1e-6, no time embedding."""
 
     def __init__(self, net, P, B):
-        self.net, self.P, self.B = net, P, B
-        self.dev, self.w = net.device, net.w
-        self.A = _Arena(self.dev)
-        self.main, self.meta, self.descs = [], [], []
-        self.gn_need = 4
+        super().__init__(net.device, B)
+        self.P, self.w = P, net.w
 
-    def emit(self, fn, kind, flops=0, info=""):
-        self.main.append(fn)
-        self.meta.append({"kind": kind, "flops": int(flops), "launches": 1, "info": info})
-
-    def gemm(self, **kw):
-        d = ops.make_gemm_desc(**kw)
-        self.descs.append(d)
-        ks, up, st = kw.get("ksize", 1), kw.get("upsample", 0), kw.get("stride", 1)
-        m_rows = kw["B"] * kw["H"] * kw["W"] * (4 if up else 1) // (st * st)
-        kdim = ks * ks * kw["c1"]
-        self.emit(lambda d=d: ops.gemm_run(d), "gemm", 2 * m_rows * kw["N"] * kdim,
-                  f"M={m_rows} N={kw['N']} K={kdim} k{ks}s{st}u{up}")
-
-    def gn(self, x, g, b, silu, out):
-        Bq, HW, C = x.shape
-        self.gn_need = max(self.gn_need, ops.groupnorm_ws_floats(Bq, HW, C))
-        P = self.P
-        self.emit(lambda: ops.groupnorm(x, None, g, b, 1e-6, silu, ws=P.gn_ws, out=out), "groupnorm", 0, f"B={Bq} HW={HW} C={C}")
-
-    def conv3(self, src, cin, cout, wt, bias, h, wd, upsample=0, residual=None, n_store=None, stride=1, asym_pad=0):
-        ho, wo = (2 * h, 2 * wd) if upsample else (h // stride, wd // stride)
-        n_store = n_store or cout
-        out = self.A.get((self.B, ho * wo, n_store))
-        self.gemm(a=src, w=wt, N=n_store, B=self.B, H=h, W=wd, c1=cin, out=out, out_ld=n_store, bias=bias, residual=residual,
-                  residual_ld=n_store if residual is not None else 0, ksize=3, upsample=upsample, stride=stride,
-                  asym_pad=asym_pad)
-        return out
-
-    def conv1(self, src, tokens, cin, cout, wt, bias, residual=None, out=None, out_ld=None, out_mode=ops.OUT_ROWMAJOR):
-        if out is None:
-            out, out_ld = self.A.get((self.B, tokens, cout)), cout
-        self.gemm(a=src, w=wt, N=cout, B=self.B, H=tokens, W=1, c1=cin, out=out, out_ld=out_ld, bias=bias, residual=residual,
-                  residual_ld=cout if residual is not None else 0, out_mode=out_mode)
-        return out
+    def conv1(self, src, tokens, cin, cout, wt, bias, **kw):
+        return self.dense(src, self.B, tokens, cin, cout, wt, bias=bias, **kw)
 
     def resblock(self, pre, x, cin, cout, h, wd):          # ResnetBlock.construct model.py:128-148, temb = None
-        A, w, B = self.A, self.w, self.B
+        w, B = self.w, self.B
         hw = h * wd
-        a = A.get((B, hw, cin))
-        self.gn(x, w[pre + "norm1.g"], w[pre + "norm1.b"], True, a)
-        h1 = self.conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd)
-        A.release(a)
-        a2 = A.get((B, hw, cout))
-        self.gn(h1, w[pre + "norm2.g"], w[pre + "norm2.b"], True, a2)
-        A.release(h1)
+        a = self.get((B, hw, cin))
+        self.gn(x, None, w[pre + "norm1.g"], w[pre + "norm1.b"], 1e-6, True, a)
+        h1, _, _ = self.conv3(a, cin, cout, w[pre + "conv1.w"], w[pre + "conv1.b"], h, wd)
+        self.release(a)
+        a2 = self.get((B, hw, cout))
+        self.gn(h1, None, w[pre + "norm2.g"], w[pre + "norm2.b"], 1e-6, True, a2)
+        self.release(h1)
         skip = x if cin == cout else self.conv1(x, hw, cin, cout, w[pre + "nin.w"], w[pre + "nin.b"])
-        out = self.conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2.b"], h, wd, residual=skip)
-        A.release(a2)
+        out, _, _ = self.conv3(a2, cout, cout, w[pre + "conv2.w"], w[pre + "conv2.b"], h, wd, residual=skip)
+        self.release(a2)
         if skip is not x:
-            A.release(skip)
+            self.release(skip)
         return out
 
     def attnblock(self, pre, x, c, h, wd):                 # AttnBlock.construct model.py:182-206
-        A, w, B = self.A, self.w, self.B
+        w, B = self.w, self.B
         hw = h * wd
         if hw % 8:
             raise MdxError("VAE attention needs h*w % 8 == 0")
-        hn = A.get((B, hw, c))
-        self.gn(x, w[pre + "norm.g"], w[pre + "norm.b"], False, hn)
+        hn = self.get((B, hw, c))
+        self.gn(x, None, w[pre + "norm.g"], w[pre + "norm.b"], 1e-6, False, hn)
         q = self.conv1(hn, hw, c, c, w[pre + "q.w"], w[pre + "q.b"])
         k = self.conv1(hn, hw, c, c, w[pre + "k.w"], w[pre + "k.b"])
-        vt = A.get((B, c, hw))                         # V^T [b][c][hw]: the GEMM stores it transposed
+        vt = self.get((B, c, hw))                      # V^T [b][c][hw]: the GEMM stores it transposed
         self.conv1(hn, hw, c, c, w[pre + "v.w"], w[pre + "v.b"], out=vt, out_ld=hw, out_mode=ops.OUT_TRANSPOSED)
-        A.release(hn)
-        o = A.get((B, hw, c))
-        kp = A.get((((hw + 63) // 64) * ((c + 63) // 64) * 4096,))     # packed K   (rows = keys, K = c)
-        vp = A.get((((c + 63) // 64) * ((hw + 63) // 64) * 4096,))     # packed V^T (rows = c,    K = keys)
-        s = A.get((hw, hw))                            # scores of ONE image (the reference holds all B at once)
+        self.release(hn)
+        o = self.get((B, hw, c))
+        kp = self.get((((hw + 63) // 64) * ((c + 63) // 64) * 4096,))     # packed K   (rows = keys, K = c)
+        vp = self.get((((c + 63) // 64) * ((hw + 63) // 64) * 4096,))     # packed V^T (rows = c,    K = keys)
+        s = self.get((hw, hw))                         # scores of ONE image (the reference holds all B at once)
         scale = float(int(c) ** (-0.5))
         for b in range(B):
             self.emit(lambda b=b: ops.pack_b_operand(k[b], out=kp), "small")
@@ -124,21 +82,14 @@ class _PlanBuilder:
             self.emit(lambda: ops.softmax_rows(s, scale), "small")                                   # * c^-0.5, Softmax
             self.emit(lambda b=b: ops.pack_b_operand(vt[b], out=vp), "small")
             self.gemm(a=s, w=vp, N=c, B=1, H=hw, W=1, c1=hw, out=o[b], out_ld=c)                    # h_ = bmm(v, w_^T)
-        for t in (q, k, vt, kp, vp, s):
-            A.release(t)
+        self.release(q, k, vt, kp, vp, s)
         out = self.conv1(o, hw, c, c, w[pre + "proj_out.w"], w[pre + "proj_out.b"], residual=x)
-        A.release(o)
+        self.release(o)
         return out
 
     def finish(self):
-        P = self.P
-        need = max([ops.gemm_workspace_bytes(d) for d in self.descs] + [16])
-        P.gemm_ws = ops.new_gemm_workspace(need, self.dev)
-        for d in self.descs:
-            d.workspace, d.workspace_bytes = P.gemm_ws.data_ptr(), P.gemm_ws.numel() * 4
-        P.gn_ws = torch.empty(self.gn_need, dtype=f32, device=self.dev)
-        P.main, P.meta, P.descs, P.arena = self.main, self.meta, self.descs, self.A
-        P.activation_bytes = self.A.total
+        super().finish(self.P)
+        self.P.activation_bytes = self.A.total
 
 
 class Decoder:
@@ -273,18 +224,17 @@ class Decoder:
         dev, w = self.device, self.w
         P = Decoder._Plan()
         pb = _PlanBuilder(self, P, B)
-        A = pb.A
         P.z_static = torch.zeros((B, self.z_channels, H, W), dtype=f32, device=dev)
-        zin = A.get((B, H * W, self.zc_pad))
+        zin = pb.get((B, H * W, self.zc_pad))
         pb.emit(lambda: ops.nchw_to_nhwc(P.z_static, self.zc_pad, out=zin), "small")
         hcur = zin
         if "pq.w" in w:                                  # AutoencoderKL.post_quant_conv (1x1)
             hcur = pb.conv1(zin, H * W, self.zc_pad, self.zc_pad, w["pq.w"], w["pq.b"])
-            A.release(zin)
+            pb.release(zin)
         seq, first, last = self._structure()
         h, wd = H, W
-        nxt = pb.conv3(hcur, self.zc_pad, first, w["conv_in.w"], w["conv_in.b"], h, wd)
-        A.release(hcur)
+        nxt, _, _ = pb.conv3(hcur, self.zc_pad, first, w["conv_in.w"], w["conv_in.b"], h, wd)
+        pb.release(hcur)
         hcur = nxt
         for pre, kind, cin, cout in seq:
             if kind == "res":
@@ -292,15 +242,14 @@ class Decoder:
             elif kind == "attn":
                 nxt = pb.attnblock(pre, hcur, cin, h, wd)
             else:                                        # Upsample model.py:45-52: nearest x2 folded into the gather
-                nxt = pb.conv3(hcur, cin, cin, w[pre + "conv.w"], w[pre + "conv.b"], h, wd, upsample=1)
-                h, wd = 2 * h, 2 * wd
-            A.release(hcur)
+                nxt, h, wd = pb.conv3(hcur, cin, cin, w[pre + "conv.w"], w[pre + "conv.b"], h, wd, upsample=1)
+            pb.release(hcur)
             hcur = nxt
-        a = A.get((B, h * wd, last))
-        pb.gn(hcur, w["norm_out.g"], w["norm_out.b"], True, a)
-        A.release(hcur)
-        y = pb.conv3(a, last, self.out_ch, w["conv_out.w"], w["conv_out.b"], h, wd, n_store=self.out_pad)
-        A.release(a)
+        a = pb.get((B, h * wd, last))
+        pb.gn(hcur, None, w["norm_out.g"], w["norm_out.b"], 1e-6, True, a)
+        pb.release(hcur)
+        y, _, _ = pb.conv3(a, last, self.out_pad, w["conv_out.w"], w["conv_out.b"], h, wd)      # (out_ch padded to 8 columns)
+        pb.release(a)
         P.out_nchw = torch.empty((B, self.out_ch, h, wd), dtype=f32, device=dev)
         pb.emit(lambda: ops.nhwc_to_nchw(y, self.out_ch, h, wd, out=P.out_nchw), "small")
         pb.finish()
@@ -446,29 +395,27 @@ class Encoder:
         dev, w = self.device, self.w
         P = Decoder._Plan()
         pb = _PlanBuilder(self, P, B)
-        A = pb.A
         P.x_static = torch.zeros((B, self.in_channels, H, W), dtype=f32, device=dev)
-        xin = A.get((B, H * W, self.cin_pad))
+        xin = pb.get((B, H * W, self.cin_pad))
         pb.emit(lambda: ops.nchw_to_nhwc(P.x_static, self.cin_pad, out=xin), "small")
         seq, first, last = self._structure()
         h, wd = H, W
-        hcur = pb.conv3(xin, self.cin_pad, first, w["conv_in.w"], w["conv_in.b"], h, wd)
-        A.release(xin)
+        hcur, _, _ = pb.conv3(xin, self.cin_pad, first, w["conv_in.w"], w["conv_in.b"], h, wd)
+        pb.release(xin)
         for pre, kind, cin, cout in seq:
             if kind == "res":
                 nxt = pb.resblock(pre, hcur, cin, cout, h, wd)
             elif kind == "attn":
                 nxt = pb.attnblock(pre, hcur, cin, h, wd)
             else:                                        # Downsample model.py:70-75
-                nxt = pb.conv3(hcur, cin, cin, w[pre + "conv.w"], w[pre + "conv.b"], h, wd, stride=2, asym_pad=1)
-                h, wd = h // 2, wd // 2
-            A.release(hcur)
+                nxt, h, wd = pb.conv3(hcur, cin, cin, w[pre + "conv.w"], w[pre + "conv.b"], h, wd, stride=2, asym_pad=1)
+            pb.release(hcur)
             hcur = nxt
-        a = A.get((B, h * wd, last))
-        pb.gn(hcur, w["norm_out.g"], w["norm_out.b"], True, a)
-        A.release(hcur)
-        mom = pb.conv3(a, last, 2 * self.z_channels, w["conv_out.w"], w["conv_out.b"], h, wd, n_store=self.mom_pad)
-        A.release(a)
+        a = pb.get((B, h * wd, last))
+        pb.gn(hcur, None, w["norm_out.g"], w["norm_out.b"], 1e-6, True, a)
+        pb.release(hcur)
+        mom, _, _ = pb.conv3(a, last, self.mom_pad, w["conv_out.w"], w["conv_out.b"], h, wd)   # (2 z_channels padded to 8 columns)
+        pb.release(a)
         if "q.w" in w:                                   # AutoencoderKL.quant_conv (1x1) on the moments
             mom = pb.conv1(mom, h * wd, self.mom_pad, self.mom_pad, w["q.w"], w["q.b"])
         P.moments = mom                                  # NHWC fp16 [B, h*w, mom_pad] = [mean | logvar | pad]

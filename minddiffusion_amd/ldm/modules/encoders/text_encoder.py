@@ -16,7 +16,7 @@ import torch
 
 from ...._lib import MdxError
 from .... import ops
-from ..diffusionmodules.openaimodel import _Arena
+from ....planner import PlanBuilder, capture_or_eager
 
 f16, f32 = torch.float16, torch.float32
 
@@ -98,53 +98,37 @@ class TextEncoder:
         dev, w, wd, T, H = self.device, self.w, self.width, self.t_pad, self.heads
         dh = wd // H
         P = TextEncoder._Plan()
-        A = _Arena(dev)
-        main, descs = [], []
+        pb = PlanBuilder(dev, B)
         P.tokens = torch.zeros((B, T), dtype=torch.int32, device=dev)
         P.ones = torch.ones((B, T), dtype=torch.int32, device=dev)
         epi = ops.EPI_GELU if self.act == "gelu_tanh" else ops.EPI_QUICKGELU
 
-        def gemm(**kw):
-            d = ops.make_gemm_desc(**kw)
-            descs.append(d)
-            main.append(lambda d=d: ops.gemm_run(d))
+        def layernorm(src, g, b, eps, out):
+            pb.emit(lambda: ops.layernorm(src.view(B * T, wd), g, b, eps, out=out.view(B * T, wd)), "layernorm")
 
-        x = A.get((B, T, wd))
+        x = pb.get((B, T, wd))
         # gather(embedding_table, ids) + positional_embedding (:144-147); mask all ones, so `pad` is never read
-        main.append(lambda: ops.glide_text_embed(P.tokens, P.ones, w["emb"], w["pos"], w["pos"], out=x))
-        a = A.get((B, T, wd))
-        qk = A.get((B, T, 2 * wd))
-        vt = A.get((B, wd, T))
-        o = A.get((B, T, wd))
-        h = A.get((B, T, 4 * wd))
-        x2 = A.get((B, T, wd))
-        scale = float(dh) ** -0.5
+        pb.emit(lambda: ops.glide_text_embed(P.tokens, P.ones, w["emb"], w["pos"], w["pos"], out=x), "small")
+        a = pb.get((B, T, wd))
+        qk = pb.get((B, T, 2 * wd))
+        vt = pb.get((B, wd, T))
+        o = pb.get((B, T, wd))
+        h = pb.get((B, T, 4 * wd))
+        x2 = pb.get((B, T, wd))
         for i in range(self.layers):
             L = f"l{i}."
-            main.append(lambda x=x, L=L: ops.layernorm(x.view(B * T, wd), w[L + "ln_1.g"], w[L + "ln_1.b"], self.ln_eps,
-                                                       out=a.view(B * T, wd)))
-            gemm(a=a, w=w[L + "qk.w"], N=2 * wd, B=B, H=T, W=1, c1=wd, out=qk, out_ld=2 * wd, bias=w[L + "qk.b"])
-            gemm(a=a, w=w[L + "v.w"], N=wd, B=B, H=T, W=1, c1=wd, out=vt, out_ld=T, bias=w[L + "v.b"],
-                 out_mode=ops.OUT_TRANSPOSED)
-            main.append(lambda: ops.attention(qk.data_ptr(), qk.data_ptr() + wd * 2, vt.data_ptr(), o.data_ptr(), B, H, dh,
-                                              T, T, scale, T * 2 * wd, 2 * wd, T * 2 * wd, 2 * wd, wd * T, T, T * wd, wd,
-                                              causal=True))                                     # mask :136-139, :57-60
-            gemm(a=o, w=w[L + "out.w"], N=wd, B=B, H=T, W=1, c1=wd, out=x2, out_ld=wd, bias=w[L + "out.b"],
-                 residual=x, residual_ld=wd)                                                     # x + attn(ln_1(x)) :94
-            main.append(lambda x2=x2, L=L: ops.layernorm(x2.view(B * T, wd), w[L + "ln_2.g"], w[L + "ln_2.b"], self.ln_eps,
-                                                         out=a.view(B * T, wd)))
-            gemm(a=a, w=w[L + "fc.w"], N=4 * wd, B=B, H=T, W=1, c1=wd, out=h, out_ld=4 * wd, bias=w[L + "fc.b"],
-                 epilogue=epi)
-            gemm(a=h, w=w[L + "proj.w"], N=wd, B=B, H=T, W=1, c1=4 * wd, out=x, out_ld=wd, bias=w[L + "proj.b"],
-                 residual=x2, residual_ld=wd)                                                    # x + mlp(ln_2(x)) :95
+            layernorm(x, w[L + "ln_1.g"], w[L + "ln_1.b"], self.ln_eps, a)
+            pb.dense(a, B, T, wd, 2 * wd, w[L + "qk.w"], bias=w[L + "qk.b"], out=qk, out_ld=2 * wd)
+            pb.dense(a, B, T, wd, wd, w[L + "v.w"], bias=w[L + "v.b"], out=vt, out_ld=T, out_mode=ops.OUT_TRANSPOSED)
+            pb.attention(qk, vt, o, H, dh, causal=True)                                         # mask :136-139, :57-60
+            pb.dense(o, B, T, wd, wd, w[L + "out.w"], bias=w[L + "out.b"], residual=x, out=x2, out_ld=wd)   # x + attn(ln_1(x)) :94
+            layernorm(x2, w[L + "ln_2.g"], w[L + "ln_2.b"], self.ln_eps, a)
+            pb.dense(a, B, T, wd, 4 * wd, w[L + "fc.w"], bias=w[L + "fc.b"], epilogue=epi, out=h, out_ld=4 * wd)
+            pb.dense(h, B, T, 4 * wd, wd, w[L + "proj.w"], bias=w[L + "proj.b"], residual=x2, out=x, out_ld=wd)   # x + mlp(ln_2(x)) :95
         P.out = torch.empty((B, T, wd), dtype=f16, device=dev)
         # ln_final = nn.LayerNorm([width]): MindSpore's default epsilon is 1e-7 (:132)
-        main.append(lambda: ops.layernorm(x.view(B * T, wd), w["lnf.g"], w["lnf.b"], 1e-7, out=P.out.view(B * T, wd)))
-        need = max([ops.gemm_workspace_bytes(d) for d in descs] + [16])
-        P.gemm_ws = ops.new_gemm_workspace(need, dev)
-        for d in descs:
-            d.workspace, d.workspace_bytes = P.gemm_ws.data_ptr(), P.gemm_ws.numel() * 4
-        P.main, P.descs, P.arena = main, descs, A
+        layernorm(x, w["lnf.g"], w["lnf.b"], 1e-7, P.out)
+        pb.finish(P)
         self._plans[B] = P
         return P
 
@@ -161,15 +145,8 @@ class TextEncoder:
         P.tokens[:, : self.context_length].copy_(tok.to(device=self.device, dtype=torch.int32))
         if self.use_graph and not P.graph_failed:
             if P.graph is None:
-                try:
-                    for op in P.main:
-                        op()
-                    torch.cuda.synchronize()
-                    P.graph = ops.capture_graph(P.main)
-                except Exception as e:  # pragma: no cover - depends on the runtime
-                    P.graph, P.graph_failed = None, True
-                    import warnings
-                    warnings.warn(f"hipGraph capture failed, running eagerly: {e}")
+                graphs = capture_or_eager([P.main])
+                P.graph, P.graph_failed = (None, True) if graphs is None else (graphs[0], False)
             if P.graph is not None:
                 P.graph.replay()
                 return P.out[:, : self.context_length].clone()   # a fresh tensor: callers keep c and uc side by side

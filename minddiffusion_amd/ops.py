@@ -535,18 +535,6 @@ def gemm_query(desc):
     return tuple(int(v) for v in out)
 
 
-def account_gemm_launches(meta):
-    """Plan post-pass (after the shared workspace is patched into the descriptors): launches per GEMM op = the kernel
-    plus a split-K reduce launch unless the split is reduced in the kernel; the op's info string gets the real split."""
-    for m in meta:
-        d = m.get("desc")
-        if d is None:
-            continue
-        q = gemm_query(d)
-        m["launches"] = 2 if (q[2] > 1 and not q[6] and not d.defer_reduce) else 1
-        m["info"] = m["info"].split(" split=")[0] + f" split={q[2] if q[2] > 1 else 0}" + ("i" if q[6] else "")
-
-
 # First-use tuning (include/mdx.h mdx_gemm_tune): the user-side cache.  key = gemm_shape_key(desc) -> (tile_m, tile_n, splitk,
 # stages, us of the library's choice, us of the best form).  save_tune_cache / load_tune_cache keep it across processes.
 tune_cache = {}
@@ -802,146 +790,8 @@ def vae_gaussian_sample(moments, zc, noise, out):
     return out
 
 
-def wire_groupnorm_colstats(gn_calls, meta, batch, device, table):
-    """Plan-time post-pass shared by the UNet planners (run AFTER the split-K workspace is patched into the descriptors, so
-    that mdx_gemm_query sees the real split factors): every GroupNorm whose inputs are GEMM outputs and that would take the
-    two-launch path (>= ~1k pixels per sample) gets its statistics from its producers' epilogues
-    (mdx_gemm_desc.colstats_out) -- gn_stats and its read pass disappear.  gn_calls: dicts with x1, x2, prod = (desc of x1's
-    producer, desc of x2's producer), meta = index into `meta`; sets call["cs"] = (cs1, nrb1, cs2, nrb2).  `table` keeps the
-    statistics buffers alive (descriptor address -> tensor)."""
-    import math
-    fold_many = get_option("gn_colstats_fold") != 0
-    for c in gn_calls:
-        _, HW, C1 = c["x1"].shape
-        # fused SpatialTransformer head / GroupNorm inside the consuming conv: the statistics feed that launch (any block count)
-        is_head = c.get("head") is not None or c.get("conv") is not None or c.get("proj") is not None
-        C2 = 0 if c["x2"] is None else c["x2"].shape[2]
-        cpg = (C1 + C2) // 32
-        L = cpg // math.gcd(cpg, 8)           # chunk columns of the minimal whole-group column block
-        if not is_head and L <= 64 and HW * L * 16 <= (64 << 10):
-            meta[c["meta"]]["launches"] = 1   # the one-launch fused kernel (norm.hip groupnorm_impl)
-            continue
-
-        fresh = []      # producers wired by THIS GroupNorm (undone if its other source cannot supply statistics)
-
-        def stats_of(d, cx):
-            if isinstance(d, _lib.StTailDesc):      # fused SpatialTransformer tail: per-row-block column sums of its output
-                key = ctypes.addressof(d)
-                if key not in table:
-                    rows = d.tile_rows
-                    if d.C != cx or HW % rows or HW // rows > 128:
-                        return None
-                    buf = torch.zeros((batch * (HW // rows), cx, 2), dtype=f32, device=device)
-                    d.colstats_out = buf.data_ptr()
-                    table[key] = (buf, HW // rows)
-                    fresh.append((key, d))
-                return table[key]
-            if d is None or d.N != cx or d.out_ld != cx or d.defer_reduce:
-                return None
-            key = ctypes.addressof(d)
-            if key in table:
-                return table[key]
-            # The statistics epilogue is part of the launch VARIANT the tile table is keyed by: ask with the field already set
-            # (any non-null value), or the row blocks the query reports are those of a different tile / split choice than the
-            # launch will make (a 64-row split-K reduce writing into a buffer sized for 128-row tiles).
-            d.colstats_out = 8
-            # ... and with an AMPLE workspace: the planners size the shared workspace again after this pass (to the largest ideal need
-            # of any descriptor), so the launch will take the variant's ideal form -- with the workspace of the first sizing the query
-            # can report a fallback (e.g. an un-split 128-row tile where the tuned row splits five ways and its reduce kernel writes
-            # 64-row blocks: found by tools/shape_sweep.py --model glide at a 32-pixel base, round 5 -- the launch then refused
-            # the statistics buffer as too small)
-            keep_ws = d.workspace_bytes
-            d.workspace_bytes = 1 << 40
-            rows = gemm_query(d)[5]
-            d.workspace_bytes = keep_ws
-            if rows <= 0 or HW % rows or HW // rows > 4096:
-                d.colstats_out = 0
-                return None
-            buf = torch.zeros((batch * (HW // rows), cx, 2), dtype=f32, device=device)
-            d.colstats_out, d.colstats_cap = buf.data_ptr(), batch * (HW // rows)
-            d._cs_rows = rows       # (python-side) what the buffer was sized for: check_colstats_wiring() re-asks after the final sizing
-            if HW // rows > 64 and not is_head and fold_many:
-                # > 64 row blocks per sample (GLIDE's 128 x 128 / 256 x 256 levels: 512 HALO patches): folding them in EVERY
-                # gn_apply block cost more than the statistics pass it saved (profiles/r02_e_ab.txt); they are folded ONCE by
-                # a small launch in front of the GroupNorm instead (mdx_colstats_fold_f32)
-                table[key] = (FoldedColStats(buf, HW // rows, batch), HW // rows)
-            elif HW // rows > 64 and not is_head:
-                d.colstats_out = 0
-                return None
-            else:
-                table[key] = (buf, HW // rows)
-            fresh.append((key, d))
-            return table[key]
-        s1 = stats_of(c["prod"][0], C1)
-        if c.get("proj") is not None:
-            # GroupNorm (no activation) in front of a Dense / 1x1 conv: the consumer applies it to its A fragments when the
-            # producer can supply column statistics in <= 64 row blocks per sample and an M tile stays inside one sample;
-            # otherwise this call falls back to the GroupNorm launch it was planned with (handled below like any other)
-            pj = c.pop("proj")
-            dd = pj["desc"]
-            ok = False
-            if s1 is not None and not isinstance(s1[0], FoldedColStats) and int(s1[1]) <= 64:
-                keep = (dd.a, dd.gn_colstats, dd.gn_nrb, dd.gn_gamma, dd.gn_beta, dd.gn_eps, dd.gn_silu)
-                dd.a, dd.gn_colstats, dd.gn_nrb = c["x1"].data_ptr(), s1[0].data_ptr(), int(s1[1])
-                dd.gn_gamma, dd.gn_beta, dd.gn_eps, dd.gn_silu = c["g"].data_ptr(), c["b"].data_ptr(), float(c["eps"]), 0
-                ok = _lib.load().mdx_gemm_check(ctypes.byref(dd)) == 0 and HW % gemm_query(dd)[0] == 0
-                if not ok:
-                    dd.a, dd.gn_colstats, dd.gn_nrb, dd.gn_gamma, dd.gn_beta, dd.gn_eps, dd.gn_silu = keep
-            if ok:
-                dd._gn_src = (c["x1"], s1[0])       # (python-side: keeps the raw input and the statistics buffer alive)
-                meta[c["meta"]]["dead"] = True      # the planner drops the GroupNorm op
-                meta[pj["meta"]]["info"] += " +groupnorm(in)"
-                continue
-            for key, d in fresh:
-                table.pop(key, None)
-                d.colstats_out = 0
-                if hasattr(d, "colstats_cap"):
-                    d.colstats_cap = 0
-            fresh.clear()
-            is_head = False
-            L_ = cpg // math.gcd(cpg, 8)
-            if L_ <= 64 and HW * L_ * 16 <= (64 << 10):
-                meta[c["meta"]]["launches"] = 1
-                continue
-            s1 = stats_of(c["prod"][0], C1)
-        if is_head:
-            if s1 is not None and c.get("head") is not None:
-                c["head"].colstats, c["head"].nrb = s1[0].data_ptr(), int(s1[1])
-            elif s1 is not None:
-                c["conv"].gn_colstats, c["conv"].gn_nrb = s1[0].data_ptr(), int(s1[1])
-            continue
-        s2 = stats_of(c["prod"][1], C2) if C2 else (None, 0)
-        if s1 is None or s2 is None:
-            # one source cannot supply statistics: the GroupNorm takes the two-launch path, and a producer that was wired only
-            # for it must not keep paying for the statistics epilogue (nor resolve to that launch variant's tile-table row)
-            for key, d in fresh:
-                table.pop(key, None)
-                d.colstats_out = 0
-                if hasattr(d, "colstats_cap"):
-                    d.colstats_cap = 0
-            continue
-        c["cs"] = (s1[0], s1[1], s2[0], s2[1])
-        meta[c["meta"]]["launches"] = 1 + isinstance(s1[0], FoldedColStats) + isinstance(s2[0], FoldedColStats)
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # Row-local fused SpatialTransformer tail (include/mdx.h: mdx_st_tail_f16, csrc/stchain.hip)
-def check_colstats_wiring(descs):
-    """Called by the planners AFTER the shared split-K workspace has its final size: wire_groupnorm_colstats sized every statistics
-    buffer for the row blocks the launch reports under an AMPLE workspace (its ideal form); the launch takes that form only if
-    the final workspace really holds it.  A planner that kept the first-sized workspace would fail at its first launch with a
-    colstats_cap mismatch -- fail here instead, with the descriptor named."""
-    for d in descs:
-        rows = getattr(d, "_cs_rows", None)
-        if rows is None or not d.colstats_out:
-            continue
-        now = gemm_query(d)[5]
-        if now != rows:
-            raise _lib.MdxError(f"GroupNorm statistics wiring: the launch M={d.B * d.H * d.W} N={d.N} k{d.ksize} writes {now}-row "
-                                f"blocks under the final workspace ({d.workspace_bytes} bytes) but its statistics buffer was sized "
-                                f"for {rows}-row blocks: size the workspace from gemm_workspace_bytes() AFTER the wiring pass")
-
-
 def pack_frag_weight(w2d):
     """[N, K] nn.Dense weight -> MFMA-fragment-major pieces [N/32 column tiles][K/16 k-steps][64 lanes * 8 halves]:
     piece (ct, s)[lane] = W[32 ct + lane % 32][16 s + 8 (lane // 32) + 0..7] -- the first operand of
