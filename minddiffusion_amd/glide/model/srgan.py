@@ -21,6 +21,7 @@ import torch
 from ..._lib import MdxError
 from ... import ops
 from ...ldm.modules.diffusionmodules.model import _run_plan
+from ...loader import WeightLoader
 from ...planner import PlanBuilder
 
 f16, f32 = torch.float16, torch.float32
@@ -109,48 +110,32 @@ class Generator:
         return out
 
     # ------------------------------------------------------------------ weights
-    def _f32(self, a):
-        return torch.as_tensor(np.asarray(a, np.float64), dtype=f32).to(self.device).contiguous()
-
-    def _f16(self, a):
-        return torch.as_tensor(np.asarray(a, np.float64), dtype=f32).to(f16).to(self.device).contiguous()
-
-    def _conv3(self, wt):
-        return ops.pack_conv_weight(torch.as_tensor(np.asarray(wt, np.float64), dtype=f32).to(self.device))
-
     def load_state_dict(self, params, strict=True):
         """params: reference parameter name -> array (PReLU slopes as `.a` or `.w`).  BN folded, weights packed once."""
         params = self.normalize_keys(params)
         shapes = self.parameter_shapes()
-        for k, shp in shapes.items():
-            if k not in params:
-                if k.endswith(".a"):
-                    prelu_keys(k[:-2], params)           # raises with both spellings named
-                raise MdxError(f"SRGAN Generator: missing parameter {k}")
-            if tuple(np.shape(params[k])) != tuple(shp):
-                raise MdxError(f"SRGAN Generator: {k} has shape {tuple(np.shape(params[k]))}, expected {shp}")
-        if strict:
-            extra = sorted(k for k in params if k not in shapes)
-            if extra:
-                raise MdxError(f"SRGAN Generator: unexpected parameters {extra[:8]}")
-        g = params.__getitem__
-        w = {"in.w": self._f16(g("conv1.0.weight")), "in.b": self._f32(g("conv1.0.bias")), "in.a": self._f32(g("conv1.1.a"))}
+        for base in self._prelu_bases():
+            prelu_keys(base, params)                     # a missing slope raises with both spellings named
+        L = WeightLoader(params, self.device, "SRGAN Generator", error=MdxError, via_f32=True)
+        L.check(shapes, unexpected=strict)
+        w, g = L.w, L.src
+        w["in.w"], w["in.b"], w["in.a"] = L.raw("conv1.0.weight", f16), L.vec("conv1.0.bias"), L.vec("conv1.1.a")
         for i in range(TRUNK):
             p = f"trunk.{i}."
             for c, b in (("conv1", "bn1"), ("conv2", "bn2")):
                 wf, bf = fold_batchnorm(g(p + c + ".weight"), g(p + c + ".bias"), g(p + b + ".gamma"), g(p + b + ".beta"),
                                         g(p + b + ".moving_mean"), g(p + b + ".moving_variance"))
-                w[p + c + ".w"], w[p + c + ".b"] = self._conv3(wf), self._f32(bf)
-            w[p + "a"] = self._f32(g(p + "prelu.a"))
-        w["c2.w"], w["c2.b"], w["c2.a"] = self._conv3(g("conv2.0.weight")), self._f32(g("conv2.0.bias")), self._f32(g("conv2.1.a"))
+                w[p + c + ".w"], w[p + c + ".b"] = L.conv(wf), L.vec(bf)
+            w[p + "a"] = L.vec(p + "prelu.a")
+        w["c2.w"], w["c2.b"], w["c2.a"] = L.conv("conv2.0.weight"), L.vec("conv2.0.bias"), L.vec("conv2.1.a")
         rows = d2s_weight_rows(CH)
         for j in range(self.n_sub):
             p = f"subpixel_conv.{j}."
-            w[p + "w"] = self._conv3(np.asarray(g(p + "conv.weight"))[rows])
-            w[p + "b"] = self._f32(np.asarray(g(p + "conv.bias"))[rows])
-            w[p + "a"] = self._f32(g(p + "prelu.a"))
-        w["out.w"], w["out.b"] = self._f16(g("conv3.weight")), self._f32(g("conv3.bias"))
-        self.w = w
+            w[p + "w"] = L.conv(np.asarray(g(p + "conv.weight"))[rows])
+            w[p + "b"] = L.vec(np.asarray(g(p + "conv.bias"))[rows])
+            w[p + "a"] = L.vec(p + "prelu.a")
+        w["out.w"], w["out.b"] = L.raw("conv3.weight", f16), L.vec("conv3.bias")
+        self.w = L.finish(shapes)
         self._plans.clear()
 
     # ------------------------------------------------------------------ plan

@@ -20,12 +20,11 @@ names (`load_state_dict`).  Execution is planned once per (N, H, W) into a flat 
 """
 import math
 
-import numpy as np
 import torch
 
 from ... import ops
 from ..._lib import MdxError
-from ...weights import check_state_dict
+from ...loader import WeightLoader, named_layers
 from ...planner import PlanBuilder, capture_or_eager, round_up
 
 f16, f32 = torch.float16, torch.float32
@@ -96,21 +95,11 @@ class Text2ImUNet:
                 outb.append(layers)
         return inb, mid, outb
 
-    def _named_layers(self):
-        for i, blk in enumerate(self.input_blocks):
-            for j, layer in enumerate(blk):
-                yield f"input_blocks.{i}.{j}.", layer
-        for j, layer in enumerate(self.middle_block):
-            yield f"middle_block.{j}.", layer
-        for i, blk in enumerate(self.output_blocks):
-            for j, layer in enumerate(blk):
-                yield f"output_blocks.{i}.{j}.", layer
-
     def parameter_shapes(self):
         mc, ted, xw = self.model_channels, self.time_embed_dim, self.xf_width
         s = {"time_embed.0.weight": (ted, mc), "time_embed.0.bias": (ted,),
              "time_embed.2.weight": (ted, ted), "time_embed.2.bias": (ted,)}
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             if layer[0] == "conv":
                 s[pre + "conv.weight"] = (layer[2], layer[1], 3, 3)
                 s[pre + "conv.bias"] = (layer[2],)
@@ -160,109 +149,81 @@ class Text2ImUNet:
         return s
 
     # ------------------------------------------------------------------ weights
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _conv(self, wt, cin_pad=None, cout_pad=None):
-        return ops.pack_conv_weight(self._dev(wt, f32), cin_pad, cout_pad)
-
-    def _dense(self, wt):
-        return ops.pack_gemm_weight(self._dev(wt, f16))
-
     def load_state_dict(self, params, strict=True):
         shapes = self.parameter_shapes()
-        check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True,
-                         f"{type(self).__name__}.load_state_dict")
-        P, w = params, {}
-        ted = self.time_embed_dim
-        w["te0.w"] = self._dev(P["time_embed.0.weight"], f16)
-        w["te0.b"] = self._dev(P["time_embed.0.bias"], f32)
+        L = WeightLoader(params, self.device, f"{type(self).__name__}.load_state_dict")
+        L.check(shapes, unexpected=strict)
+        w = L.w
+        w["te0.w"], w["te0.b"] = L.raw("time_embed.0.weight", f16), L.vec("time_embed.0.bias")
         # emb = time_embed.2(e1) + transformer_proj(xf_out[:, -1])  (text2im_model.py:102-105) as ONE small GEMV
         # over the concatenated input [e1 | last token]
-        w["te2proj.w"] = torch.cat([self._dev(P["time_embed.2.weight"], f16),
-                                    self._dev(P["transformer_proj.weight"], f16)], 1).contiguous()
-        w["te2proj.b"] = (self._dev(P["time_embed.2.bias"], f32) + self._dev(P["transformer_proj.bias"], f32)).contiguous()
+        w["te2proj.w"] = torch.cat([L.raw("time_embed.2.weight", f16), L.raw("transformer_proj.weight", f16)], 1).contiguous()
+        w["te2proj.b"] = (L.vec("time_embed.2.bias") + L.vec("transformer_proj.bias")).contiguous()
         emb_w, emb_b, self._emb_off, off = [], [], {}, 0
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             if layer[0] == "conv":
-                w[pre + "w"] = self._conv(P[pre + "conv.weight"], cin_pad=self.cin_pad)
-                w[pre + "b"] = self._dev(P[pre + "conv.bias"], f32)
+                w[pre + "w"], w[pre + "b"] = L.conv(pre + "conv.weight", cin_pad=self.cin_pad), L.vec(pre + "conv.bias")
             elif layer[0] == "res":
                 cin, cout = layer[1], layer[2]
-                w[pre + "n1.g"] = self._dev(P[pre + "in_layers_0.gamma"], f32)
-                w[pre + "n1.b"] = self._dev(P[pre + "in_layers_0.beta"], f32)
-                w[pre + "n2.g"] = self._dev(P[pre + "out_layers_0.gamma"], f32)
-                w[pre + "n2.b"] = self._dev(P[pre + "out_layers_0.beta"], f32)
-                w[pre + "conv1.w"] = self._conv(P[pre + "in_layers_2.conv.weight"])
-                w[pre + "conv1.b"] = self._dev(P[pre + "in_layers_2.conv.bias"], f32)
+                L.norm(pre + "n1", pre + "in_layers_0")
+                L.norm(pre + "n2", pre + "out_layers_0")
+                w[pre + "conv1.w"], w[pre + "conv1.b"] = L.conv(pre + "in_layers_2.conv.weight"), L.vec(pre + "in_layers_2.conv.bias")
                 if len(layer) > 3 and layer[3] == "up" and cin % 64 == 0 and cout % 64 == 0 and ops.get_option("unet_subpixel_upsample"):
                     # the up-sampling ResBlock's conv1 follows a nearest-2x (unet.py:178-218): sub-pixel weights (mdx_gemm_desc.w_sub)
-                    w[pre + "conv1.wsub"] = ops.pack_subpixel_conv_weight(self._dev(P[pre + "in_layers_2.conv.weight"], f32))
-                w[pre + "conv2.w"] = self._conv(P[pre + "out_layers_3.conv.weight"])
-                w[pre + "conv2.b"] = self._dev(P[pre + "out_layers_3.conv.bias"], f32)
+                    w[pre + "conv1.wsub"] = ops.pack_subpixel_conv_weight(L.raw(pre + "in_layers_2.conv.weight", f32))
+                w[pre + "conv2.w"], w[pre + "conv2.b"] = L.conv(pre + "out_layers_3.conv.weight"), L.vec(pre + "out_layers_3.conv.bias")
                 if cin != cout:
-                    w[pre + "skip.w"] = self._conv(P[pre + "skip_connection.conv.weight"])
-                    w[pre + "skip.b"] = self._dev(P[pre + "skip_connection.conv.bias"], f32)
-                emb_w.append(self._dev(P[pre + "emb_layers.1.weight"], f16))
-                emb_b.append(self._dev(P[pre + "emb_layers.1.bias"], f32))
+                    w[pre + "skip.w"], w[pre + "skip.b"] = L.conv(pre + "skip_connection.conv.weight"), L.vec(pre + "skip_connection.conv.bias")
+                emb_w.append(L.raw(pre + "emb_layers.1.weight", f16))
+                emb_b.append(L.vec(pre + "emb_layers.1.bias"))
                 self._emb_off[pre] = off
                 off += 2 * cout
             else:
                 c, heads = layer[1], layer[2]
-                w[pre + "norm.g"] = self._dev(P[pre + "norm.gamma"], f32)
-                w[pre + "norm.b"] = self._dev(P[pre + "norm.beta"], f32)
+                L.norm(pre + "norm", pre + "norm")
                 # legacy order (unet.py:293-295): rows of head h are [q(64) | k(64) | v(64)]
-                qkv = self._dev(P[pre + "qkv.conv.weight"], f16).reshape(heads, 3, 64, c)
-                qb = self._dev(P[pre + "qkv.conv.bias"], f32).reshape(heads, 3, 64)
+                qkv = L.raw(pre + "qkv.conv.weight", f16).reshape(heads, 3, 64, c)
+                qb = L.vec(pre + "qkv.conv.bias").reshape(heads, 3, 64)
                 for idx, nm in enumerate("qkv"):
-                    w[pre + nm + ".w"] = self._dense(qkv[:, idx].reshape(c, c))
+                    w[pre + nm + ".w"] = L.dense(qkv[:, idx].reshape(c, c))
                     w[pre + nm + ".b"] = qb[:, idx].reshape(c).contiguous()
                 # (round 6) one launch for the three image-token projections: rows [q | k | v] (mdx_gemm_desc.n_split = 2 c: q | k
                 # row-major, V transposed)
-                w[pre + "qkv.w"] = self._dense(torch.cat([qkv[:, 0].reshape(c, c), qkv[:, 1].reshape(c, c), qkv[:, 2].reshape(c, c)], 0))
+                w[pre + "qkv.w"] = L.dense(torch.cat([qkv[:, 0].reshape(c, c), qkv[:, 1].reshape(c, c), qkv[:, 2].reshape(c, c)], 0))
                 w[pre + "qkv.b"] = torch.cat([qb[:, 0].reshape(c), qb[:, 1].reshape(c), qb[:, 2].reshape(c)], 0).contiguous()
-                ekv = self._dev(P[pre + "encoder_kv.conv.weight"], f16).reshape(heads, 2, 64, self.xf_width)
-                eb = self._dev(P[pre + "encoder_kv.conv.bias"], f32).reshape(heads, 2, 64)
+                ekv = L.raw(pre + "encoder_kv.conv.weight", f16).reshape(heads, 2, 64, self.xf_width)
+                eb = L.vec(pre + "encoder_kv.conv.bias").reshape(heads, 2, 64)
                 for idx, nm in enumerate(("ek", "ev")):
-                    w[pre + nm + ".w"] = self._dense(ekv[:, idx].reshape(c, self.xf_width))
+                    w[pre + nm + ".w"] = L.dense(ekv[:, idx].reshape(c, self.xf_width))
                     w[pre + nm + ".b"] = eb[:, idx].reshape(c).contiguous()
-                w[pre + "proj.w"] = self._dense(self._dev(P[pre + "proj_out.conv.weight"], f16).reshape(c, c))
-                w[pre + "proj.b"] = self._dev(P[pre + "proj_out.conv.bias"], f32)
+                w[pre + "proj.w"] = L.dense(L.raw(pre + "proj_out.conv.weight", f16).reshape(c, c))
+                w[pre + "proj.b"] = L.vec(pre + "proj_out.conv.bias")
         w["emb.w"] = torch.cat(emb_w, 0).contiguous()
         w["emb.b"] = torch.cat(emb_b, 0).contiguous()
         self._emb_total = off
-        w["out.g"] = self._dev(P["out.0.gamma"], f32)
-        w["out.b"] = self._dev(P["out.0.beta"], f32)
-        w["out2.w"] = self._conv(P["out2.conv.weight"], cout_pad=self.cout_pad)
-        ob = torch.zeros(self.cout_pad, dtype=f32, device=self.device)
-        ob[: self.out_channels] = self._dev(P["out2.conv.bias"], f32)
-        w["out2.b"] = ob
+        w["out.g"], w["out.b"] = L.vec("out.0.gamma"), L.vec("out.0.beta")
+        w["out2.w"] = L.conv("out2.conv.weight", cout_pad=self.cout_pad)
+        w["out2.b"] = L.vec("out2.conv.bias", pad=self.cout_pad)
         xw, xh = self.xf_width, self.xf_heads
         for l in range(self.xf_layers):
             t = f"transformer.resblocks.{l}."
             for n in ("ln_1", "ln_2"):
-                w[t + n + ".g"] = self._dev(P[t + n + ".gamma"], f32)
-                w[t + n + ".b"] = self._dev(P[t + n + ".beta"], f32)
+                L.norm(t + n, t + n)
             # xf.py:79-81: qkv.view(b, ctx, heads, 3*64) then split -> rows of head h are [q | k | v]
-            cq = self._dev(P[t + "attn.c_qkv.weight"], f16).reshape(xh, 3, 64, xw)
-            cb = self._dev(P[t + "attn.c_qkv.bias"], f32).reshape(xh, 3, 64)
-            w[t + "qk.w"] = self._dense(torch.cat([cq[:, 0].reshape(xw, xw), cq[:, 1].reshape(xw, xw)], 0))
+            cq = L.raw(t + "attn.c_qkv.weight", f16).reshape(xh, 3, 64, xw)
+            cb = L.vec(t + "attn.c_qkv.bias").reshape(xh, 3, 64)
+            w[t + "qk.w"] = L.dense(torch.cat([cq[:, 0].reshape(xw, xw), cq[:, 1].reshape(xw, xw)], 0))
             w[t + "qk.b"] = torch.cat([cb[:, 0].reshape(xw), cb[:, 1].reshape(xw)], 0).contiguous()
-            w[t + "v.w"] = self._dense(cq[:, 2].reshape(xw, xw))
+            w[t + "v.w"] = L.dense(cq[:, 2].reshape(xw, xw))
             w[t + "v.b"] = cb[:, 2].reshape(xw).contiguous()
-            w[t + "proj.w"] = self._dense(P[t + "attn.c_proj.weight"])
-            w[t + "proj.b"] = self._dev(P[t + "attn.c_proj.bias"], f32)
-            w[t + "fc.w"] = self._dense(P[t + "mlp.c_fc.weight"])
-            w[t + "fc.b"] = self._dev(P[t + "mlp.c_fc.bias"], f32)
-            w[t + "fc2.w"] = self._dense(P[t + "mlp.c_proj.weight"])
-            w[t + "fc2.b"] = self._dev(P[t + "mlp.c_proj.bias"], f32)
-        w["final_ln.g"] = self._dev(P["final_ln.gamma"], f32)
-        w["final_ln.b"] = self._dev(P["final_ln.beta"], f32)
-        w["tok"] = self._dev(P["token_embedding.embedding_table"], f16)
-        w["pos"] = self._dev(P["positional_embedding"], f16)
-        w["pad"] = self._dev(P["padding_embedding"], f16)
-        self.w = w
+            w[t + "proj.w"], w[t + "proj.b"] = L.dense(t + "attn.c_proj.weight"), L.vec(t + "attn.c_proj.bias")
+            w[t + "fc.w"], w[t + "fc.b"] = L.dense(t + "mlp.c_fc.weight"), L.vec(t + "mlp.c_fc.bias")
+            w[t + "fc2.w"], w[t + "fc2.b"] = L.dense(t + "mlp.c_proj.weight"), L.vec(t + "mlp.c_proj.bias")
+        L.norm("final_ln", "final_ln")
+        w["tok"] = L.raw("token_embedding.embedding_table", f16)
+        w["pos"] = L.raw("positional_embedding", f16)
+        w["pad"] = L.raw("padding_embedding", f16)
+        self.w = L.finish(shapes)
         self._plans = {}
         return self
 
@@ -375,7 +336,7 @@ class Text2ImUNet:
         pass
 
     def _attn_layers(self):
-        return [(pre, layer[1]) for pre, layer in self._named_layers() if layer[0] == "attn"]
+        return [(pre, layer[1]) for pre, layer in named_layers(self) if layer[0] == "attn"]
 
     def _text_plan(self, R):
         """Text transformer + every AttentionBlock's encoder_kv projection on R prompt rows: static token / mask inputs, an op

@@ -9,11 +9,11 @@ HALO kernel, the nearest-2x of Upsample folded into the next conv's gather), Gro
 mdx_groupnorm_f16.  AttnBlock has ONE head of d = C = 512: like the reference it materialises the [hw, hw] scores,
 as two plain GEMMs (K and V^T re-laid as packed B operands, mdx_pack_b_operand_f16) around mdx_softmax_rows_f16.
 """
-import numpy as np
 import torch
 
 from ...._lib import MdxError
 from .... import ops
+from ....loader import WeightLoader
 from ....planner import PlanBuilder, capture_or_eager
 
 f16, f32 = torch.float16, torch.float32
@@ -92,6 +92,54 @@ class _PlanBuilder(PlanBuilder):
         self.P.activation_bytes = self.A.total
 
 
+def _block_shapes(s, seq, prefix):
+    """Reference names and shapes of the ResnetBlock / AttnBlock / resampling-conv sequence `seq` into `s`."""
+    for pre, kind, cin, cout in seq:
+        p = prefix + pre
+        if kind == "res":
+            s[p + "norm1.gamma"] = (cin,); s[p + "norm1.beta"] = (cin,)
+            s[p + "conv1.weight"] = (cout, cin, 3, 3); s[p + "conv1.bias"] = (cout,)
+            s[p + "norm2.gamma"] = (cout,); s[p + "norm2.beta"] = (cout,)
+            s[p + "conv2.weight"] = (cout, cout, 3, 3); s[p + "conv2.bias"] = (cout,)
+            if cin != cout:
+                s[p + "nin_shortcut.weight"] = (cout, cin, 1, 1); s[p + "nin_shortcut.bias"] = (cout,)
+        elif kind == "attn":
+            s[p + "norm.gamma"] = (cin,); s[p + "norm.beta"] = (cin,)
+            for n in ("q", "k", "v", "proj_out"):
+                s[p + n + ".weight"] = (cin, cin, 1, 1); s[p + n + ".bias"] = (cin,)
+        else:
+            s[p + "conv.weight"] = (cin, cin, 3, 3); s[p + "conv.bias"] = (cin,)
+
+
+def _loader(net, params, prefix):
+    """Every parameter of a VAE half is needed to run, so a missing key raises whatever `strict` says; keys the half does not own
+    are never reported (the dict is the whole autoencoder's)."""
+    L = WeightLoader(params, net.device, f"{type(net).__name__}.load_state_dict", error=MdxError, prefix=prefix)
+    L.check(net.parameter_shapes(prefix), unexpected=False)
+    return L
+
+
+def _load_conv(L, dst, key, cin_pad=None, cout_pad=None):
+    L.w[dst + ".w"], L.w[dst + ".b"] = L.conv(key + ".weight", cin_pad, cout_pad), L.vec(key + ".bias", cout_pad)
+
+
+def _load_blocks(L, seq):
+    for pre, kind, cin, cout in seq:
+        if kind == "res":
+            for n in ("norm1", "norm2"):
+                L.norm(pre + n, pre + n)
+            for n in ("conv1", "conv2"):
+                _load_conv(L, pre + n, pre + n)
+            if cin != cout:
+                _load_conv(L, pre + "nin", pre + "nin_shortcut")
+        elif kind == "attn":
+            L.norm(pre + "norm", pre + "norm")
+            for n in ("q", "k", "v", "proj_out"):
+                _load_conv(L, pre + n, pre + n)
+        else:
+            _load_conv(L, pre + "conv", pre + "conv")
+
+
 class Decoder:
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False,
@@ -133,81 +181,26 @@ class Decoder:
     def parameter_shapes(self, prefix=""):
         seq, first, last = self._structure()
         s = {prefix + "conv_in.weight": (first, self.z_channels, 3, 3), prefix + "conv_in.bias": (first,)}
-        for pre, kind, cin, cout in seq:
-            p = prefix + pre
-            if kind == "res":
-                s[p + "norm1.gamma"] = (cin,); s[p + "norm1.beta"] = (cin,)
-                s[p + "conv1.weight"] = (cout, cin, 3, 3); s[p + "conv1.bias"] = (cout,)
-                s[p + "norm2.gamma"] = (cout,); s[p + "norm2.beta"] = (cout,)
-                s[p + "conv2.weight"] = (cout, cout, 3, 3); s[p + "conv2.bias"] = (cout,)
-                if cin != cout:
-                    s[p + "nin_shortcut.weight"] = (cout, cin, 1, 1); s[p + "nin_shortcut.bias"] = (cout,)
-            elif kind == "attn":
-                s[p + "norm.gamma"] = (cin,); s[p + "norm.beta"] = (cin,)
-                for n in ("q", "k", "v", "proj_out"):
-                    s[p + n + ".weight"] = (cin, cin, 1, 1); s[p + n + ".bias"] = (cin,)
-            else:
-                s[p + "conv.weight"] = (cin, cin, 3, 3); s[p + "conv.bias"] = (cin,)
+        _block_shapes(s, seq, prefix)
         s[prefix + "norm_out.gamma"] = (last,); s[prefix + "norm_out.beta"] = (last,)
         s[prefix + "conv_out.weight"] = (self.out_ch, last, 3, 3); s[prefix + "conv_out.bias"] = (self.out_ch,)
         return s
 
     # ------------------------------------------------------------------ weights
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _vec(self, v, n=None):
-        v = self._dev(v, f32)
-        if n is None or v.numel() == n:
-            return v
-        out = torch.zeros(n, dtype=f32, device=self.device)
-        out[: v.numel()] = v
-        return out
-
-    def _conv_w(self, wt, cin_pad=None, cout_pad=None):
-        wt = wt if isinstance(wt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wt))
-        return ops.pack_conv_weight(wt.to(self.device), cin_pad, cout_pad)
-
     def load_state_dict(self, params, prefix="", post_quant=None, strict=True):
         """params: reference parameter name (after `prefix`, e.g. 'decoder.') -> array.  `post_quant` = (weight
-        [zc, embed, 1, 1], bias) of AutoencoderKL.post_quant_conv, which runs in front of conv_in (autoencoder.py:66)."""
-        shapes = self.parameter_shapes(prefix)
-        missing = [k for k in shapes if k not in params]
-        if missing and strict:
-            raise MdxError(f"Decoder.load_state_dict: missing {len(missing)} parameters, e.g. {missing[:3]}")
-        for k, shp in shapes.items():
-            if k in params and tuple(np.shape(params[k])) != tuple(shp):
-                raise MdxError(f"Decoder.load_state_dict: {k} has shape {tuple(np.shape(params[k]))}, expected {shp}")
-        g = lambda k: params[prefix + k]
-        w = {}
+        [zc, embed, 1, 1], bias) of AutoencoderKL.post_quant_conv, which runs in front of conv_in (autoencoder.py:66).  A missing
+        key raises MdxError with or without `strict` (see _loader)."""
+        L = _loader(self, params, prefix)
+        w = L.w
         seq, first, last = self._structure()
         if post_quant is not None:
-            pw, pb = post_quant
-            pw = pw if isinstance(pw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pw))
-            w["pq.w"] = ops.pack_conv_weight(pw.to(self.device), self.zc_pad, self.zc_pad)
-            w["pq.b"] = self._vec(pb, self.zc_pad)
-        w["conv_in.w"] = self._conv_w(g("conv_in.weight"), cin_pad=self.zc_pad)
-        w["conv_in.b"] = self._vec(g("conv_in.bias"))
-        for pre, kind, cin, cout in seq:
-            if kind == "res":
-                for n in ("norm1", "norm2"):
-                    w[pre + n + ".g"], w[pre + n + ".b"] = self._vec(g(pre + n + ".gamma")), self._vec(g(pre + n + ".beta"))
-                for n in ("conv1", "conv2"):
-                    w[pre + n + ".w"], w[pre + n + ".b"] = self._conv_w(g(pre + n + ".weight")), self._vec(g(pre + n + ".bias"))
-                if cin != cout:
-                    w[pre + "nin.w"] = self._conv_w(g(pre + "nin_shortcut.weight"))
-                    w[pre + "nin.b"] = self._vec(g(pre + "nin_shortcut.bias"))
-            elif kind == "attn":
-                w[pre + "norm.g"], w[pre + "norm.b"] = self._vec(g(pre + "norm.gamma")), self._vec(g(pre + "norm.beta"))
-                for n in ("q", "k", "v", "proj_out"):
-                    w[pre + n + ".w"], w[pre + n + ".b"] = self._conv_w(g(pre + n + ".weight")), self._vec(g(pre + n + ".bias"))
-            else:
-                w[pre + "conv.w"], w[pre + "conv.b"] = self._conv_w(g(pre + "conv.weight")), self._vec(g(pre + "conv.bias"))
-        w["norm_out.g"], w["norm_out.b"] = self._vec(g("norm_out.gamma")), self._vec(g("norm_out.beta"))
-        w["conv_out.w"] = self._conv_w(g("conv_out.weight"), cout_pad=self.out_pad)
-        w["conv_out.b"] = self._vec(g("conv_out.bias"), self.out_pad)
-        self.w = w
+            w["pq.w"], w["pq.b"] = L.conv(post_quant[0], self.zc_pad, self.zc_pad), L.vec(post_quant[1], self.zc_pad)
+        _load_conv(L, "conv_in", "conv_in", cin_pad=self.zc_pad)
+        _load_blocks(L, seq)
+        L.norm("norm_out", "norm_out")
+        _load_conv(L, "conv_out", "conv_out", cout_pad=self.out_pad)
+        self.w = L.finish(self.parameter_shapes(prefix))
         self._plans.clear()
 
     # ------------------------------------------------------------------ plan
@@ -297,8 +290,6 @@ class Encoder:
         self.w = None
         self._plans = {}
 
-    _dev, _vec, _conv_w = Decoder._dev, Decoder._vec, Decoder._conv_w
-
     def _structure(self):
         nres = len(self.ch_mult)
         in_mult = (1,) + self.ch_mult
@@ -322,63 +313,23 @@ class Encoder:
     def parameter_shapes(self, prefix=""):
         seq, first, last = self._structure()
         s = {prefix + "conv_in.weight": (first, self.in_channels, 3, 3), prefix + "conv_in.bias": (first,)}
-        for pre, kind, cin, cout in seq:
-            p = prefix + pre
-            if kind == "res":
-                s[p + "norm1.gamma"] = (cin,); s[p + "norm1.beta"] = (cin,)
-                s[p + "conv1.weight"] = (cout, cin, 3, 3); s[p + "conv1.bias"] = (cout,)
-                s[p + "norm2.gamma"] = (cout,); s[p + "norm2.beta"] = (cout,)
-                s[p + "conv2.weight"] = (cout, cout, 3, 3); s[p + "conv2.bias"] = (cout,)
-                if cin != cout:
-                    s[p + "nin_shortcut.weight"] = (cout, cin, 1, 1); s[p + "nin_shortcut.bias"] = (cout,)
-            elif kind == "attn":
-                s[p + "norm.gamma"] = (cin,); s[p + "norm.beta"] = (cin,)
-                for n in ("q", "k", "v", "proj_out"):
-                    s[p + n + ".weight"] = (cin, cin, 1, 1); s[p + n + ".bias"] = (cin,)
-            else:
-                s[p + "conv.weight"] = (cin, cin, 3, 3); s[p + "conv.bias"] = (cin,)
+        _block_shapes(s, seq, prefix)
         s[prefix + "norm_out.gamma"] = (last,); s[prefix + "norm_out.beta"] = (last,)
         s[prefix + "conv_out.weight"] = (2 * self.z_channels, last, 3, 3); s[prefix + "conv_out.bias"] = (2 * self.z_channels,)
         return s
 
     def load_state_dict(self, params, prefix="", quant=None, strict=True):
         """`quant` = (weight [2*embed, 2*zc, 1, 1], bias) of AutoencoderKL.quant_conv, applied after conv_out (autoencoder.py:72)."""
-        shapes = self.parameter_shapes(prefix)
-        missing = [k for k in shapes if k not in params]
-        if missing and strict:
-            raise MdxError(f"Encoder.load_state_dict: missing {len(missing)} parameters, e.g. {missing[:3]}")
-        for k, shp in shapes.items():
-            if k in params and tuple(np.shape(params[k])) != tuple(shp):
-                raise MdxError(f"Encoder.load_state_dict: {k} has shape {tuple(np.shape(params[k]))}, expected {shp}")
-        g = lambda k: params[prefix + k]
-        w = {}
+        L = _loader(self, params, prefix)
+        w = L.w
         seq, first, last = self._structure()
-        w["conv_in.w"] = self._conv_w(g("conv_in.weight"), cin_pad=self.cin_pad)
-        w["conv_in.b"] = self._vec(g("conv_in.bias"))
-        for pre, kind, cin, cout in seq:
-            if kind == "res":
-                for n in ("norm1", "norm2"):
-                    w[pre + n + ".g"], w[pre + n + ".b"] = self._vec(g(pre + n + ".gamma")), self._vec(g(pre + n + ".beta"))
-                for n in ("conv1", "conv2"):
-                    w[pre + n + ".w"], w[pre + n + ".b"] = self._conv_w(g(pre + n + ".weight")), self._vec(g(pre + n + ".bias"))
-                if cin != cout:
-                    w[pre + "nin.w"] = self._conv_w(g(pre + "nin_shortcut.weight"))
-                    w[pre + "nin.b"] = self._vec(g(pre + "nin_shortcut.bias"))
-            elif kind == "attn":
-                w[pre + "norm.g"], w[pre + "norm.b"] = self._vec(g(pre + "norm.gamma")), self._vec(g(pre + "norm.beta"))
-                for n in ("q", "k", "v", "proj_out"):
-                    w[pre + n + ".w"], w[pre + n + ".b"] = self._conv_w(g(pre + n + ".weight")), self._vec(g(pre + n + ".bias"))
-            else:
-                w[pre + "conv.w"], w[pre + "conv.b"] = self._conv_w(g(pre + "conv.weight")), self._vec(g(pre + "conv.bias"))
-        w["norm_out.g"], w["norm_out.b"] = self._vec(g("norm_out.gamma")), self._vec(g("norm_out.beta"))
-        w["conv_out.w"] = self._conv_w(g("conv_out.weight"), cout_pad=self.mom_pad)
-        w["conv_out.b"] = self._vec(g("conv_out.bias"), self.mom_pad)
+        _load_conv(L, "conv_in", "conv_in", cin_pad=self.cin_pad)
+        _load_blocks(L, seq)
+        L.norm("norm_out", "norm_out")
+        _load_conv(L, "conv_out", "conv_out", cout_pad=self.mom_pad)
         if quant is not None:
-            qw, qb = quant
-            qw = qw if isinstance(qw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(qw))
-            w["q.w"] = ops.pack_conv_weight(qw.to(self.device), self.mom_pad, self.mom_pad)
-            w["q.b"] = self._vec(qb, self.mom_pad)
-        self.w = w
+            w["q.w"], w["q.b"] = L.conv(quant[0], self.mom_pad, self.mom_pad), L.vec(quant[1], self.mom_pad)
+        self.w = L.finish(self.parameter_shapes(prefix))
         self._plans.clear()
 
     _Plan = Decoder._Plan

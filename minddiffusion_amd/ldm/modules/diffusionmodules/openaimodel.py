@@ -23,13 +23,12 @@ import os
 import re
 import weakref
 
-import numpy as np
 import torch
 
 from .... import ops
 from ...._lib import MdxError
 from ....planner import PlanBuilder, round_up, capture_or_eager
-from ....weights import check_state_dict
+from ....loader import WeightLoader, named_layers
 
 f16, f32 = torch.float16, torch.float32
 
@@ -158,16 +157,6 @@ class UNetModel:
                 outb.append(layers)
         return inb, mid, outb
 
-    def _named_layers(self):
-        for i, blk in enumerate(self.input_blocks):
-            for j, layer in enumerate(blk):
-                yield f"input_blocks.{i}.{j}.", layer
-        for j, layer in enumerate(self.middle_block):
-            yield f"middle_block.{j}.", layer
-        for i, blk in enumerate(self.output_blocks):
-            for j, layer in enumerate(blk):
-                yield f"output_blocks.{i}.{j}.", layer
-
     def parameter_shapes(self):
         """name -> shape, in the reference's naming."""
         mc, ted, ctx = self.model_channels, self.time_embed_dim, self.context_dim
@@ -176,7 +165,7 @@ class UNetModel:
         if self.num_classes is not None:
             s["label_emb.embedding_table"] = (self.num_classes, ted)
         ssn = 2 if self.use_scale_shift_norm else 1
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             kind = layer[0]
             if kind == "conv":
                 s[pre + "conv.weight"] = (layer[2], layer[1], 3, 3)
@@ -238,7 +227,7 @@ class UNetModel:
 
     def _lora_targets(self):
         """(reference name of the Dense, out, in) of every LoRA target, in structure order."""
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             if layer[0] != "st":
                 continue
             inner = layer[2] * layer[3]
@@ -262,164 +251,115 @@ class UNetModel:
         return s
 
     # ------------------------------------------------------------------ weights
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _dev_own(self, a, dtype):
-        """_dev, but never the caller's own tensor: what the model keeps (the merge sources) must not change when the caller
-        reuses its buffer for the next checkpoint."""
-        t = self._dev(a, dtype)
-        return t.clone() if t is a else t
-
-    def _pack_conv(self, wt, cin_pad=None, cout_pad=None):
-        """[Cout,Cin,kh,kw] -> the packed GEMM weight storage (ops.pack_conv_weight, include/mdx.h)."""
-        wt = wt if isinstance(wt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wt))
-        return ops.pack_conv_weight(wt.to(self.device), cin_pad, cout_pad)
-
-    def _pack_dense(self, wt):
-        """nn.Dense weight [out,in] -> packed GEMM weight storage."""
-        return ops.pack_gemm_weight(self._dev(wt, f16))
-
-    def _pad_vec(self, v, n):
-        v = self._dev(v, f32)
-        if v.numel() == n:
-            return v
-        out = torch.zeros(n, dtype=f32, device=self.device)
-        out[: v.numel()] = v
-        return out
-
     def load_state_dict(self, params, strict=True):
         """params: name -> array/tensor keyed by the reference's parameter names.  Packs everything into
         the kernels' layouts on the device (fp16 weights, fp32 biases / norm affine)."""
         shapes = self.parameter_shapes()
+        who = "UNetModel.load_state_dict"
         lora_params = {}
         if self.enable_lora:    # the adapter may ride in the same dict (one merged checkpoint) or come in a second call
             lora_params = {k: v for k, v in params.items() if is_lora_key(k)}
             params = {k: v for k, v in params.items() if k not in lora_params}
         # every owned parameter is needed to run: missing keys always raise; strict additionally rejects unexpected ones
-        check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True, "UNetModel.load_state_dict")
+        L = WeightLoader(params, self.device, who)
+        L.check(shapes, unexpected=strict)
         if lora_params:
-            lora_params = self._check_lora(lora_params, strict, "UNetModel.load_state_dict")
-        P = params
-        w = {}
-        w["te0.w"] = self._dev(P["time_embed.0.weight"], f16)
-        w["te0.b"] = self._dev(P["time_embed.0.bias"], f32)
-        w["te2.w"] = self._dev(P["time_embed.2.weight"], f16)
-        w["te2.b"] = self._dev(P["time_embed.2.bias"], f32)
+            lora_params = self._check_lora(lora_params, strict, who)
+        ln_fold = os.environ.get("MDX_UNET_LN_FOLD", "1") != "0"
+        qkv_merge = os.environ.get("MDX_UNET_QKV_MERGE", "1") != "0"
+        w = L.w
+        w["te0.w"], w["te0.b"] = L.raw("time_embed.0.weight", f16), L.vec("time_embed.0.bias")
+        w["te2.w"], w["te2.b"] = L.raw("time_embed.2.weight", f16), L.vec("time_embed.2.bias")
         if self.num_classes is not None:
-            w["label_emb"] = self._dev(P["label_emb.embedding_table"], f32)
+            w["label_emb"] = L.raw("label_emb.embedding_table", f32)
         emb_w, emb_b, self._emb_off = [], [], {}
         off = 0
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             kind = layer[0]
             if kind == "conv":
-                w[pre + "w"] = self._pack_conv(P[pre + "conv.weight"], cin_pad=self.cin_pad)
-                w[pre + "b"] = self._dev(P[pre + "conv.bias"], f32)
+                w[pre + "w"], w[pre + "b"] = L.conv(pre + "conv.weight", cin_pad=self.cin_pad), L.vec(pre + "conv.bias")
             elif kind in ("res", "resdown", "resup"):
                 cin, cout = layer[1], layer[2]
                 for n in ("in_layers_norm", "out_layers_norm"):
-                    w[pre + n + ".g"] = self._dev(P[pre + n + ".gamma"], f32)
-                    w[pre + n + ".b"] = self._dev(P[pre + n + ".beta"], f32)
-                w[pre + "conv1.w"] = self._pack_conv(P[pre + "in_layers_conv.conv.weight"])
-                w[pre + "conv1.b"] = self._dev(P[pre + "in_layers_conv.conv.bias"], f32)
-                w[pre + "conv2.w"] = self._pack_conv(P[pre + "out_layers_conv.conv.weight"])
-                w[pre + "conv2.b"] = self._dev(P[pre + "out_layers_conv.conv.bias"], f32)
+                    L.norm(pre + n, pre + n)
+                w[pre + "conv1.w"], w[pre + "conv1.b"] = L.conv(pre + "in_layers_conv.conv.weight"), L.vec(pre + "in_layers_conv.conv.bias")
+                w[pre + "conv2.w"], w[pre + "conv2.b"] = L.conv(pre + "out_layers_conv.conv.weight"), L.vec(pre + "out_layers_conv.conv.bias")
                 if cin != cout:
-                    w[pre + "skip.w"] = self._pack_conv(P[pre + "skip_connection.conv.weight"])
-                    w[pre + "skip.b"] = self._dev(P[pre + "skip_connection.conv.bias"], f32)
-                emb_w.append(self._dev(P[pre + "emb_layers.1.weight"], f16))
-                emb_b.append(self._dev(P[pre + "emb_layers.1.bias"], f32))
+                    w[pre + "skip.w"], w[pre + "skip.b"] = L.conv(pre + "skip_connection.conv.weight"), L.vec(pre + "skip_connection.conv.bias")
+                emb_w.append(L.raw(pre + "emb_layers.1.weight", f16))
+                emb_b.append(L.vec(pre + "emb_layers.1.bias"))
                 self._emb_off[pre] = off
                 off += cout * (2 if self.use_scale_shift_norm else 1)
             elif kind == "st":
                 inner = layer[2] * layer[3]
-                w[pre + "norm.g"] = self._dev(P[pre + "norm.gamma"], f32)
-                w[pre + "norm.b"] = self._dev(P[pre + "norm.beta"], f32)
+                L.norm(pre + "norm", pre + "norm")
+                proj = {}
                 for n in ("proj_in", "proj_out"):
-                    wt = self._dev(P[pre + n + ".weight"], f16)
-                    w[pre + n + ".w"] = self._pack_dense(wt.reshape(wt.shape[0], wt.shape[1]))  # 1x1 conv == Dense in NHWC
-                    w[pre + n + ".b"] = self._dev(P[pre + n + ".bias"], f32)
+                    wt = L.raw(pre + n + ".weight", f16)
+                    proj[n] = wt.reshape(wt.shape[0], wt.shape[1])     # 1x1 conv == Dense in NHWC
+                    w[pre + n + ".w"], w[pre + n + ".b"] = L.dense(proj[n]), L.vec(pre + n + ".bias")
                 for k in range(self.transformer_depth):
                     t = pre + f"transformer_blocks.{k}."
                     # self-attention: ONE [q | k | v] projection launch; the q|k columns are stored row-major and the v columns
                     # transposed (mdx_gemm_desc.n_split), which needs 2 * inner to be a multiple of 128
-                    wq, wk, wv = (self._dev(P[t + f"attn1.to_{n}.weight"], f16) for n in "qkv")
+                    wq, wk, wv = (L.raw(t + f"attn1.to_{n}.weight", f16) for n in "qkv")
                     for n in ("norm1", "norm2", "norm3"):
-                        w[t + n + ".g"] = self._dev(P[t + n + ".gamma"], f32)
-                        w[t + n + ".b"] = self._dev(P[t + n + ".beta"], f32)
+                        L.norm(t + n, t + n)
                     # LayerNorm fold (mdx_gemm_desc.ln_stats): norm1/2/3 disappear into the GEMMs around them -- the consumer
                     # weights become gamma (.) W, with S = row sums and W beta (+ b) as the bias (ops.fold_layernorm)
-                    fold = inner % 64 == 0 and os.environ.get("MDX_UNET_LN_FOLD", "1") != "0"
+                    fold = inner % 64 == 0 and ln_fold
 
                     def put(name, wt, norm, bias=None):
                         if fold:
                             wt, w[name + ".s"], w[name + ".cb"] = ops.fold_layernorm(wt, w[t + norm + ".g"], w[t + norm + ".b"], bias)
-                        w[name + ".w"] = self._pack_dense(wt)
-                    if (2 * wq.shape[0]) % 128 == 0 and os.environ.get("MDX_UNET_QKV_MERGE", "1") != "0":
+                        w[name + ".w"] = L.dense(wt)
+                    if (2 * wq.shape[0]) % 128 == 0 and qkv_merge:
                         put(t + "attn1.qkv", torch.cat([wq, wk, wv], 0), "norm1")
                     else:   # fall back to a [q | k] launch and a transposed-store v launch
-                        w[t + "attn1.qk.w"] = self._pack_dense(torch.cat([wq, wk], 0))
-                        w[t + "attn1.v.w"] = self._pack_dense(wv)
-                    put(t + "attn2.q", self._dev(P[t + "attn2.to_q.weight"], f16), "norm2")
-                    w[t + "attn2.k.w"] = self._pack_dense(P[t + "attn2.to_k.weight"])
-                    w[t + "attn2.v.w"] = self._pack_dense(P[t + "attn2.to_v.weight"])
+                        w[t + "attn1.qk.w"] = L.dense(torch.cat([wq, wk], 0))
+                        w[t + "attn1.v.w"] = L.dense(wv)
+                    wq2 = L.raw(t + "attn2.to_q.weight", f16)
+                    put(t + "attn2.q", wq2, "norm2")
+                    w[t + "attn2.k.w"] = L.dense(t + "attn2.to_k.weight")
+                    w[t + "attn2.v.w"] = L.dense(t + "attn2.to_v.weight")
+                    wo = {a: L.raw(t + a + ".to_out.0.weight", f16) for a in ("attn1", "attn2")}
                     for a in ("attn1", "attn2"):
-                        w[t + a + ".o.w"] = self._pack_dense(P[t + a + ".to_out.0.weight"])
-                        w[t + a + ".o.b"] = self._dev(P[t + a + ".to_out.0.bias"], f32)
+                        w[t + a + ".o.w"], w[t + a + ".o.b"] = L.dense(wo[a]), L.vec(t + a + ".to_out.0.bias")
                     # GEGLU (attention.py:41-51): interleave 64 'x' rows with their 64 'gate' rows per 128-wide tile
-                    gw = self._dev(P[t + "ff.net.0.proj.weight"], f16)
-                    gb = self._dev(P[t + "ff.net.0.proj.bias"], f32)
+                    gw, gb = L.raw(t + "ff.net.0.proj.weight", f16), L.vec(t + "ff.net.0.proj.bias")
                     half = 4 * inner
-                    assert half % 64 == 0
-                    nt = half // 64
-                    w[t + "ff1.b"] = torch.stack([gb[:half].reshape(nt, 64), gb[half:].reshape(nt, 64)], 1).reshape(-1).contiguous()
-                    put(t + "ff1", torch.stack([gw[:half].reshape(nt, 64, inner), gw[half:].reshape(nt, 64, inner)], 1)
-                        .reshape(2 * half, inner), "norm3", w[t + "ff1.b"])
-                    w[t + "ff2.w"] = self._pack_dense(P[t + "ff.net.2.weight"])
-                    w[t + "ff2.b"] = self._dev(P[t + "ff.net.2.bias"], f32)
+                    w[t + "ff1.b"] = ops.geglu_interleave(gb[:half], gb[half:], 64)
+                    put(t + "ff1", ops.geglu_interleave(gw[:half], gw[half:], 64), "norm3", w[t + "ff1.b"])
+                    w2 = L.raw(t + "ff.net.2.weight", f16)
+                    w[t + "ff2.w"], w[t + "ff2.b"] = L.dense(w2), L.vec(t + "ff.net.2.bias")
                     # row-local fused tail (mdx_st_tail_f16): to_out1 .. proj_out as one launch where a level has enough
                     # token rows to fill the chip; its own packing (MFMA-fragment-major per-wave streams, unfolded LayerNorms)
                     if (self.transformer_depth == 1 and inner == layer[1]
                             and ops.st_tail_supported(inner, layer[2], layer[3], 64, 64)):
-                        po = self._dev(P[pre + "proj_out.weight"], f16)
                         w[t + "tail.stream"], w[t + "tail.vec"] = ops.pack_st_tail(
-                            self._dev(P[t + "attn1.to_out.0.weight"], f16), self._dev(P[t + "attn2.to_q.weight"], f16),
-                            self._dev(P[t + "attn2.to_out.0.weight"], f16), gw, self._dev(P[t + "ff.net.2.weight"], f16),
-                            po.reshape(po.shape[0], po.shape[1]),
+                            wo["attn1"], wq2, wo["attn2"], gw, w2, proj["proj_out"],
                             w[t + "attn1.o.b"], w[t + "norm2.g"], w[t + "norm2.b"], w[t + "attn2.o.b"], w[t + "norm3.g"],
                             w[t + "norm3.b"], gb, w[t + "ff2.b"], w[pre + "proj_out.b"])
                         if ops.st_head_supported(inner, 64, 64):
-                            pi = self._dev(P[pre + "proj_in.weight"], f16)
                             w[t + "head.stream"], w[t + "head.vec"] = ops.pack_st_head(
-                                pi.reshape(pi.shape[0], pi.shape[1]), wq, wk, wv, w[pre + "norm.g"], w[pre + "norm.b"],
+                                proj["proj_in"], wq, wk, wv, w[pre + "norm.g"], w[pre + "norm.b"],
                                 w[pre + "proj_in.b"], w[t + "norm1.g"], w[t + "norm1.b"])
             elif kind == "down" and self.conv_resample:
-                w[pre + "w"] = self._pack_conv(P[pre + "op.conv.weight"])
-                w[pre + "b"] = self._dev(P[pre + "op.conv.bias"], f32)
+                w[pre + "w"], w[pre + "b"] = L.conv(pre + "op.conv.weight"), L.vec(pre + "op.conv.bias")
             elif kind == "up" and self.conv_resample:
-                w[pre + "w"] = self._pack_conv(P[pre + "conv.conv.weight"])
-                w[pre + "b"] = self._dev(P[pre + "conv.conv.bias"], f32)
+                w[pre + "w"], w[pre + "b"] = L.conv(pre + "conv.conv.weight"), L.vec(pre + "conv.conv.bias")
                 if layer[1] % 64 == 0 and ops.get_option("unet_subpixel_upsample"):
                     # sub-pixel form of nearest-2x + conv (mdx_gemm_desc.w_sub): 4 Cin instead of 9 Cin products per output; the
                     # library uses it where the eight-wave conv core applies and falls back to `w` + the upsampling gather elsewhere
-                    wt = P[pre + "conv.conv.weight"]
-                    wt = wt if isinstance(wt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wt))
-                    w[pre + "wsub"] = ops.pack_subpixel_conv_weight(wt.to(self.device))
+                    w[pre + "wsub"] = ops.pack_subpixel_conv_weight(L.raw(pre + "conv.conv.weight", f32))
         w["emb.w"] = torch.cat(emb_w, 0).contiguous()
         w["emb.b"] = torch.cat(emb_b, 0).contiguous()
         self._emb_total = off
-        if self.n_embed is None:
-            w["out.g"] = self._dev(P["out.0.gamma"], f32)
-            w["out.b"] = self._dev(P["out.0.beta"], f32)
-            w["out.w"] = self._pack_conv(P["out.2.conv.weight"], cout_pad=self.cout_pad)
-            w["out.cb"] = self._pad_vec(P["out.2.conv.bias"], self.cout_pad)
-        else:
-            w["out.g"] = self._dev(P["id_predictor.0.gamma"], f32)
-            w["out.b"] = self._dev(P["id_predictor.0.beta"], f32)
-            w["out.w"] = self._pack_conv(P["id_predictor.1.conv.weight"], cout_pad=self.cout_pad)
-            w["out.cb"] = self._pad_vec(P["id_predictor.1.conv.bias"], self.cout_pad)
-        self.w = w
+        # with n_embed the reference builds `out` as well (openaimodel.py:520-531); only id_predictor runs
+        norm, conv = ("out.0", "out.2.conv") if self.n_embed is None else ("id_predictor.0", "id_predictor.1.conv")
+        w["out.g"], w["out.b"] = L.vec(norm + ".gamma"), L.vec(norm + ".beta")
+        w["out.w"] = L.conv(conv + ".weight", cout_pad=self.cout_pad)
+        w["out.cb"] = L.vec(conv + ".bias", pad=self.cout_pad)
         self._frag_w = {}
         self._geglu80 = {}
         self._plans = {}
@@ -429,7 +369,9 @@ class UNetModel:
         self._lora_base, self._lora_sites = {}, {}
         if self.enable_lora:
             for name, _, _ in self._lora_targets():
-                self._lora_base[name] = self._dev_own(P[name + ".weight"], f32)
+                self._lora_base[name] = L.own(name + ".weight", f32)
+        self.w = L.finish(shapes, unused=() if self.n_embed is None else [k for k in shapes if k.startswith("out.")])
+        if self.enable_lora:
             self._lora_sites = self._find_lora_sites()
             if lora_params:
                 self._set_lora(lora_params)
@@ -452,7 +394,7 @@ class UNetModel:
         w = self.w
         T, F = ops.LORA_TILED, ops.LORA_FRAG
         sites = {}
-        for pre, layer in self._named_layers():
+        for pre, layer in named_layers(self):
             if layer[0] != "st":
                 continue
             inner = layer[2] * layer[3]
@@ -498,13 +440,12 @@ class UNetModel:
             raise KeyError(f"{who}: adapter keys mix the prefixes {sorted(found)}")
         prefix = found.pop() if found else LORA_PREFIXES[0]
         shapes = self.lora_parameter_shapes(prefix)
-        check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True, who)
+        WeightLoader(params, self.device, who).check(shapes, unexpected=strict)
         return {k.replace("." + prefix, "." + LORA_PREFIXES[0]): params[k] for k in shapes}
 
     def _set_lora(self, checked):
-        p = LORA_PREFIXES[0]
-        self._lora = {name: (self._dev_own(checked[f"{name}.{p}lora_a"], f32), self._dev_own(checked[f"{name}.{p}lora_b"], f32))
-                      for name in self._lora_base}
+        p, L = LORA_PREFIXES[0], WeightLoader(checked, self.device, "UNetModel.load_lora_state_dict")
+        self._lora = {name: (L.own(f"{name}.{p}lora_a", f32), L.own(f"{name}.{p}lora_b", f32)) for name in self._lora_base}
         self._merge_lora()
 
     def _merge_lora(self):
@@ -648,7 +589,7 @@ class UNetModel:
             # to_k / to_v (Dense(context_dim, inner)) then see the block's own tokens, which only type-checks -- in the reference
             # as here -- when context_dim equals the transformer width at every attention level
             if getattr(self, "_selfctx_bad", None) is None:      # (structure and context_dim are fixed at construction: checked once,
-                self._selfctx_bad = sorted({l[2] * l[3] for _, l in self._named_layers()      # not on every sampler step)
+                self._selfctx_bad = sorted({l[2] * l[3] for _, l in named_layers(self)      # not on every sampler step)
                                             if l[0] == "st" and l[2] * l[3] != self.context_dim})
             bad = self._selfctx_bad
             if bad:

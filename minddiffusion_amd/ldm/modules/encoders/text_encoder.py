@@ -16,6 +16,7 @@ import torch
 
 from ...._lib import MdxError
 from .... import ops
+from ....loader import WeightLoader
 from ....planner import PlanBuilder, capture_or_eager
 
 f16, f32 = torch.float16, torch.float32
@@ -54,36 +55,28 @@ class TextEncoder:
             s[b + "ln_2.gamma"] = (w,); s[b + "ln_2.beta"] = (w,)
         return s
 
-    def _dev(self, a, dtype):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
     def load_state_dict(self, params, prefix="", strict=True):
         shapes = self.parameter_shapes(prefix)
-        from ....weights import check_state_dict
-        check_state_dict(shapes, {k: v for k, v in params.items() if strict or k in shapes}, True,
-                         "TextEncoder.load_state_dict")
+        L = WeightLoader(params, self.device, "TextEncoder.load_state_dict", prefix=prefix)
+        L.check(shapes, unexpected=strict)
         wd = self.width
-        g = lambda k: params[prefix + k]
-        w = {"emb": self._dev(g("embedding_table"), f16)}
+        w = L.w
+        w["emb"] = L.raw("embedding_table", f16)
         pos = torch.zeros((self.t_pad, wd), dtype=f16, device=self.device)      # pad rows: zeros (never read back)
-        pos[: self.context_length] = self._dev(g("positional_embedding"), f16)
+        pos[: self.context_length] = L.raw("positional_embedding", f16)
         w["pos"] = pos
-        w["lnf.g"], w["lnf.b"] = self._dev(g("ln_final.gamma"), f32), self._dev(g("ln_final.beta"), f32)
+        L.norm("lnf", "ln_final")
         for i in range(self.layers):
             b, o = f"transformer_layer.resblocks.{i}.", f"l{i}."
-            ipw, ipb = self._dev(g(b + "attn.attn.in_proj.weight"), f16), self._dev(g(b + "attn.attn.in_proj.bias"), f32)
-            w[o + "qk.w"], w[o + "qk.b"] = ops.pack_gemm_weight(ipw[: 2 * wd].contiguous()), ipb[: 2 * wd].contiguous()
-            w[o + "v.w"], w[o + "v.b"] = ops.pack_gemm_weight(ipw[2 * wd:].contiguous()), ipb[2 * wd:].contiguous()
-            w[o + "out.w"] = ops.pack_gemm_weight(self._dev(g(b + "attn.attn.out_proj.weight"), f16))
-            w[o + "out.b"] = self._dev(g(b + "attn.attn.out_proj.bias"), f32)
-            w[o + "fc.w"] = ops.pack_gemm_weight(self._dev(g(b + "c_fc.weight"), f16))
-            w[o + "fc.b"] = self._dev(g(b + "c_fc.bias"), f32)
-            w[o + "proj.w"] = ops.pack_gemm_weight(self._dev(g(b + "c_proj.weight"), f16))
-            w[o + "proj.b"] = self._dev(g(b + "c_proj.bias"), f32)
+            ipw, ipb = L.raw(b + "attn.attn.in_proj.weight", f16), L.vec(b + "attn.attn.in_proj.bias")
+            w[o + "qk.w"], w[o + "qk.b"] = L.dense(ipw[: 2 * wd]), ipb[: 2 * wd].contiguous()
+            w[o + "v.w"], w[o + "v.b"] = L.dense(ipw[2 * wd:]), ipb[2 * wd:].contiguous()
+            w[o + "out.w"], w[o + "out.b"] = L.dense(b + "attn.attn.out_proj.weight"), L.vec(b + "attn.attn.out_proj.bias")
+            w[o + "fc.w"], w[o + "fc.b"] = L.dense(b + "c_fc.weight"), L.vec(b + "c_fc.bias")
+            w[o + "proj.w"], w[o + "proj.b"] = L.dense(b + "c_proj.weight"), L.vec(b + "c_proj.bias")
             for n in ("ln_1", "ln_2"):
-                w[o + n + ".g"], w[o + n + ".b"] = self._dev(g(b + n + ".gamma"), f32), self._dev(g(b + n + ".beta"), f32)
-        self.w = w
+                L.norm(o + n, b + n)
+        self.w = L.finish(shapes)
         self._plans.clear()
 
     class _Plan:
