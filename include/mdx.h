@@ -473,6 +473,31 @@ int mdx_sampler_step_f32(const float* x, const void* eps_u, const void* eps_c, i
                          const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
                          int W, mdx_stream_t s);
 
+/* ---- the same fused update for a model whose output is eps or v (SD 2.x 768-v checkpoints, `parameterization: "v"`)
+ * The reference's LatentDiffusion stops at eps / x0 (ddpm.py:65); its dpm_solver.py:281-284 carries the conversion for
+ * model_type "v", and upstream LDM's predict_eps_from_z_and_v is the same two lines.
+ * out_u / out_c: UNet outputs, NHWC fp16 [B][HW][out_ld] (first C channels used).
+ *   m   = out_c                                  if out_u == NULL
+ *       = out_u + cfg_scale * (out_c - out_u)    otherwise            (plms.py:197, applied to the model outputs)
+ *   e_t = m                                                            pred_type == MDX_PRED_EPS
+ *       = sqrt_at_model * m + sqrt_one_minus_at_model * x_model        pred_type == MDX_PRED_V   (dpm_solver.py:281-284)
+ * then e', pred_x0, x_prev exactly as mdx_sampler_step_f32 (e_t_out receives the converted eps, so a multistep history
+ * holds eps).  x_model, sqrt_at_model, sqrt_one_minus_at_model: the latent and the schedule point the model was EVALUATED
+ * at -- not x / sqrt_at / sqrt_one_minus_at in the second call of the PLMS first step (plms.py:231-235: model at
+ * (x_next, t_next), update applied to x at index).  x_model: NCHW fp32 like x; NULL = x; not read for MDX_PRED_EPS.
+ * x_prev may alias x and / or x_model (x_model[i] is read before the first store for element i, x[i] before x_prev[i] is
+ * stored); the outputs may alias no other input.
+ * With MDX_PRED_EPS the launch IS mdx_sampler_step_f32's (x_model is not read), bit for bit.
+ * coef4 is a HOST pointer to 4 floats (read at call time). */
+#define MDX_PRED_EPS 0
+#define MDX_PRED_V 1
+int mdx_sampler_step_pred_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                              float cfg_scale, int pred_type, float sqrt_at_model, float sqrt_one_minus_at_model,
+                              const float* old1, const float* old2, const float* old3, const float* coef4,
+                              float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
+                              const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
+                              int W, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

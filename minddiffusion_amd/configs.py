@@ -22,6 +22,10 @@ WUKONG_INPAINT_UNET = dict(WUKONG_UNET, in_channels=9)
 SD2_LDM = dict(linear_start=0.00085, linear_end=0.0120, timesteps=1000, scale_factor=0.18215,
                conditioning_key="crossattn", image_size=64, channels=4, use_fp16=True)
 
+# the SD 2.x 768-v checkpoints: v-prediction at a 96x96 latent.  The UNet is SD2_UNET unchanged -- only what its output means
+# differs, and the samplers convert it to eps inside their fused step kernel.
+SD2_768V_LDM = dict(SD2_LDM, parameterization="v", image_size=96)
+
 # a small structurally identical UNet for tests (head dim 64, channels multiples of 64)
 TINY_UNET = dict(image_size=8, in_channels=4, out_channels=4, model_channels=64, attention_resolutions=[2, 1],
                  num_res_blocks=1, channel_mult=[1, 2], num_head_channels=64, use_spatial_transformer=True,

@@ -153,8 +153,16 @@ struct StepParams {
     int eps_ld, B, C, HW;
     float cfg_scale, c0, c1, c2, c3;
     float sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma;
+    // MDX_PRED_V only: the latent the model was evaluated on, sqrt(alphas_cumprod) and sqrt(1 - alphas_cumprod) there
+    const float* x_model;
+    float am, bm;
 };
 
+// PRED: MDX_PRED_EPS | MDX_PRED_V.  No __restrict__: x_prev may alias x, and for MDX_PRED_V also x_model (the second call of
+// the PLMS first step writes the latent its model output was computed on).  The outputs may alias no other input, so what
+// matters is that x_model[i] is read before the first store for i and x[i] before x_prev[i] is stored -- both hold below.
+// MDX_PRED_EPS compiles to exactly the statements mdx_sampler_step_f32 has always launched.
+template <int PRED>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
     mdx_kernarg_touch<sizeof(StepParams)>();
     const size_t total = (size_t)p.B * p.C * p.HW;
@@ -169,6 +177,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
             const float eu = (float)p.eps_u[ei];
             e_t = eu + p.cfg_scale * (e_t - eu);
         }
+        if constexpr (PRED == MDX_PRED_V) e_t = p.am * e_t + p.bm * p.x_model[i];   // eps = a v + b x_m (dpm_solver.py:281-284)
         if (p.e_t_out) p.e_t_out[i] = e_t;
         float ep = p.c0 * e_t;
         if (p.old1) ep += p.c1 * p.old1[i];
@@ -256,20 +265,24 @@ extern "C" int mdx_dense_small_f32(const float* x, int x_ld, const void* w, cons
     return MDX_OK;
 }
 
-extern "C" int mdx_sampler_step_f32(const float* x, const void* eps_u, const void* eps_c, int eps_ld, float cfg_scale,
-                                    const float* old1, const float* old2, const float* old3, const float* coef4,
-                                    float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef,
-                                    float sigma, const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
-                                    int B, int C, int H, int W, mdx_stream_t s) {
-    MDX_REQUIRE(x && eps_c && coef4 && x_prev, "mdx_sampler_step_f32: null pointer");
-    MDX_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && eps_ld >= C, "mdx_sampler_step_f32: bad extents");
-    MDX_REQUIRE(sigma == 0.f || noise, "mdx_sampler_step_f32: sigma != 0 needs a noise tensor");
+// One host body for both entries; `fn` names the entry in its messages.
+static int sampler_step_launch(const char* fn, const float* x, const float* x_model, const void* out_u, const void* out_c,
+                               int out_ld, float cfg_scale, int pred_type, float am, float bm, const float* old1,
+                               const float* old2, const float* old3, const float* coef4, float sqrt_at,
+                               float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
+                               const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
+                               int W, mdx_stream_t s) {
+    MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
+    MDX_REQUIRE(x && out_c && coef4 && x_prev, "%s: null pointer", fn);
+    MDX_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && out_ld >= C, "%s: bad extents", fn);
+    MDX_REQUIRE(sigma == 0.f || noise, "%s: sigma != 0 needs a noise tensor", fn);
     MDX_REQUIRE((coef4[1] == 0.f || old1) && (coef4[2] == 0.f || old2) && (coef4[3] == 0.f || old3),
-                "mdx_sampler_step_f32: non-zero multistep coefficient without its eps history");
+                "%s: non-zero multistep coefficient without its eps history", fn);
     StepParams p{};
     p.x = x;
-    p.eps_u = (const f16*)eps_u;
-    p.eps_c = (const f16*)eps_c;
+    p.x_model = x_model ? x_model : x;
+    p.eps_u = (const f16*)out_u;
+    p.eps_c = (const f16*)out_c;
     p.old1 = coef4[1] != 0.f ? old1 : nullptr;
     p.old2 = coef4[2] != 0.f ? old2 : nullptr;
     p.old3 = coef4[3] != 0.f ? old3 : nullptr;
@@ -277,7 +290,7 @@ extern "C" int mdx_sampler_step_f32(const float* x, const void* eps_u, const voi
     p.e_t_out = e_t_out;
     p.x_prev = x_prev;
     p.pred_x0 = pred_x0;
-    p.eps_ld = eps_ld;
+    p.eps_ld = out_ld;
     p.B = B;
     p.C = C;
     p.HW = H * W;
@@ -291,9 +304,38 @@ extern "C" int mdx_sampler_step_f32(const float* x, const void* eps_u, const voi
     p.sqrt_a_prev = sqrt_a_prev;
     p.dir_coef = dir_coef;
     p.sigma = sigma;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((size_t)B * C * H * W)), dim3(256), 0, (hipStream_t)s, p);
-    MDX_LAUNCH_CHECK("mdx_sampler_step_f32");
+    p.am = am;
+    p.bm = bm;
+    const dim3 grid(grid_for((size_t)B * C * H * W));
+    if (pred_type == MDX_PRED_V)
+        hipLaunchKernelGGL(sampler_step_kernel<MDX_PRED_V>, grid, dim3(256), 0, (hipStream_t)s, p);
+    else
+        hipLaunchKernelGGL(sampler_step_kernel<MDX_PRED_EPS>, grid, dim3(256), 0, (hipStream_t)s, p);
+    MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
+}
+
+extern "C" int mdx_sampler_step_f32(const float* x, const void* eps_u, const void* eps_c, int eps_ld, float cfg_scale,
+                                    const float* old1, const float* old2, const float* old3, const float* coef4,
+                                    float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef,
+                                    float sigma, const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
+                                    int B, int C, int H, int W, mdx_stream_t s) {
+    return sampler_step_launch("mdx_sampler_step_f32", x, nullptr, eps_u, eps_c, eps_ld, cfg_scale, MDX_PRED_EPS, 1.f, 0.f,
+                               old1, old2, old3, coef4, sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise,
+                               e_t_out, x_prev, pred_x0, B, C, H, W, s);
+}
+
+extern "C" int mdx_sampler_step_pred_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
+                                         int out_ld, float cfg_scale, int pred_type, float sqrt_at_model,
+                                         float sqrt_one_minus_at_model, const float* old1, const float* old2,
+                                         const float* old3, const float* coef4, float sqrt_at, float sqrt_one_minus_at,
+                                         float sqrt_a_prev, float dir_coef, float sigma, const float* noise,
+                                         float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H, int W,
+                                         mdx_stream_t s) {
+    return sampler_step_launch("mdx_sampler_step_pred_f32", x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
+                               sqrt_at_model, sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at,
+                               sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev, pred_x0, B, C, H, W,
+                               s);
 }
 
 extern "C" int mdx_probe_mfma_32x32x16_f16(const void* a, const void* b, float* c, mdx_stream_t s) {

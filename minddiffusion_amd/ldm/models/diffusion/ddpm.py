@@ -58,7 +58,9 @@ class LatentDiffusion:
                  conditioning_key="crossattn", scale_factor=1.0, parameterization="eps", use_fp16=False,
                  first_stage_config=None, cond_stage_config=None, image_size=64, channels=4, v_posterior=0.0,
                  **unused):
-        assert parameterization in ["eps", "x0"], 'currently only supporting "eps" and "x0"'
+        # "v": the SD 2.x 768-v checkpoints.  The reference stops at eps / x0 (ddpm.py:65); the samplers convert the UNet's v
+        # output to eps inside their fused step kernel (mdx_sampler_step_pred_f32)
+        assert parameterization in ["eps", "x0", "v"], 'currently only supporting "eps", "x0" and "v"'
         self.parameterization = parameterization
         self.image_size = image_size
         self.channels = channels
@@ -165,6 +167,27 @@ class LatentDiffusion:
         a = torch.as_tensor(self.sqrt_alphas_cumprod, device=x_start.device)[t].reshape(-1, 1, 1, 1)
         b = torch.as_tensor(self.sqrt_one_minus_alphas_cumprod, device=x_start.device)[t].reshape(-1, 1, 1, 1)
         return a * x_start + b * noise
+
+    # ---- v-prediction (upstream LDM ddpm.py predict_eps_from_z_and_v / predict_start_from_z_and_v / get_v; the reference's
+    #      dpm_solver.py:281-284 is the first of them).  Plain torch on any device, outside the hot path: the samplers do the
+    #      v -> eps conversion inside their fused step kernel.
+    def _ab(self, t, like):
+        t = torch.as_tensor(t, device=like.device).long()
+        a = torch.as_tensor(self.sqrt_alphas_cumprod, device=like.device)[t].reshape(-1, 1, 1, 1)
+        b = torch.as_tensor(self.sqrt_one_minus_alphas_cumprod, device=like.device)[t].reshape(-1, 1, 1, 1)
+        return a, b
+
+    def predict_eps_from_z_and_v(self, x_t, t, v):
+        a, b = self._ab(t, x_t)
+        return a * v + b * x_t
+
+    def predict_start_from_z_and_v(self, x_t, t, v):
+        a, b = self._ab(t, x_t)
+        return a * x_t - b * v
+
+    def get_v(self, x, noise, t):
+        a, b = self._ab(t, x)
+        return a * noise - b * x
 
     # ---- ddpm.py:274-288: outside the hot path, delegated to injected objects
     def get_learned_conditioning(self, c):

@@ -10,6 +10,8 @@ fused ``mdx_sampler_step_f32`` kernel.  With e = CFG-combined eps, x0 = (x - sig
 is exactly that kernel's  sqrt_a_prev * pred_x0 + dir_coef * e' + sigma * noise  with
     sqrt_at = alpha_s, sqrt_one_minus_at = sigma_s, sqrt_a_prev = A alpha_s + c0, dir_coef = A sigma_s,
     sigma = c1, noise = x0_prev  -- so no extra elementwise passes and no extra kernel.
+A `parameterization: "v"` model goes through ``mdx_sampler_step_pred_f32``, which first converts the CFG-combined v to
+e = alpha_s v + sigma_s x (the reference's model_wrapper for model_type "v", dpm_solver.py:281-284) in the same launch.
 Differences from the reference, both on the fp32 side of its fp16 arithmetic: the time grid and the schedule scalars
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
@@ -85,6 +87,7 @@ class DPMSolverSampler:
         t_all = t_all[:, None].expand(S, nb).contiguous()
         x0_bufs = [torch.empty_like(img), torch.empty_like(img)]    # data predictions at the last two grid points
         x_next = torch.empty_like(img)
+        v_pred = getattr(self.model, "parameterization", "eps") == "v"
         for k, p in enumerate(plan):
             if use_cfg:
                 x_in[:b].copy_(img)
@@ -95,9 +98,13 @@ class DPMSolverSampler:
                 eps_u, eps_c = None, self._eps_nhwc(img, t_all[k], c_in, None if temb_all is None else temb_all[k])
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
             f = np.float32
-            ops.sampler_step(img, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.),
-                             f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]),
-                             f(p["c1"]), prev if p["c1"] != 0.0 else None, None, x_next, cur)
+            update = (f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]),
+                      f(p["c1"]), prev if p["c1"] != 0.0 else None, None, x_next, cur)
+            if v_pred:      # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, same launch
+                ops.sampler_step_pred(img, None, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V, f(p["alpha"]),
+                                      f(p["sigma"]), [], (1., 0., 0., 0.), *update)
+            else:
+                ops.sampler_step(img, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.), *update)
             img, x_next = x_next, img
             if callback:
                 callback(k)

@@ -4,7 +4,8 @@ WK/ldm/models/diffusion/plms.py:185-215 for the dict-conditioning form).
 
 Same class name, constructor and ``sample(...)`` keyword surface.  What changes is the execution:
   * the host loop only enqueues work: one UNet forward (a replayed hipGraph) and ONE fused
-    elementwise kernel per step (mdx_sampler_step_f32: CFG combine + Adams-Bashforth mix + x0/dir/x_prev),
+    elementwise kernel per step (mdx_sampler_step_f32: CFG combine + Adams-Bashforth mix + x0/dir/x_prev;
+    mdx_sampler_step_pred_f32 for a `parameterization: "v"` model, which adds the v -> eps conversion to the same launch),
     instead of ~15 separately dispatched MindSpore ops (plms.py:192-197, 218-226, 235-244);
   * the constant [2B,77,D] CFG context concat (plms.py:194) is built once, not every step, and its
     cross-attention K/V projections are cached inside the UNet;
@@ -224,7 +225,8 @@ class _SamplerBase:
             mask = torch.as_tensor(mask).to(device=dev, dtype=torch.float32)
             x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32)
         # per-step timestep vectors, fp32 on the device (the UNet's sinusoid takes float timesteps, util.py:111-131)
-        t_all = torch.as_tensor(np.ascontiguousarray(time_range), dtype=torch.float32, device=dev)
+        # (a fresh array: the flipped view of a ONE-step grid still counts as contiguous and keeps its negative stride)
+        t_all = torch.as_tensor(np.array(time_range, dtype=np.float32), device=dev)
         # the timestep-only part of the UNet (time_embed MLP + the ResBlock emb_layers, openaimodel.py:550-551,188) for
         # ALL steps in one batched pass; step i then hands row i to the UNet instead of recomputing it
         temb_all = None
@@ -258,11 +260,14 @@ class _SamplerBase:
         hook_e = torch.empty_like(img) if score_corrector is not None else None
         hook_x = torch.empty_like(img) if score_corrector is not None else None
         hook_p = torch.empty_like(img) if quantize_denoised else None
+        # a v-prediction model (SD 2.x 768-v): the step kernel converts the UNet's output to eps at the point (xm, tm) the model
+        # was evaluated at; everything after that -- history, pred_x0, x_prev -- is the eps path.  "eps" / "x0" keep the old entry.
+        v_pred = getattr(self.model, "parameterization", "eps") == "v"
 
         def step(x, eps_u, eps_c, index, coef, olds, e_out, x_out, p_out, xm=None, tm=None):
             """One get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] * olds[k-1], e_t = the
             CFG-combined model output (optionally written to e_out).  xm / tm: the image and timestep the model output
-            was evaluated at (what a score corrector is handed, plms.py:201)."""
+            was evaluated at (what a score corrector is handed, plms.py:201, and where a v output is converted to eps)."""
             a_t, a_prev = np.float32(alphas[index]), np.float32(alphas_prev[index])
             sigma_t = np.float32(sigmas[index])
             if score_corrector is not None:
@@ -297,9 +302,14 @@ class _SamplerBase:
                     noise = noise * keep / (1. - float(noise_dropout))
             if quantize_denoised and p_out is None:
                 p_out = hook_p
-            ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, olds, coef,
-                             np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
-                             np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t, noise, e_out, x_out, p_out)
+            update = (np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
+                      np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t, noise, e_out, x_out, p_out)
+            if v_pred:
+                ops.sampler_step_pred(x, xm, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V,
+                                      self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)],
+                                      olds, coef, *update)
+            else:
+                ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, olds, coef, *update)
             if quantize_denoised:
                 # pred_x0, _, *_ = first_stage_model.quantize(pred_x0) (plms.py:218-219); x_prev is linear in pred_x0
                 q = self.model.first_stage_model.quantize(p_out)[0]
