@@ -498,6 +498,29 @@ int mdx_sampler_step_pred_f32(const float* x, const float* x_model, const void* 
                               const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
                               int W, mdx_stream_t s);
 
+/* ---- the same fused update with guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are
+ * Flawed", section 3.4; `guidance_rescale` of the SD 2.x samplers).  Neither reference tree has it.  Per sample b, on the
+ * model outputs as the UNet wrote them (v or eps: before the conversion), N = C * H * W:
+ *   m    = out_u + cfg_scale * (out_c - out_u)
+ *   f[b] = guidance_rescale * std(out_c[b]) / std(m[b]) + (1 - guidance_rescale)      std unbiased (/ (N - 1)), fp32, from
+ *          the fp16 values as stored (first C of out_ld channels); f[b] = 1 when std(m[b]) is 0 or not finite
+ *   m'   = f[b] * m
+ * then e_t from m', e', pred_x0, x_prev exactly as mdx_sampler_step_pred_f32.  ONE launch: a workgroup per sample reduces the
+ * statistics (sums of v - K, K = the mean of the sample's first 64 values: not a one-pass E[x^2] - E[x]^2) and then applies
+ * the update.  factor_out: device [B] fp32, receives f; may be NULL.
+ * Aliasing as mdx_sampler_step_pred_f32: x_prev may alias x and / or x_model, the outputs (factor_out included) alias no
+ * other input; the statistics read only out_u / out_c.
+ * guidance_rescale == 0 or out_u == NULL (no guidance: f == 1) is the launch of mdx_sampler_step_pred_f32 with the same
+ * arguments, bit for bit, and factor_out is filled with 1.0 on the same stream.
+ * Refused before any launch: guidance_rescale outside [0, 1] or not finite, C * H * W < 2, and everything
+ * mdx_sampler_step_pred_f32 refuses.  coef4 is a HOST pointer to 4 floats (read at call time). */
+int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                                 float cfg_scale, int pred_type, float sqrt_at_model, float sqrt_one_minus_at_model,
+                                 const float* old1, const float* old2, const float* old3, const float* coef4,
+                                 float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
+                                 const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
+                                 float guidance_rescale, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

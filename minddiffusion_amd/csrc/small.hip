@@ -192,6 +192,134 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
     }
 }
 
+// ------------------------------------------------------------------ fused sampler update with guidance rescale
+// Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4: the CFG-combined model output m is
+// scaled by f[b] = phi * std(out_c[b]) / std(m[b]) + (1 - phi) before the step.  The statistics are per sample over C * HW,
+// so ONE workgroup owns a sample: pass 1 reads only the two model outputs (which no output may alias) in their own NHWC order,
+// pass 2 is sampler_step_kernel's statement sequence with m *= f after the combine.
+struct RescaleParams {
+    StepParams s;
+    float phi;
+    float* factor_out;
+};
+
+constexpr int RESCALE_THREADS = 1024;
+
+// Sums are taken of d = v - K with K = the mean of the sample's first 64 values (the same bits in every wave), so that
+// sum(d^2) - sum(d)^2 / N cancels nothing to speak of when the outputs sit on an offset far above their spread.
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(const RescaleParams rp) {
+    mdx_kernarg_touch<sizeof(RescaleParams)>();
+    const StepParams& p = rp.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW;      // per sample: the host refuses what does not fit 31 bits
+    const unsigned C = p.C, HW = p.HW;
+    const f16* ou = p.eps_u + (size_t)b * HW * p.eps_ld;
+    const f16* oc = p.eps_c + (size_t)b * HW * p.eps_ld;
+
+    // ---- pass 1: unbiased per-sample std of out_c and of m, in the outputs' own (pixel, channel) order
+    float kc, km;
+    {
+        const unsigned j = (unsigned)lane < N ? (unsigned)lane : N - 1;
+        const size_t ei = (size_t)(j / C) * p.eps_ld + j % C;
+        const float c = (float)oc[ei], u = (float)ou[ei];
+        kc = wave_sum(c) * (1.f / 64.f);
+        km = wave_sum(u + p.cfg_scale * (c - u)) * (1.f / 64.f);
+    }
+    float sc = 0.f, scc = 0.f, sm = 0.f, smm = 0.f;
+#pragma unroll 4
+    for (unsigned j = threadIdx.x; j < N; j += RESCALE_THREADS) {
+        const size_t ei = (size_t)(j / C) * p.eps_ld + j % C;
+        const float c = (float)oc[ei], u = (float)ou[ei];
+        const float dc = c - kc, dm = u + p.cfg_scale * (c - u) - km;
+        sc += dc;
+        scc += dc * dc;
+        sm += dm;
+        smm += dm * dm;
+    }
+    sc = wave_sum(sc);
+    scc = wave_sum(scc);
+    sm = wave_sum(sm);
+    smm = wave_sum(smm);
+    if (lane == 0) {
+        part[wave][0] = sc;
+        part[wave][1] = scc;
+        part[wave][2] = sm;
+        part[wave][3] = smm;
+    }
+    __syncthreads();
+    sc = scc = sm = smm = 0.f;
+#pragma unroll
+    for (int w = 0; w < RESCALE_THREADS / 64; ++w) {     // the same order in every thread: one f per sample, bit for bit
+        sc += part[w][0];
+        scc += part[w][1];
+        sm += part[w][2];
+        smm += part[w][3];
+    }
+    const float n = (float)N;
+    const float std_c = sqrtf(fmaxf(scc - sc * sc / n, 0.f) / (n - 1.f));
+    const float std_m = sqrtf(fmaxf(smm - sm * sm / n, 0.f) / (n - 1.f));
+    float f = 1.f;
+    if (std_m > 0.f && std_m <= 3.402823466e38f) f = rp.phi * std_c / std_m + (1.f - rp.phi);   // NaN fails both tests
+    if (rp.factor_out && threadIdx.x == 0) rp.factor_out[b] = f;
+
+    // ---- pass 2: the step (sampler_step_kernel's statements on m' = f m), U elements of a thread at a time: all their
+    // loads first, then the arithmetic and the stores.  The outputs may alias x / x_model only element for element, so a
+    // thread that has read its own U elements may store them; without the batching every trip of the loop waits out one
+    // memory latency behind the previous trip's stores (a workgroup has a sample to itself, so there is no one else to hide it).
+    constexpr int U = 4;
+    const size_t base = (size_t)b * N;
+    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * U) {
+        float m[U], xm[U], xv[U], o1[U], o2[U], o3[U], nz[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                const size_t i = base + j;
+                const unsigned c = j / HW;
+                const size_t ei = (size_t)(j - c * HW) * p.eps_ld + c;
+                const float eu = (float)ou[ei];
+                m[u] = eu + p.cfg_scale * ((float)oc[ei] - eu);
+                if constexpr (PRED == MDX_PRED_V) xm[u] = p.x_model[i];
+                xv[u] = p.x[i];
+                if (p.old1) o1[u] = p.old1[i];
+                if (p.old2) o2[u] = p.old2[i];
+                if (p.old3) o3[u] = p.old3[i];
+                if (p.noise) nz[u] = p.noise[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                const size_t i = base + j;
+                float e_t = m[u] * f;
+                // eps = a v + b x_m (dpm_solver.py:281-284).  This statement and x_prev below are spelled in the form
+                // sampler_step_kernel's expressions compile to (here: the product with x_m rounded, the one with m' fused;
+                // below: both products rounded, then added), so that with f == 1 the two kernels agree to the bit
+                // (test_constant_outputs_give_factor_one holds them to it).
+                if constexpr (PRED == MDX_PRED_V) e_t = __builtin_fmaf(p.am, e_t, p.bm * xm[u]);
+                if (p.e_t_out) p.e_t_out[i] = e_t;
+                float ep = p.c0 * e_t;
+                if (p.old1) ep += p.c1 * o1[u];
+                if (p.old2) ep += p.c2 * o2[u];
+                if (p.old3) ep += p.c3 * o3[u];
+                const float px0 = (xv[u] - p.sqrt_one_minus_at * ep) / p.sqrt_at;
+                float xp;
+                {
+#pragma clang fp contract(off)
+                    xp = p.sqrt_a_prev * px0 + p.dir_coef * ep;
+                }
+                if (p.noise) xp += p.sigma * nz[u];
+                if (p.pred_x0) p.pred_x0[i] = px0;
+                p.x_prev[i] = xp;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ MFMA layout probe
 __global__ void probe_mfma_kernel(const f16* a, const f16* b, float* c) {
     const int lane = threadIdx.x;
@@ -265,20 +393,21 @@ extern "C" int mdx_dense_small_f32(const float* x, int x_ld, const void* w, cons
     return MDX_OK;
 }
 
-// One host body for both entries; `fn` names the entry in its messages.
-static int sampler_step_launch(const char* fn, const float* x, const float* x_model, const void* out_u, const void* out_c,
-                               int out_ld, float cfg_scale, int pred_type, float am, float bm, const float* old1,
-                               const float* old2, const float* old3, const float* coef4, float sqrt_at,
+// One host body for all entries; `fn` names the entry in its messages.  sampler_step_params refuses and fills,
+// sampler_step_run launches sampler_step_kernel on filled parameters, sampler_step_launch does both.
+static int sampler_step_params(StepParams& p, const char* fn, const float* x, const float* x_model, const void* out_u,
+                               const void* out_c, int out_ld, float cfg_scale, int pred_type, float am, float bm,
+                               const float* old1, const float* old2, const float* old3, const float* coef4, float sqrt_at,
                                float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
                                const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
-                               int W, mdx_stream_t s) {
+                               int W) {
     MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
     MDX_REQUIRE(x && out_c && coef4 && x_prev, "%s: null pointer", fn);
     MDX_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && out_ld >= C, "%s: bad extents", fn);
     MDX_REQUIRE(sigma == 0.f || noise, "%s: sigma != 0 needs a noise tensor", fn);
     MDX_REQUIRE((coef4[1] == 0.f || old1) && (coef4[2] == 0.f || old2) && (coef4[3] == 0.f || old3),
                 "%s: non-zero multistep coefficient without its eps history", fn);
-    StepParams p{};
+    p = StepParams{};
     p.x = x;
     p.x_model = x_model ? x_model : x;
     p.eps_u = (const f16*)out_u;
@@ -306,13 +435,31 @@ static int sampler_step_launch(const char* fn, const float* x, const float* x_mo
     p.sigma = sigma;
     p.am = am;
     p.bm = bm;
-    const dim3 grid(grid_for((size_t)B * C * H * W));
+    return MDX_OK;
+}
+
+static int sampler_step_run(const char* fn, const StepParams& p, int pred_type, mdx_stream_t s) {
+    const dim3 grid(grid_for((size_t)p.B * p.C * p.HW));
     if (pred_type == MDX_PRED_V)
         hipLaunchKernelGGL(sampler_step_kernel<MDX_PRED_V>, grid, dim3(256), 0, (hipStream_t)s, p);
     else
         hipLaunchKernelGGL(sampler_step_kernel<MDX_PRED_EPS>, grid, dim3(256), 0, (hipStream_t)s, p);
     MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
+}
+
+static int sampler_step_launch(const char* fn, const float* x, const float* x_model, const void* out_u, const void* out_c,
+                               int out_ld, float cfg_scale, int pred_type, float am, float bm, const float* old1,
+                               const float* old2, const float* old3, const float* coef4, float sqrt_at,
+                               float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
+                               const float* noise, float* e_t_out, float* x_prev, float* pred_x0, int B, int C, int H,
+                               int W, mdx_stream_t s) {
+    StepParams p;
+    const int rc = sampler_step_params(p, fn, x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, am, bm, old1, old2,
+                                       old3, coef4, sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise,
+                                       e_t_out, x_prev, pred_x0, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    return sampler_step_run(fn, p, pred_type, s);
 }
 
 extern "C" int mdx_sampler_step_f32(const float* x, const void* eps_u, const void* eps_c, int eps_ld, float cfg_scale,
@@ -336,6 +483,43 @@ extern "C" int mdx_sampler_step_pred_f32(const float* x, const float* x_model, c
                                sqrt_at_model, sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at,
                                sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev, pred_x0, B, C, H, W,
                                s);
+}
+
+extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
+                                            int out_ld, float cfg_scale, int pred_type, float sqrt_at_model,
+                                            float sqrt_one_minus_at_model, const float* old1, const float* old2,
+                                            const float* old3, const float* coef4, float sqrt_at, float sqrt_one_minus_at,
+                                            float sqrt_a_prev, float dir_coef, float sigma, const float* noise,
+                                            float* e_t_out, float* x_prev, float* pred_x0, float guidance_rescale,
+                                            float* factor_out, int B, int C, int H, int W, mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_rescale_f32";
+    RescaleParams rp;
+    const int rc = sampler_step_params(rp.s, fn, x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, sqrt_at_model,
+                                       sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at, sqrt_one_minus_at,
+                                       sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev, pred_x0, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "%s: guidance_rescale %g is not in [0, 1]", fn,
+                (double)guidance_rescale);
+    MDX_REQUIRE((size_t)C * H * W >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
+    MDX_REQUIRE((size_t)C * H * W <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
+    if (guidance_rescale == 0.f || !out_u) {      // f == 1: the launch of mdx_sampler_step_pred_f32, bit for bit
+        const int rc1 = sampler_step_run(fn, rp.s, pred_type, s);
+        if (rc1 != MDX_OK || !factor_out) return rc1;
+        const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)factor_out, 0x3f800000 /* 1.0f */, (size_t)B, (hipStream_t)s);
+        if (e != hipSuccess) {
+            mdx_set_error("%s: factor_out fill failed: %s", fn, hipGetErrorString(e));
+            return MDX_E_HIP;
+        }
+        return MDX_OK;
+    }
+    rp.phi = guidance_rescale;
+    rp.factor_out = factor_out;
+    if (pred_type == MDX_PRED_V)
+        hipLaunchKernelGGL(sampler_step_rescale_kernel<MDX_PRED_V>, dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, rp);
+    else
+        hipLaunchKernelGGL(sampler_step_rescale_kernel<MDX_PRED_EPS>, dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, rp);
+    MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
 }
 
 extern "C" int mdx_probe_mfma_32x32x16_f16(const void* a, const void* b, float* c, mdx_stream_t s) {

@@ -12,6 +12,8 @@ is exactly that kernel's  sqrt_a_prev * pred_x0 + dir_coef * e' + sigma * noise 
     sigma = c1, noise = x0_prev  -- so no extra elementwise passes and no extra kernel.
 A `parameterization: "v"` model goes through ``mdx_sampler_step_pred_f32``, which first converts the CFG-combined v to
 e = alpha_s v + sigma_s x (the reference's model_wrapper for model_type "v", dpm_solver.py:281-284) in the same launch.
+`guidance_rescale` != 0 with guidance on goes through ``mdx_sampler_step_rescale_f32``: the CFG-combined output (eps or v)
+is rescaled per sample to the conditional output's std in the same launch (not in the reference).
 Differences from the reference, both on the fp32 side of its fp16 arithmetic: the time grid and the schedule scalars
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
@@ -23,7 +25,7 @@ import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..plms import _first_tensor
+from ..plms import _first_tensor, check_guidance_rescale
 from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
 
 
@@ -48,7 +50,8 @@ class DPMSolverSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, **kwargs):
+               unconditional_conditioning=None, guidance_rescale=0., **kwargs):
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if conditioning is None:
             raise MdxError("DPMSolverSampler: conditioning is required (classifier-free guidance on a text-conditional UNet)")
         cond = _first_tensor(conditioning)
@@ -100,7 +103,11 @@ class DPMSolverSampler:
             f = np.float32
             update = (f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]),
                       f(p["c1"]), prev if p["c1"] != 0.0 else None, None, x_next, cur)
-            if v_pred:      # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, same launch
+            if use_cfg and guidance_rescale != 0.:
+                ops.sampler_step_rescale(img, None, eps_u, eps_c, eps_c.shape[-1], scale,
+                                         ops.PRED_V if v_pred else ops.PRED_EPS, f(p["alpha"]) if v_pred else 1.,
+                                         f(p["sigma"]) if v_pred else 0., [], (1., 0., 0., 0.), *update, guidance_rescale)
+            elif v_pred:    # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, same launch
                 ops.sampler_step_pred(img, None, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V, f(p["alpha"]),
                                       f(p["sigma"]), [], (1., 0., 0., 0.), *update)
             else:

@@ -5,7 +5,9 @@ WK/ldm/models/diffusion/plms.py:185-215 for the dict-conditioning form).
 Same class name, constructor and ``sample(...)`` keyword surface.  What changes is the execution:
   * the host loop only enqueues work: one UNet forward (a replayed hipGraph) and ONE fused
     elementwise kernel per step (mdx_sampler_step_f32: CFG combine + Adams-Bashforth mix + x0/dir/x_prev;
-    mdx_sampler_step_pred_f32 for a `parameterization: "v"` model, which adds the v -> eps conversion to the same launch),
+    mdx_sampler_step_pred_f32 for a `parameterization: "v"` model, which adds the v -> eps conversion to the same launch;
+    mdx_sampler_step_rescale_f32 when `guidance_rescale` != 0, which adds the per-sample std rescale of the CFG-combined
+    output to the same launch),
     instead of ~15 separately dispatched MindSpore ops (plms.py:192-197, 218-226, 235-244);
   * the constant [2B,77,D] CFG context concat (plms.py:194) is built once, not every step, and its
     cross-attention K/V projections are cached inside the UNet;
@@ -27,6 +29,15 @@ def _first_tensor(c):
     while isinstance(c, (dict, list, tuple)):
         c = c[list(c.keys())[0]] if isinstance(c, dict) else c[0]
     return c
+
+
+def check_guidance_rescale(value):
+    """`guidance_rescale` (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4) as a float in
+    [0, 1]; anything else, NaN included, is a ValueError."""
+    phi = float(value)
+    if not 0. <= phi <= 1.:
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {value!r}")
+    return phi
 
 
 class _SamplerBase:
@@ -74,7 +85,8 @@ class _SamplerBase:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
+               unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., **kwargs):
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if conditioning is not None:
             cbs = _first_tensor(conditioning).shape[0]
             if cbs != batch_size:
@@ -96,7 +108,7 @@ class _SamplerBase:
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  blend_noises=kwargs.get("blend_noises"))
+                                  blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale)
 
     # ---- model call: prefer the NHWC fast path of our LatentDiffusion; any object with the reference's
     #      apply_model(x, t, cond) -> NCHW eps still works (its output is re-laid-out by a HIP kernel).
@@ -116,7 +128,8 @@ class _SamplerBase:
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None):
+                      dropout_masks=None, step_noises=None, guidance_rescale=0.):
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if mask is not None and x0 is None:
             raise ValueError("mask blending needs x0 (plms.py:154)")
         # quantize_x0 / score_corrector (plms.py:199-201, 218-219) call into caller-supplied objects (a first stage with
@@ -263,6 +276,9 @@ class _SamplerBase:
         # a v-prediction model (SD 2.x 768-v): the step kernel converts the UNet's output to eps at the point (xm, tm) the model
         # was evaluated at; everything after that -- history, pred_x0, x_prev -- is the eps path.  "eps" / "x0" keep the old entry.
         v_pred = getattr(self.model, "parameterization", "eps") == "v"
+        # guidance rescale: the CFG-combined output of every model evaluation is pulled back to the conditional output's
+        # per-sample std inside the step launch; without guidance (or at 0) the calls below are the ones always made
+        rescale = use_cfg and guidance_rescale != 0.
 
         def step(x, eps_u, eps_c, index, coef, olds, e_out, x_out, p_out, xm=None, tm=None):
             """One get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] * olds[k-1], e_t = the
@@ -273,8 +289,14 @@ class _SamplerBase:
             if score_corrector is not None:
                 # e_t leaves the fused kernel (pass 1: CFG combine only), goes through the caller's modify_score, and
                 # re-enters as a single NHWC fp16 model output (pass 2: multistep mix + update)
-                ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.), 1., 0., 1., 0., 0., None,
-                                 hook_e, hook_x, None)
+                # (a corrector implies an eps model -- asserted above -- so hook_e holds eps and PRED_EPS is the whole story)
+                if rescale:     # the rescale belongs to the combine that produces e_t, so to this pass
+                    ops.sampler_step_rescale(x, None, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_EPS, 1., 0., [],
+                                             (1., 0., 0., 0.), 1., 0., 1., 0., 0., None, hook_e, hook_x, None,
+                                             guidance_rescale)
+                else:
+                    ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.), 1., 0., 1., 0., 0.,
+                                     None, hook_e, hook_x, None)
                 tvec = torch.full((b,), int(tm), device=dev, dtype=torch.long)
                 e_mod = score_corrector.modify_score(self.model, hook_e, x if xm is None else xm, tvec, cond,
                                                      **corrector_kwargs)
@@ -304,7 +326,12 @@ class _SamplerBase:
                 p_out = hook_p
             update = (np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
                       np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t, noise, e_out, x_out, p_out)
-            if v_pred:
+            if rescale and eps_u is not None:
+                am, bm = ((self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)]) if v_pred
+                          else (1., 0.))
+                ops.sampler_step_rescale(x, xm, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V if v_pred else ops.PRED_EPS,
+                                         am, bm, olds, coef, *update, guidance_rescale)
+            elif v_pred:
                 ops.sampler_step_pred(x, xm, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V,
                                       self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)],
                                       olds, coef, *update)

@@ -746,6 +746,27 @@ def sampler_step_pred(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, sq
         "mdx_sampler_step_pred_f32")
 
 
+def sampler_step_rescale(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, sqrt_at_model, sqrt_one_minus_at_model,
+                         olds, coef, sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev,
+                         pred_x0, guidance_rescale, factor_out=None):
+    """sampler_step_pred with guidance rescale: the CFG-combined model output of sample b is scaled by
+    f[b] = guidance_rescale * std(out_c[b]) / std(m[b]) + (1 - guidance_rescale) inside the same launch (see
+    include/mdx.h).  factor_out: optional [B] fp32 tensor that receives f."""
+    B, C, H, W = x.shape
+    c4 = (ctypes.c_float * 4)(*[float(v) for v in coef])
+    o = list(olds) + [None] * (3 - len(olds))
+    if factor_out is not None:
+        _chk(factor_out, f32, "factor_out")
+        if factor_out.numel() < B:
+            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    _lib.check(_lib.load().mdx_sampler_step_rescale_f32(
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_ld), float(cfg_scale), int(pred_type),
+        float(sqrt_at_model), float(sqrt_one_minus_at_model), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
+        ctypes.cast(c4, ctypes.c_void_p), float(sqrt_at), float(sqrt_one_minus_at), float(sqrt_a_prev), float(dir_coef),
+        float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), float(guidance_rescale), _ptr(factor_out),
+        B, C, H, W, _stream()), "mdx_sampler_step_rescale_f32")
+
+
 def probe_mfma(a, b):
     c = torch.empty((64, 16), dtype=f32, device=a.device)
     _lib.check(_lib.load().mdx_probe_mfma_32x32x16_f16(_ptr(a), _ptr(b), _ptr(c), _stream()), "mdx_probe_mfma")

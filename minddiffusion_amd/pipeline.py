@@ -17,7 +17,7 @@ import torch
 from . import distributed as D
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
-from .ldm.models.diffusion.plms import PLMSSampler
+from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
 
 
 class DiffusionPipeline:
@@ -40,9 +40,12 @@ class DiffusionPipeline:
         return torch.from_numpy(np.random.RandomState(seed).randn(batch, *shape).astype(np.float32))
 
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
-                 decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False):
+                 decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
+                 guidance_rescale=0.0):
         """Multi-rank runs: every rank calls with the same `prompts` list (or the same `batch_size` when rank 0 passes
-        precomputed (c, uc) tensors); only rank 0's c / uc / x_T are used, the other ranks may pass None."""
+        precomputed (c, uc) tensors); only rank 0's c / uc / x_T are used, the other ranks may pass None.
+        guidance_rescale in [0, 1]: the samplers' keyword (CFG rescale for v-prediction checkpoints), every rank the same."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         rank, n = D.world()
         shape = [4, H // 8, W // 8]                                   # txt2img.py:253
         if prompts is not None and rank == 0:
@@ -73,10 +76,13 @@ class DiffusionPipeline:
             if uc is not None and uc.shape[0] == 1 and B > 1:
                 uc = uc.expand(B, -1, -1).contiguous()
             x_T = x_T.to(self.device)
+        # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W
         local_b = int(c.shape[0])
+        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}   # (a caller's own sampler object)
         samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=local_b, shape=shape, verbose=False,
                                              unconditional_guidance_scale=scale, unconditional_conditioning=uc,
-                                             eta=eta, x_T=x_T, callback=callback, img_callback=img_callback)
+                                             eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
+                                             **rescale_kw)
         if decode:
             x = self.model.decode_first_stage(samples)                # txt2img.py:265-266
             samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)

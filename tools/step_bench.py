@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Launch cost of the fused sampler step with and without guidance rescale, at the latent shapes the samplers run.
+
+  pred     mdx_sampler_step_pred_f32      (MDX_PRED_V, guidance on): the flat grid-stride kernel
+  rescale  mdx_sampler_step_rescale_f32   (same arguments, guidance_rescale = 0.7): one workgroup per sample, statistics pass
+           in front of the update
+
+Both in the steady state of a PLMS run (order 3: three eps histories read, e_t / pred_x0 / x_prev written).  One process:
+`--launches` launches of each entry are captured into a hipGraph (so the host's enqueue rate is not what is measured), the two
+graphs are replayed alternately `--rounds` times after a warm-up, each replay between two hip events.  Reported per launch:
+median over rounds of (replay time / launches), and rescale - pred, which is what a step gains by turning the rescale on.
+Prints one JSON line (and writes --out)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = ((1, 4, 96, 96), (2, 4, 64, 64), (8, 4, 64, 64))      # 768^2 batch 1, 512^2 batch 2, 512^2 batch 8
+
+
+def bench_shape(shape, launches, rounds, warmup):
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    B, C, H, W = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    r32 = lambda: torch.randn(shape, device=dev, generator=g)
+    x, olds = r32(), [r32(), r32(), r32()]
+    out = torch.randn((2 * B, H * W, 8), device=dev, generator=g).half()       # [uncond; cond], NHWC, ld = 8
+    out_u, out_c = out[:B], out[B:]
+    e_out, x_prev, p_out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    coef = (55 / 24, -59 / 24, 37 / 24, -9 / 24)
+    args = (x, None, out_u, out_c, 8, 7.5, ops.PRED_V, 0.8, 0.6, olds, coef, 0.55, 0.83, 0.6, 0.8, 0.0, None, e_out, x_prev,
+            p_out)
+    entries = {"pred": lambda: ops.sampler_step_pred(*args), "rescale": lambda: ops.sampler_step_rescale(*args, 0.7)}
+    graphs = {}
+    for name, fn in entries.items():
+        fn()
+        torch.cuda.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name]):
+            for _ in range(launches):
+                fn()
+    for _ in range(warmup):
+        for gr in graphs.values():
+            gr.replay()
+    torch.cuda.synchronize()
+    us = {name: [] for name in graphs}
+    for _ in range(rounds):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            gr.replay()
+            t1.record()
+            t1.synchronize()
+            us[name].append(t0.elapsed_time(t1) * 1e3 / launches)
+    res = {"shape": list(shape)}
+    for name, v in us.items():
+        res[name + "_us"] = round(statistics.median(v), 3)
+        res[name + "_us_min"] = round(min(v), 3)
+        res[name + "_us_max"] = round(max(v), 3)
+    res["extra_us"] = round(res["rescale_us"] - res["pred_us"], 3)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--launches", type=int, default=300)
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("step_bench: needs a GPU")
+    res = {"launches": a.launches, "rounds": a.rounds,
+           "shapes": [bench_shape(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
