@@ -21,13 +21,12 @@ import numpy as np
 import pytest
 import torch
 
+import _guard as G
 import _norm_regimes as R
 from _util import check, h16
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 4096          # sentinel elements on either side of an output
-SENT = -1234.0      # fp16-exact
 
 
 @pytest.fixture(scope="module")
@@ -45,17 +44,13 @@ def dev32(a):
 
 
 def guarded(shape):
-    """(buffer, view): an fp16 output of `shape` in the middle of a sentinel-filled buffer (the output starts as sentinel too, so
-    an element the launch leaves out shows up as an error)."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * PAD,), SENT, dtype=torch.float16, device=DEV)
-    return buf, buf[PAD:PAD + n].view(shape)
+    """(buffer, view): an fp16 output of `shape` in the middle of a sentinel-filled buffer (tests/_guard.py; the output starts as
+    sentinel too, so an element the launch leaves out shows up as an error)."""
+    return G.guarded(shape, torch.float16, device=DEV)
 
 
-def assert_guard(buf, name):
-    torch.cuda.synchronize()
-    assert bool((buf[:PAD] == SENT).all()), f"{name}: wrote in front of its output"
-    assert bool((buf[-PAD:] == SENT).all()), f"{name}: wrote behind its output"
+def assert_guard(buf, out, name):
+    G.assert_footprint(buf, out, name)
 
 
 @contextlib.contextmanager
@@ -187,7 +182,7 @@ def test_groupnorm_forms(ops, case, regime):
                     ops.groupnorm_scaleshift(x1, x2, gd, bd, mod[:, :C], mod[:, C:], 2 * C, eps, act, out=out)
                 else:
                     ops.groupnorm_colstats(x1, cs1, nrb1, x2, cs2, nrb2, gd, bd, eps, act, out=out)
-                assert_guard(buf, name)
+                assert_guard(buf, out, name)
                 check_gn(name, regime, x, out, g, b, eps, groups, act, scale, shift, max_abs=3e-2 if kind == "film" else 2e-2)
 
 
@@ -217,7 +212,7 @@ def test_groupnorm_from_splitk_slabs(ops, H, W, splitk, regime):
             ops.gemm_run(d)
             buf, out = guarded((B, HW, C))
             ops.groupnorm_from_splitk(d, gd, bd, eps, act, out, groups)
-            assert_guard(buf, name)
+            assert_guard(buf, out, name)
             assert torch.equal(conv_out, a), f"{name}: the identity conv's output is not its input"
             check_gn(name, regime, x, out, g, b, eps, groups, act)
 
@@ -266,7 +261,7 @@ def test_layernorm_regimes(ops, C, regime):
             name = f"regime_ln_{rows}x{C}_{regime}_eps{eps:g}"
             buf, out = guarded((rows, C))
             ops.layernorm(xd, gd, bd, eps, out=out)
-            assert_guard(buf, name)
+            assert_guard(buf, out, name)
             got = out.float().cpu().numpy()
             check(name, got, R.ln_ref(x, g, b, eps), rel_l2=1e-3, max_abs=None if regime == "spike" else 2e-2)
             if regime == "const":
