@@ -587,6 +587,28 @@ int mdx_softmax_rows_f16(void* x, long ld, int rows, int cols, float scale, mdx_
 int mdx_vae_gaussian_sample_f32(const void* moments, int ld, const float* noise, float* out, int B, int zc, int HW,
                                 mdx_stream_t s);
 
+/* ---- img2img: the forward-process sample and its fusion onto the encoder's posterior sample (csrc/qsample.hip).
+ * q = a * x0 + b * noise (ddpm.py:197-200: a = sqrt(alphas_cumprod[t]), b = sqrt(1 - alphas_cumprod[t])), computed as
+ * fma(a, x0, b * noise).  mask == NULL: out = q.  Otherwise the running latent keeps its unmasked part (plms.py:153-157):
+ *   out = m * q + (1 - m) * img,   m = mask[b][mask_c == 1 ? 0 : c][p]      (mask_c is 1 or C)
+ * x0, noise, img, out: NCHW fp32 [B][C][HW]; mask NCHW fp32 [B][mask_c][HW].  Where m == 0 out is img and where m == 1 out is
+ * q, bit for bit; a = 1, b = 0 without a mask returns x0.  out may alias img element for element (out == img) and nothing
+ * else.  16-byte accesses when HW % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise.
+ * Refused before any launch: null x0 / noise / out, mask without img, mask_c not in {1, C}, non-positive extents, an out
+ * that overlaps an input other than img == out. */
+int mdx_q_sample_f32(const float* x0, const float* noise, float a, float b, const float* mask, int mask_c,
+                     const float* img, float* out, int B, int C, int HW, mdx_stream_t s);
+
+/* Encoder moments -> start latent of an img2img run, one launch: with moments as mdx_vae_gaussian_sample_f32 takes them,
+ *   z  = mean + exp(0.5 * clip(logvar, -30, 20)) * post_noise      (post_noise NULL: the mode, z = mean)
+ *   z0 = scale_factor * z                                           (get_first_stage_encoding)
+ *   xt = a * z0 + b * noise                                         (the q-sample statement of mdx_q_sample_f32)
+ * post_noise, noise, z0_out, xt_out: NCHW fp32 [B][zc][HW].  Either output may be NULL, not both; xt_out needs noise.
+ * scale_factor = 1 makes z0_out mdx_vae_gaussian_sample_f32's output and xt_out is mdx_q_sample_f32(z0_out, noise, a, b),
+ * both bit for bit. */
+int mdx_vae_encode_noised_f32(const void* moments, int ld, const float* post_noise, float scale_factor, float a, float b,
+                              const float* noise, float* z0_out, float* xt_out, int B, int zc, int HW, mdx_stream_t s);
+
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
  *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)

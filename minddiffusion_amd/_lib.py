@@ -153,6 +153,10 @@ SIGNATURES = {
     "mdx_srgan_conv_in_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_srgan_conv_out_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_vae_gaussian_sample_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_q_sample_f32": (c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_void_p]),
+    "mdx_vae_encode_noised_f32": (c_int, [c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_int, c_int, c_void_p]),
     "mdx_softmax_rows_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_void_p]),
     "mdx_probe_mfma_32x32x16_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mdx_probe_mfma_16x16x32_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -90,3 +90,25 @@ class AutoencoderKL:
         if noise is not None:
             noise = noise.to(device=mom.device, dtype=torch.float32).contiguous()
         return ops.vae_gaussian_sample(mom, zc, noise if sample else None, out)
+
+    def latent_shape(self, image_shape):
+        """[B, embed_dim, h, w] of encode()'s result for images [B, 3, H, W]: the encoder plan's own output size (the
+        downsampling factor is 2^(levels - 1): 8 for the SD VAE, 2 for the tiny test VAE)."""
+        B, _, H, W = image_shape
+        h, w = self.encoder._plan(B, H, W).out_hw
+        return (B, self.embed_dim, h, w)
+
+    def encode_noised(self, x, scale_factor, a, b, noise, post_noise=None, sample=True):
+        """img2img start: the encoder, then ONE launch (mdx_vae_encode_noised_f32) that draws the posterior sample as encode()
+        does, scales it (z0 = scale_factor * z, LatentDiffusion.get_first_stage_encoding) and noises it
+        (x_t = a * z0 + b * noise, the samplers' stochastic_encode).  noise: N(0, 1) of latent_shape(x.shape); post_noise /
+        sample: encode()'s `noise` / `sample`.  Returns (z0, x_t), fresh tensors."""
+        mom = self.encoder(x)
+        shape = self.latent_shape(x.shape)
+        z0 = torch.empty(shape, dtype=torch.float32, device=mom.device)
+        x_t = torch.empty_like(z0)
+        if sample and post_noise is None:
+            post_noise = torch.randn(shape, device=mom.device, dtype=torch.float32, generator=self.generator)
+        to_dev = lambda t: torch.as_tensor(t).to(device=mom.device, dtype=torch.float32).contiguous()
+        return ops.vae_encode_noised(mom, self.embed_dim, to_dev(post_noise) if sample else None, scale_factor, a, b,
+                                     to_dev(noise), z0, x_t)

@@ -62,8 +62,9 @@ def time_uniform_steps(ns, steps, t_start=None, t_end=None):
     return np.linspace(t_T, t_0, steps + 1)
 
 
-def multistep_2m_plan(ns, steps, order=2, lower_order_final=True):
+def multistep_2m_plan(ns, steps, order=2, lower_order_final=True, t_start=None):
     """The S updates of DPM_Solver.sample(method='multistep', order=2, predict_x0=True) :1044-1075 as scalars.
+    t_start: DPM_Solver.sample's own option (:958-1041) -- the grid runs from t_start instead of T (img2img).
 
     Step k (k = 0 .. S-1) evaluates the model at timesteps[k] (x0_k = (x - sigma_k eps) / alpha_k) and moves x from
     timesteps[k] to timesteps[k+1]:
@@ -73,7 +74,7 @@ def multistep_2m_plan(ns, steps, order=2, lower_order_final=True):
     with h = lambda_t - lambda_s, r0 = (lambda_s - lambda_{s-1}) / h.  S model evaluations in total (the last
     update's target needs none, :1073-1075)."""
     assert order in (1, 2) and steps >= order
-    ts = time_uniform_steps(ns, steps)
+    ts = time_uniform_steps(ns, steps, t_start=t_start)
     lam, alpha, sigma = ns.marginal_lambda(ts), ns.marginal_alpha(ts), ns.marginal_std(ts)
     plan = []
     for k in range(steps):

@@ -25,7 +25,7 @@ import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..plms import _first_tensor, check_guidance_rescale
+from ..plms import _first_tensor, check_guidance_rescale, noised_latent
 from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
 
 
@@ -37,6 +37,25 @@ class DPMSolverSampler:
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
+
+    # ---- img2img: a run that starts at a continuous time t_start below T (dpm_solver.py:958-1075, `t_start`)
+    def _check_t_start(self, t_start):
+        t, n = float(t_start), self.alphas_cumprod.shape[0]
+        if not 1.0 / n < t <= 1.0:
+            raise ValueError(f"t_start must be a continuous time in (1/{n}, 1], got {t_start!r}")
+        return t
+
+    def q_coefficients(self, t_start):
+        """(marginal_alpha, marginal_std) at the continuous time t_start."""
+        ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
+        t = self._check_t_start(t_start)
+        return float(ns.marginal_alpha(t)), float(ns.marginal_std(t))
+
+    def stochastic_encode(self, x0, t_start, noise=None):
+        """x0 noised to the continuous time t_start: marginal_alpha(t_start) x0 + marginal_std(t_start) noise.  One ops.q_sample
+        launch; a fresh tensor.  `noise` None: drawn from the sampler's generator."""
+        a, b = self.q_coefficients(t_start)
+        return noised_latent(x0, a, b, noise, self.generator)
 
     def _eps_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
         if hasattr(self.model, "apply_model_nhwc"):
@@ -50,8 +69,13 @@ class DPMSolverSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, guidance_rescale=0., **kwargs):
+               unconditional_conditioning=None, guidance_rescale=0., t_start=None, **kwargs):
+        """t_start: a continuous time in (1 / N, T] -- the S evaluations then cover [t_start, 1 / N] instead of [T, 1 / N], from
+        x_T = stochastic_encode(., t_start) (the reference's DPM_Solver.sample(t_start=), dpm_solver.py:958-1075).  S == 1 is a
+        single first-order update."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if t_start is not None:
+            t_start = self._check_t_start(t_start)
         if conditioning is None:
             raise MdxError("DPMSolverSampler: conditioning is required (classifier-free guidance on a text-conditional UNet)")
         cond = _first_tensor(conditioning)
@@ -81,7 +105,7 @@ class DPMSolverSampler:
         nb = 2 * b if use_cfg else b
 
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
-        plan = multistep_2m_plan(ns, S, order=2, lower_order_final=True)
+        plan = multistep_2m_plan(ns, S, order=2 if S >= 2 else 1, lower_order_final=True, t_start=t_start)
         t_all = torch.tensor([p["t_input"] for p in plan], dtype=torch.float32, device=dev)
         # timestep-only part of the UNet for all S (fractional) timesteps in one batched pass (see PLMSSampler)
         temb_all = None

@@ -14,6 +14,8 @@ Same class name, constructor and ``sample(...)`` keyword surface.  What changes 
   * per-step scalars are host floats (no `ms.numpy.full` tensors, plms.py:212-215).
 Results are identical in structure to the reference (S+1 UNet calls for PLMS, intermediates dict,
 callbacks once per step).
+img2img (not in the reference): ``stochastic_encode(x0, t_enc)`` + ``decode(x_t, cond, t_start)`` run the last t_start steps
+of the schedule through the same loop; the per-step mask blend of that path is one mdx_q_sample_f32 launch.
 """
 import os
 
@@ -38,6 +40,18 @@ def check_guidance_rescale(value):
     if not 0. <= phi <= 1.:
         raise ValueError(f"guidance_rescale must be in [0, 1], got {value!r}")
     return phi
+
+
+def noised_latent(x0, a, b, noise, generator):
+    """stochastic_encode of every sampler: a * x0 + b * noise as one ops.q_sample launch into a fresh tensor; `noise` None is
+    drawn from `generator`."""
+    if not (isinstance(x0, torch.Tensor) and x0.is_cuda):
+        raise MdxError("stochastic_encode: x0 must be a CUDA(HIP) tensor [B, C, H, W]")
+    x0 = x0.to(torch.float32).contiguous()
+    if noise is None:
+        noise = torch.randn(x0.shape, device=x0.device, dtype=torch.float32, generator=generator)
+    noise = torch.as_tensor(noise).to(device=x0.device, dtype=torch.float32).contiguous()
+    return ops.q_sample(x0, noise, a, b)
 
 
 class _SamplerBase:
@@ -110,6 +124,59 @@ class _SamplerBase:
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
                                   blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale)
 
+    # ---- img2img: upstream LDM's DDIMSampler.stochastic_encode / decode (neither reference tree has them).
+    # t_enc / t_start count the model evaluations that REMAIN (1 .. S; PLMS spends one more on its first step): the partial run
+    # walks grid indices t_enc - 1 ... 0, and stochastic_encode noises to the level of the first step that will run,
+    # ddim_alphas[t_enc - 1] = alphas_cumprod[ddim_timesteps[t_enc - 1]].  Upstream noises to index t_enc and then starts
+    # denoising at t_enc - 1 -- one grid point of noise more than the run removes, and no way to say strength = 1 (index S does
+    # not exist); here t_enc == S is the full run from x_T's own level.
+    def _need_schedule(self, what):
+        if not hasattr(self, "ddim_timesteps"):
+            raise MdxError(f"{type(self).__name__}.{what}: call make_schedule(ddim_num_steps, ddim_eta) first")
+
+    @staticmethod
+    def _check_t_start(t_start, n):
+        if isinstance(t_start, bool) or int(t_start) != t_start or not 1 <= int(t_start) <= n:
+            raise ValueError(f"t_start / t_enc must be an integer in [1, {n}] (the model evaluations that remain), got {t_start!r}")
+        return int(t_start)
+
+    def q_coefficients(self, t_enc, use_original_steps=False):
+        """(sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)) at the first step a decode(t_start=t_enc) runs."""
+        self._need_schedule("stochastic_encode")
+        if use_original_steps:
+            t = self._check_t_start(t_enc, self.ddpm_num_timesteps) - 1
+        else:
+            t = int(self.ddim_timesteps[self._check_t_start(t_enc, self.ddim_timesteps.shape[0]) - 1])
+        return self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t]
+
+    def stochastic_encode(self, x0, t_enc, use_original_steps=False, noise=None):
+        """x0 noised to where decode(t_start=t_enc) starts: sqrt(a) x0 + sqrt(1 - a) noise, a = ddim_alphas[t_enc - 1] (see the
+        note above for the difference from upstream LDM, which uses index t_enc).  One ops.q_sample launch; a fresh tensor.
+        `noise` None: drawn from the sampler's generator."""
+        a, b = self.q_coefficients(t_enc, use_original_steps)
+        return noised_latent(x0, a, b, noise, self.generator)
+
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
+               use_original_steps=False, callback=None, img_callback=None, mask=None, x0=None, guidance_rescale=0.,
+               log_every_t=100, **test_injection_kwargs):
+        """The last t_start steps of the schedule make_schedule() set up (its eta included), from x_latent =
+        stochastic_encode(., t_start): plms_sampling's loop on ts[:t_start].  t_start == S is sample(S, x_T=x_latent).
+        mask / x0: 1 = keep x0 (the init latent), blended every step by one in-place ops.q_sample launch.
+        test_injection_kwargs: step_noises / blend_noises / dropout_masks, as sample() takes them.
+        Returns (samples, intermediates)."""
+        self._need_schedule("decode")
+        unknown = set(test_injection_kwargs) - {"step_noises", "blend_noises", "dropout_masks"}
+        if unknown:
+            raise TypeError(f"decode() got unexpected keyword arguments {sorted(unknown)}")
+        x_latent = torch.as_tensor(x_latent)
+        grid = self.ddpm_num_timesteps if use_original_steps else self.ddim_timesteps.shape[0]
+        return self.plms_sampling(cond, tuple(x_latent.shape), x_T=x_latent, ddim_use_original_steps=use_original_steps,
+                                  callback=callback, img_callback=img_callback, mask=mask, x0=x0, log_every_t=log_every_t,
+                                  unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning, verbose=False,
+                                  guidance_rescale=guidance_rescale, t_start=self._check_t_start(t_start, grid),
+                                  **test_injection_kwargs)
+
     # ---- model call: prefer the NHWC fast path of our LatentDiffusion; any object with the reference's
     #      apply_model(x, t, cond) -> NCHW eps still works (its output is re-laid-out by a HIP kernel).
     def _eps_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
@@ -128,7 +195,10 @@ class _SamplerBase:
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None, guidance_rescale=0.):
+                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None):
+        """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
+        t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
+        mask / x0 blend of every step is one ops.q_sample launch, in place."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if mask is not None and x0 is None:
             raise ValueError("mask blending needs x0 (plms.py:154)")
@@ -197,6 +267,8 @@ class _SamplerBase:
             n_orig = int(self.ddpm_num_timesteps if timesteps is None else timesteps)
             if not 0 < n_orig <= self.ddpm_num_timesteps:
                 raise ValueError(f"timesteps must be in (0, {self.ddpm_num_timesteps}] with ddim_use_original_steps")
+            if t_start is not None:
+                n_orig = self._check_t_start(t_start, n_orig)
             time_range = np.arange(n_orig - 1, -1, -1, dtype=np.int64)
             alphas, alphas_prev = self.alphas_cumprod, self.alphas_cumprod_prev
             sqrt_one_minus_alphas = self.sqrt_one_minus_alphas_cumprod
@@ -209,6 +281,8 @@ class _SamplerBase:
                 ts = ts[:subset_end]
                 if ts.shape[0] == 0:
                     raise ValueError(f"timesteps={timesteps} selects an empty subset of the {n_ddim}-step DDIM grid")
+            if t_start is not None:
+                ts = ts[:self._check_t_start(t_start, ts.shape[0])]
             time_range = np.flip(ts)
             alphas, alphas_prev = self.ddim_alphas, self.ddim_alphas_prev
             sqrt_one_minus_alphas, sigmas = self.ddim_sqrt_one_minus_alphas, self.ddim_sigmas
@@ -237,6 +311,11 @@ class _SamplerBase:
         if mask is not None:
             mask = torch.as_tensor(mask).to(device=dev, dtype=torch.float32)
             x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32)
+            if t_start is not None:     # the blend kernel's operands: contiguous, the mask [B, 1 | C, H, W]
+                x0 = x0.expand(shape).contiguous()
+                if mask.dim() != 4 or mask.shape[1] not in (1, shape[1]):
+                    raise MdxError(f"mask must be [B, 1, H, W] or [B, C, H, W], got {tuple(mask.shape)}")
+                mask = mask.expand((b, mask.shape[1]) + tuple(shape[2:])).contiguous()
         # per-step timestep vectors, fp32 on the device (the UNet's sinusoid takes float timesteps, util.py:111-131)
         # (a fresh array: the flipped view of a ONE-step grid still counts as contiguous and keeps its negative stride)
         t_all = torch.as_tensor(np.array(time_range, dtype=np.float32), device=dev)
@@ -347,13 +426,17 @@ class _SamplerBase:
         for i, step_t in enumerate(time_range):
             index = total_steps - i - 1
             if mask is not None:                                     # plms.py:153-157 (WK: q_sample gets explicit noise)
-                ts = torch.full((b,), int(step_t), device=dev, dtype=torch.long)
                 if blend_noises is not None:                          # tests inject the draws to compare with the oracle
                     noise = torch.as_tensor(blend_noises[i]).to(device=dev, dtype=torch.float32)
                 else:
                     noise = torch.randn(x0.shape, device=dev, dtype=torch.float32, generator=self.generator)
-                img_orig = self.model.q_sample(x0, ts, noise)
-                img = img_orig * mask + (1. - mask) * img
+                if t_start is not None:                               # q_sample + blend, one launch, in place
+                    ops.q_sample(x0, noise.contiguous(), self.sqrt_alphas_cumprod[int(step_t)],
+                                 self.sqrt_one_minus_alphas_cumprod[int(step_t)], out=img, mask=mask, img=img)
+                else:
+                    ts = torch.full((b,), int(step_t), device=dev, dtype=torch.long)
+                    img_orig = self.model.q_sample(x0, ts, noise)
+                    img = img_orig * mask + (1. - mask) * img
             eps_u, eps_c, _keep = model_eps(img, i)
             if not self.multistep:
                 step(img, eps_u, eps_c, index, (1., 0., 0., 0.), [], None, x_next, pred_x0, tm=step_t)

@@ -831,6 +831,52 @@ def vae_gaussian_sample(moments, zc, noise, out):
     return out
 
 
+def _same_shape(ref, name, t):
+    if t is not None and tuple(t.shape) != tuple(ref.shape):
+        raise _lib.MdxError(f"{name}: shape {tuple(t.shape)}, expected {tuple(ref.shape)}")
+
+
+def q_sample(x0, noise, a, b, out=None, mask=None, img=None):
+    """out = a * x0 + b * noise (ddpm.py:197-200); with `mask` [B, 1 | C, H, W] the result is blended into the running latent
+    `img`: out = mask * q + (1 - mask) * img (plms.py:153-157).  NCHW fp32; `out` may be `img` itself (in place) and no other
+    input.  One launch (include/mdx.h: mdx_q_sample_f32)."""
+    _chk(x0, f32, "x0"); _chk(noise, f32, "noise"); _chk(mask, f32, "mask"); _chk(img, f32, "img"); _chk(out, f32, "out")
+    if x0.dim() != 4:
+        raise _lib.MdxError(f"x0: expected [B, C, H, W], got shape {tuple(x0.shape)}")
+    B, C, H, W = x0.shape
+    if out is None:
+        out = torch.empty_like(x0)
+    _same_shape(x0, "noise", noise); _same_shape(x0, "img", img); _same_shape(x0, "out", out)
+    mask_c = 0
+    if mask is not None:
+        if mask.dim() != 4 or mask.shape[0] != B or tuple(mask.shape[2:]) != (H, W):
+            raise _lib.MdxError(f"mask: shape {tuple(mask.shape)}, expected [{B}, 1 or {C}, {H}, {W}]")
+        mask_c = int(mask.shape[1])
+    _lib.check(_lib.load().mdx_q_sample_f32(_ptr(x0), _ptr(noise), float(a), float(b), _ptr(mask), mask_c, _ptr(img),
+                                            _ptr(out), B, C, H * W, _stream()), "mdx_q_sample_f32")
+    return out
+
+
+def vae_encode_noised(moments, zc, post_noise, scale_factor, a, b, noise, z0_out, xt_out):
+    """Encoder moments NHWC fp16 [B, HW, ld] -> z0 = scale_factor * (mean + std * post_noise) and x_t = a * z0 + b * noise in
+    one launch (include/mdx.h: mdx_vae_encode_noised_f32).  post_noise None: the mode; either output may be None."""
+    _chk(moments, f16, "moments")
+    for name, t in (("post_noise", post_noise), ("noise", noise), ("z0_out", z0_out), ("xt_out", xt_out)):
+        _chk(t, f32, name)
+    B, HW, ld = moments.shape
+    ref = z0_out if z0_out is not None else xt_out
+    if ref is not None:
+        if ref.dim() != 4 or ref.shape[0] != B or ref.shape[1] != zc or ref.shape[2] * ref.shape[3] != HW:
+            raise _lib.MdxError(f"vae_encode_noised: output shape {tuple(ref.shape)} does not match moments [{B}, {HW}, {ld}], "
+                                f"zc = {zc}")
+        for name, t in (("post_noise", post_noise), ("noise", noise), ("xt_out", xt_out)):
+            _same_shape(ref, name, t)
+    _lib.check(_lib.load().mdx_vae_encode_noised_f32(_ptr(moments), ld, _ptr(post_noise), float(scale_factor), float(a),
+                                                     float(b), _ptr(noise), _ptr(z0_out), _ptr(xt_out), B, zc, HW, _stream()),
+               "mdx_vae_encode_noised_f32")
+    return z0_out, xt_out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Row-local fused SpatialTransformer tail (include/mdx.h: mdx_st_tail_f16, csrc/stchain.hip)
 def pack_frag_weight(w2d):

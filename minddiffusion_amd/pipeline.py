@@ -89,3 +89,78 @@ class DiffusionPipeline:
         if gather and n > 1:
             samples = D.gather_latents(samples)
         return samples
+
+    def img2img(self, init_image=None, init_latent=None, strength=0.75, prompts=None, c=None, uc=None, steps=50, scale=9.0,
+                eta=0.0, seed=42, noise=None, post_noise=None, sample_posterior=True, mask=None, decode=False, callback=None,
+                img_callback=None, guidance_rescale=0.0):
+        """Start from an image instead of pure noise: encode it, noise the latent to the level `strength` selects, and run only
+        the remaining t_enc = int(strength * steps) of the `steps`-step schedule (strength 1: all of them).
+
+        init_image [B, 3, H, W] in [-1, 1] (needs model.first_stage_model with an encoder) or init_latent [B, C, h, w]
+        (already scaled by model.scale_factor): exactly one of them.  noise / post_noise: the N(0, 1) draws of the forward
+        process and of the VAE posterior at the latent's shape; None = numpy RandomState(seed) / RandomState(seed + 1), as
+        start_noise().  sample_posterior False: the posterior's mode.  mask [B, 1, h, w] at latent resolution, 1 = keep the
+        init image there (PLMS / DDIM only).  Conditioning, decode and guidance_rescale as in __call__.  Single rank only."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if (init_image is None) == (init_latent is None):
+            raise ValueError("img2img: pass exactly one of init_image and init_latent")
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"img2img: strength must be in (0, 1], got {strength!r}")
+        t_enc = int(float(strength) * steps)
+        if t_enc == 0:
+            raise ValueError(f"img2img: strength {strength!r} leaves no step of {steps} to run")
+        if D.world()[1] > 1:
+            raise MdxError("img2img runs on a single rank (the sharded form is not built)")
+        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        dpm = isinstance(self.sampler, DPMSolverSampler)
+        if mask is not None and dpm:
+            raise NotImplementedError("img2img: mask blending is implemented by PLMSSampler / DDIMSampler")
+        if prompts is not None:
+            uc = self.model.get_learned_conditioning(len(prompts) * [""])
+            c = self.model.get_learned_conditioning(list(prompts))
+        if c is None:
+            raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
+        B = int(c.shape[0])
+        c = c.to(self.device, torch.float16)
+        uc = None if uc is None else uc.to(self.device, torch.float16)
+        if uc is not None and uc.shape[0] == 1 and B > 1:
+            uc = uc.expand(B, -1, -1).contiguous()
+        # where the partial run starts: a grid index for PLMS / DDIM, a continuous time for DPM-Solver -- the last t_enc of the
+        # full run's own `steps` intervals, t_0 + (T - t_0) * t_enc / steps
+        if dpm:
+            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
+            start = t_0 + (1.0 - t_0) * t_enc / steps
+            a, b = self.sampler.q_coefficients(start)
+        else:
+            self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
+            a, b = self.sampler.q_coefficients(t_enc)
+        draw = lambda given, shape, sd: (torch.from_numpy(np.random.RandomState(sd).randn(*shape).astype(np.float32))
+                                         if given is None else given)
+        if init_image is not None:
+            vae = self.model.first_stage_model
+            if vae is None or not hasattr(vae, "encode_noised"):
+                raise MdxError("img2img(init_image=) needs a VAE with an encoder attached (model.first_stage_model)")
+            x = init_image.to(device=self.device, dtype=torch.float32)
+            shape = vae.latent_shape(x.shape)                         # the encoder's output size, not H // 8
+            z0, x_enc = vae.encode_noised(x, self.model.scale_factor, a, b, draw(noise, shape, seed),
+                                          post_noise=draw(post_noise, shape, seed + 1) if sample_posterior else None,
+                                          sample=sample_posterior)
+        else:
+            z0 = init_latent.to(device=self.device, dtype=torch.float32).contiguous()
+            x_enc = self.sampler.stochastic_encode(z0, start if dpm else t_enc, noise=draw(noise, z0.shape, seed))
+        if z0.shape[0] != B:
+            raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
+        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
+        if dpm:
+            samples, _ = self.sampler.sample(S=t_enc, conditioning=c, batch_size=B, shape=list(z0.shape[1:]), verbose=False,
+                                             unconditional_guidance_scale=scale, unconditional_conditioning=uc, x_T=x_enc,
+                                             callback=callback, img_callback=img_callback, t_start=start, **rescale_kw)
+        else:
+            blend_kw = {} if mask is None else {"mask": mask, "x0": z0}
+            samples, _ = self.sampler.decode(x_enc, c, t_enc, unconditional_guidance_scale=scale,
+                                             unconditional_conditioning=uc, callback=callback, img_callback=img_callback,
+                                             **blend_kw, **rescale_kw)
+        if decode:
+            x = self.model.decode_first_stage(samples)
+            samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
+        return samples
