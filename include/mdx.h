@@ -256,7 +256,8 @@ typedef struct mdx_gemm_desc {
      * 64 -- on chip, and writes  out[m][64 h ..] = softmax(q_h K_h^T * xattn_scale) V_h  instead of q: the separate attention launch and
      * the fp16 round trip of q disappear, the arithmetic is that of mdx_attention_f16 on the fp16-rounded q (bit-identical).
      *   xattn_k  [B][xattn_cap][N] fp16 (keys, row-major: head h in columns 64 h ..), xattn_vt [B][N][xattn_cap] fp16 (values, transposed),
-     *   xattn_len <= 128 keys of xattn_cap rows are attended to.
+     *   xattn_len <= 1024 keys of xattn_cap rows are attended to (64-key tiles; past two tiles they are re-staged in LDS pair by pair:
+     *   a launch with xattn_len <= 128 keeps its LDS size, its occupancy and its bits).
      * Dense row-major launches only (ksize 1, one source, no epilogue / residual / statistics / n_split / out_bs), N % 64 == 0, tokens per
      * sample % 128 == 0 (or % 64 == 0 with tile_m = 64); set tile_n = 64 and splitk = 1. */
     const void* xattn_k;
@@ -399,7 +400,8 @@ typedef struct mdx_st_tail_desc {
     int debug_stage;
     int B, tokens;        /* M = B * tokens rows; tokens % tile_rows == 0 */
     int C, heads, dim_head;
-    int ctx_len, ctx_cap; /* keys used / row capacity of ctx_k (ctx_vt row length); ctx_cap % 8 == 0, <= 96 */
+    int ctx_len, ctx_cap; /* keys used / row capacity of ctx_k (ctx_vt row length); ctx_cap % 8 == 0, <= 1024.
+                           * ctx_len <= 96: one pass over the keys (whatever ctx_cap is); longer: 96-key chunks with online softmax */
     float scale;          /* dim_head ** -0.5 */
     float ln_eps;
     int tile_rows;        /* 32 | 64 */

@@ -45,16 +45,31 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 //      a VMEM instruction costs a lone wave ~50 clocks to issue, and 29 of them in front of the first barrier cost the launch more
 //      than the round trips they hide
 // Cross-attention over a short cached context as the epilogue of the query projection (mdx_gemm_desc.xattn_k; BN = 64 = head dim): the
-// tile's fp16 q rows are in LDS at `stg` ([BM][72]), the head's K / V^T tiles (at most two of 64 keys; attn_kernel's LDS images) at `xs`.
+// tile's fp16 q rows are in LDS at `stg` ([BM][72]), the head's K / V^T tiles (64 keys each; attn_kernel's LDS images) at `xs`: two
+// slots, tile t in slot t & 1.  Up to two tiles (xa_len <= 128) are all staged by the caller before this runs -- the only form until
+// contexts longer than 128 keys came, and its LDS size, barriers and bits are what they were.  Longer contexts re-stage the two slots
+// pair by pair (`restage`, every wave of the block issues its share) between two block barriers: readers of the old pair done | new
+// pair landed.  The tile program and its order over the tiles do not depend on where a tile was staged, so the contract holds for
+// any length (above two tiles mdx_attention_f16 runs attn_pipe_kernel, bit-identical to attn_kernel).
 // Every wave takes 32 query rows through attn_kernel's tile program -- S^T = K Q^T, lazy-reference online softmax, O^T += V^T P^T, the
 // masked form on a ragged last tile -- normalises, stages its 32 x 64 output rows over its own q rows and stores them: the same
 // operations on the same values in the same order as mdx_attention_f16 on the stored q (bit-identical).
-template <int BM>
-__device__ __forceinline__ void xattn_tile_epilogue(const GemmParams& p, char* smem, const char* xs, const int m0, const int n0) {
+template <int BM, class Restage>
+__device__ __forceinline__ void xattn_tile_epilogue(const GemmParams& p, char* smem, const char* xs, const int m0, const int n0,
+                                                    const Restage& restage) {
     constexpr int SLD = 72;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (wave * 32 >= BM) return;
+    const int ntile = (p.xa_len + 63) >> 6;
+    if (wave * 32 >= BM) {      // no query rows: this wave only stages the later tile pairs of a long context
+        for (int t0 = 2; t0 < ntile; t0 += 2) {
+            __syncthreads();
+            restage(t0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        return;
+    }
     const int hi = lane >> 5, l31 = lane & 31;
     f16* stg = reinterpret_cast<f16*>(smem);
     f16x8 qf[4];
@@ -68,10 +83,9 @@ __device__ __forceinline__ void xattn_tile_epilogue(const GemmParams& p, char* s
     float m_run = -INFINITY, l_run = 0.f;
     const int vswz = (lane >> 1) & 7;
     const int krow_l = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);      // attn_kernel's key permutation
-    const int ntile = (p.xa_len + 63) >> 6;
     auto tile = [&](const int t, auto mask_c) {
         constexpr bool MASK = decltype(mask_c)::value;
-        const char* sk = xs + t * 16384;
+        const char* sk = xs + (t & 1) * 16384;
         const char* sv = sk + 8192;
         f32x16 acc_s[2];
 #pragma unroll
@@ -140,6 +154,12 @@ __device__ __forceinline__ void xattn_tile_epilogue(const GemmParams& p, char* s
             }
     };
     for (int t = 0; t < ntile; ++t) {
+        if (t >= 2 && !(t & 1)) {      // (block-uniform) both slots read by every wave -> the next pair
+            __syncthreads();
+            restage(t);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
         if ((t + 1) * 64 > p.xa_len) tile(t, std::true_type{}); else tile(t, std::false_type{});
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -598,33 +618,38 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const GemmParams p) {
         // the head's K / V^T tiles -> LDS behind the staging area, in flight while the accumulators are corrected and staged
         constexpr int XOFF = ((BM * 72 * 2 + 2 * BM * 4 + BN * 4 + 1023) / 1024) * 1024;
         char* xs = smem + XOFF;
-        {
-            const int bsamp = m0 / p.HoWo, head = n0 >> 6;
-            const f16* kb = p.xa_k + (size_t)bsamp * p.xa_cap * p.N + head * 64;
-            const f16* vb = p.xa_vt + ((size_t)bsamp * p.N + head * 64) * p.xa_cap;
-            const __amdgpu_buffer_rsrc_t rs_k = make_rsrc(kb, (unsigned)(((size_t)(p.xa_len - 1) * p.N + 64) * 2));
-            const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(vb, (unsigned)((size_t)64 * p.xa_cap * 2));
-            const int ntile = (p.xa_len + 63) >> 6;
-            for (int t = 0; t < ntile; ++t) {
+        // (two slots; a context of more than two tiles re-stages them pair by pair inside xattn_tile_epilogue.  Offsets stay in 32 bits:
+        // xa_len <= 1024 keys of N <= 2^20 halves, checked by the resolver's 2 GiB bound)
+        const int bsamp = m0 / p.HoWo, head = n0 >> 6;
+        const f16* kb = p.xa_k + (size_t)bsamp * p.xa_cap * p.N + head * 64;
+        const f16* vb = p.xa_vt + ((size_t)bsamp * p.N + head * 64) * p.xa_cap;
+        const __amdgpu_buffer_rsrc_t rs_k = make_rsrc(kb, (unsigned)(((size_t)(p.xa_len - 1) * p.N + 64) * 2));
+        const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(vb, (unsigned)((size_t)64 * p.xa_cap * 2));
+        const int ntile = (p.xa_len + 63) >> 6;
+        auto stage_pair = [&](const int t0) {
+            const int t1 = t0 + 2 < ntile ? t0 + 2 : ntile;
+            for (int t = t0; t < t1; ++t) {
+                char* slot = xs + (t & 1) * 16384;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int inst = wave * 2 + j;
                     const int krow = inst * 8 + (lane >> 3);
                     const int kchunk = (lane & 7) ^ ((krow >> 1) & 7);
                     const int key = t * 64 + krow;
-                    dma16(rs_k, xs + t * 16384 + inst * 1024, key < p.xa_len ? (unsigned)(((size_t)key * p.N + kchunk * 8) * 2) : MDX_OOB);
+                    dma16(rs_k, slot + inst * 1024, key < p.xa_len ? (unsigned)(((size_t)key * p.N + kchunk * 8) * 2) : MDX_OOB);
                     const int vrow = inst * 8 + (lane >> 3);
                     const unsigned vchunk = (unsigned)((lane & 7) ^ ((vrow >> 1) & 7));
                     const int kc = t * 64 + (int)vchunk * 8;
-                    dma16(rs_v, xs + t * 16384 + 8192 + inst * 1024, kc < p.xa_cap ? (unsigned)(((size_t)vrow * p.xa_cap + kc) * 2) : MDX_OOB);
+                    dma16(rs_v, slot + 8192 + inst * 1024, kc < p.xa_cap ? (unsigned)(((size_t)vrow * p.xa_cap + kc) * 2) : MDX_OOB);
                 }
             }
-        }
+        };
+        stage_pair(0);
         gemm_epilogue<BM, BN, true, NW, LinearRows, NX, 3>(p, acc, smem, LinearRows{m0}, n0, split, bpre, tile_m, tile_id, ln_pre, &lns_pre, xpre,
                                                            ln_regs, lns_regs);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();      // K / V^T of every wave's DMAs landed (the staged q tile was ordered by the epilogue's own barrier)
-        xattn_tile_epilogue<BM>(p, smem, xs, m0, n0);
+        xattn_tile_epilogue<BM>(p, smem, xs, m0, n0, stage_pair);
     } else if constexpr (W41) {
         epilogue_w41<BM, BN>(p, acc[0], smem, m0, n0, bpre[0], bpre[4]);
     } else {

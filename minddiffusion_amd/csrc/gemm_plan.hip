@@ -162,8 +162,8 @@ static int fill_params(const mdx_gemm_desc* d, GemmParams& p) {
     p.xa_scale_log2 = d->xattn_scale * 1.4426950408889634f;
     if (p.xa_k) {
         const int howo = d->H * d->W;
-        MDX_REQUIRE(p.xa_vt && d->xattn_len > 0 && d->xattn_len <= 128 && d->xattn_cap >= d->xattn_len && d->xattn_cap % 8 == 0,
-                    "mdx_gemm_f16: cross-attention epilogue needs xattn_vt, 0 < xattn_len <= 128 <= ... xattn_cap (a multiple of 8)");
+        MDX_REQUIRE(p.xa_vt && d->xattn_len > 0 && d->xattn_len <= 1024 && d->xattn_cap >= d->xattn_len && d->xattn_cap % 8 == 0,
+                    "mdx_gemm_f16: cross-attention epilogue needs xattn_vt, 0 < xattn_len <= 1024 and xattn_len <= xattn_cap (a multiple of 8)");
         MDX_REQUIRE(d->ksize == 1 && d->stride == 1 && !d->upsample && d->c2 == 0 && d->N % 64 == 0 && d->c1 % 64 == 0 &&
                         d->epilogue == MDX_EPI_NONE && d->out_mode == MDX_OUT_ROWMAJOR && !d->residual && !d->rowbias && !d->stats_out &&
                         !d->colstats_out && !d->n_split && !d->out_bs && !d->gn_colstats && !d->defer_reduce,

@@ -3,7 +3,7 @@
 //
 //   t1  = attn1_out  Wo1^T + bo1 + tok                 (attention.py:151-152 to_out, :182 residual)
 //   q2  = LN2(t1)    Wq2^T                             (:177 norm2, :108 to_q)
-//   o2  = softmax(q2 K_ctx^T * scale) V_ctx            (:138-150 over the <= 80 cached context keys, per head)
+//   o2  = softmax(q2 K_ctx^T * scale) V_ctx            (:138-150 over the cached context keys, per head; > 96 keys: chunked)
 //   t2  = o2         Wo2^T + bo2 + t1                  (:183)
 //   h   = GEGLU(LN3(t2) W1^T + b1)                     (:41-51, :178)
 //   t3  = h          W2^T + b2 + t2                    (:66, :184)
@@ -23,7 +23,8 @@
 //    [M][4C] intermediate never exists;
 //  * cross-attention: one (head, 32-query tile) per wave, K / V^T fragments straight from the cached context
 //    projections (L2-resident, 77 keys), S^T = K Q^T so a lane owns one query (softmax = one lane^32 exchange), P feeds
-//    PV from the S^T accumulator registers (key permutation trick of attention.hip).
+//    PV from the S^T accumulator registers (key permutation trick of attention.hip).  Up to 96 keys are one pass; a longer context
+//    (several CLIP windows, capacity <= 1024) runs the LONG instantiation: 96-key chunks with online softmax (st_xattn_chunked).
 // Built for C = 320 (heads x head dim 5 x 64 or 8 x 40): the 64 x 64 level of SDv2 / Wukong (96 x 96 at 768^2), where M / BM fills
 // the chip; at C = 640 / 1280 the per-block weight stream (13 / 52 MB) costs more than the launches it saves.
 #include "mdx_common.h"
@@ -195,7 +196,126 @@ __device__ __forceinline__ void warmer_wave(const char* wstream, const BarSched&
     asm volatile("" ::"v"(tmp));     // the destination register stays live until here
 }
 
+// Stage S3 for a context of more than one 96-key chunk (st_tail_kernel<.., LONG = true>, launched when ctx_len > 96): the
+// one-pass softmax of the short form becomes a loop over 96-key chunks with online softmax -- a running row maximum m_run and a
+// running sum l_run per lane (a lane owns one query; the two half-waves hold the same maximum and partial sums), acc_o rescaled
+// by 2^((m_old - m_new) scale) when the maximum moved in some lane of the wave (lanes whose maximum stayed multiply by exactly 1).
+// ceil(ctx_len / 96) trips; K rows past the capacity answer zero through the descriptor and keys >= ctx_len are masked to -inf
+// (P = 0 exactly, so whatever finite V^T columns the last chunk reads past ctx_len add nothing).  Wave-local like the short form:
+// NO block barrier in here (the warmer's schedule does not know the context length).  K, V^T and q2 fragments are fetched per
+// chunk; only acc_o, m_run and l_run live across chunks.  Offsets: (ctx_cap + 95) * C * 2 < 2^20 for ctx_cap <= 1024.
 template <int C, int TM, int D>
+__device__ __forceinline__ void st_xattn_chunked(const StTailParams& p, const char* Hb, char* Ab, const int m0, const int wave,
+                                                 const int hi, const int l31) {
+    constexpr int NW = C / 32, LDB = (C + 8) * 2;
+    constexpr int KS = (D + 15) / 16, DT = (D + 31) / 32, KT = 3;
+    const int xb = m0 / p.HW;
+    const __amdgpu_buffer_rsrc_t rs_k = make_rsrc(p.kc + (size_t)xb * p.TC * C, p.kc_bytes);
+    const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(p.vtc + (size_t)xb * C * p.TC, p.vtc_bytes);
+    const int krow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);   // pi(l31): bits 2 and 3 swapped (attention.hip)
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    const int nch = (p.ctx_len + 32 * KT - 1) / (32 * KT);
+    for (int item = wave; item < p.heads * TM; item += NW) {
+        const int h = item / TM, rt = item - h * TM;
+        f32x16 acc_o[DT];
+#pragma unroll
+        for (int j = 0; j < DT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc_o[j][r] = 0.f;
+        float m_run = -INFINITY, l_run = 0.f;
+#pragma unroll 1
+        for (int ch = 0; ch < nch; ++ch) {
+            const int k0 = ch * 32 * KT;
+            u32x4 kf[KT][KS], vf[DT][2 * KT];
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const bool ok = s * 16 + hi * 8 < D;
+                    const unsigned off = (unsigned)(((k0 + t * 32 + krow) * C + h * D + s * 16 + hi * 8) * 2);
+                    kf[t][s] = ok ? __builtin_amdgcn_raw_buffer_load_b128(rs_k, off, 0, 0) : zero4;
+                }
+            auto load_v = [&](int j) {
+#pragma unroll
+                for (int c = 0; c < 2 * KT; ++c) {
+                    const unsigned off = (unsigned)(((h * D + j * 32 + l31) * p.TC + k0 + c * 16 + hi * 8) * 2);
+                    vf[j][c] = __builtin_amdgcn_raw_buffer_load_b128(rs_v, off, 0, 0);
+                }
+            };
+            load_v(0);
+            f16x8 qf[KS];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                if (s * 16 + hi * 8 < D)
+                    qf[s] = *reinterpret_cast<const f16x8*>(Hb + (rt * 32 + l31) * LDB + (h * D + s * 16 + hi * 8) * 2);
+                else
+                    qf[s] = __builtin_bit_cast(f16x8, zero4);
+            }
+            f32x16 acc_s[KT];
+#pragma unroll
+            for (int t = 0; t < KT; ++t) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc_s[t][r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < KS; ++s)
+                    acc_s[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kf[t][s]), qf[s], acc_s[t], 0, 0, 0);
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = k0 + t * 32 + (r & 3) + 4 * ((r >> 2) & 1) + 8 * hi + 16 * (r >> 3);
+                    if (key >= p.ctx_len) acc_s[t][r] = -INFINITY;
+                    mx = fmaxf(mx, acc_s[t][r]);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, mx);      // finite: every chunk holds at least one key < ctx_len
+            if (__builtin_amdgcn_ballot_w64(m_new != m_run)) {
+                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);     // first chunk: 2^-inf = 0 on zeros
+                l_run *= alpha;
+#pragma unroll
+                for (int j = 0; j < DT; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc_o[j][r] *= alpha;
+                m_run = m_new;
+            }
+            const float mb = m_run * p.scale_log2;
+            float psum = 0.f;
+            f16x8 pf[2 * KT];
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __builtin_amdgcn_exp2f(acc_s[t][r] * p.scale_log2 - mb);
+                    psum += pv;
+                    pf[t * 2 + (r >> 3)][r & 7] = (f16)pv;
+                }
+            l_run += psum;
+#pragma unroll
+            for (int j = 1; j < DT; ++j) load_v(j);
+#pragma unroll
+            for (int j = 0; j < DT; ++j)
+#pragma unroll
+                for (int c = 0; c < 2 * KT; ++c)
+                    acc_o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vf[j][c]), pf[c], acc_o[j], 0, 0, 0);
+        }
+        l_run += __shfl_xor(l_run, 32, 64);
+        const float inv = 1.0f / l_run;
+#pragma unroll
+        for (int j = 0; j < DT; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int dd = j * 32 + 8 * g + 4 * hi;
+                if (dd < D)
+                    *reinterpret_cast<f16x4*>(Ab + (rt * 32 + l31) * LDB + (h * D + dd) * 2) =
+                        f16x4{(f16)(acc_o[j][4 * g] * inv), (f16)(acc_o[j][4 * g + 1] * inv), (f16)(acc_o[j][4 * g + 2] * inv),
+                              (f16)(acc_o[j][4 * g + 3] * inv)};
+            }
+    }
+}
+
+template <int C, int TM, int D, bool LONG>
 __global__ __launch_bounds__((C / 32 + 1) * 64) void st_tail_kernel(const StTailParams p) {
     mdx_kernarg_touch<sizeof(StTailParams)>();
     constexpr int NW = C / 32;
@@ -340,7 +460,10 @@ __global__ __launch_bounds__((C / 32 + 1) * 64) void st_tail_kernel(const StTail
     if (p.stop_after == 3) { dump(Hb); return; }
 
     // ---- S3: cross-attention over the cached context keys: A <- softmax(q2 K^T scale) V, per (head, 32-row tile)
-    {
+    // (ctx_len <= 96: one pass over KT * 32 keys, the block below; longer contexts: the chunked instantiation, same barriers)
+    if constexpr (LONG) {
+        st_xattn_chunked<C, TM, D>(p, Hb, Ab, m0, wave, hi, l31);
+    } else {
         constexpr int KS = (D + 15) / 16, DT = (D + 31) / 32, KT = 3;
         const int xb = m0 / p.HW;
         const __amdgpu_buffer_rsrc_t rs_k = make_rsrc(p.kc + (size_t)xb * p.TC * C, p.kc_bytes);
@@ -548,17 +671,17 @@ __global__ __launch_bounds__((C / 32 + 1) * 64) void st_tail_kernel(const StTail
     if (p.stop_after == ST_COUNT_BARRIERS && blockIdx.x == 0 && tid == 0) *reinterpret_cast<int*>(p.dbg) = nbar;
 }
 
-template <int C, int TM, int D>
+template <int C, int TM, int D, bool LONG>
 void launch_tail(const StTailParams& p, hipStream_t st) {
     constexpr int NW = C / 32, BM = 32 * TM;
     constexpr size_t lds = (size_t)(TM == 1 ? 4 : 3) * BM * (C + 8) * 2 + (size_t)VecOff<C>::total * 4 + (size_t)NW * BM * 8;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static MdxPerDeviceOnce attr_once;
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&st_tail_kernel<C, TM, D>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&st_tail_kernel<C, TM, D, LONG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    hipLaunchKernelGGL((st_tail_kernel<C, TM, D>), dim3(p.M / BM), dim3((NW + 1) * 64), lds, st, p);
+    hipLaunchKernelGGL((st_tail_kernel<C, TM, D, LONG>), dim3(p.M / BM), dim3((NW + 1) * 64), lds, st, p);
 }
 
 
@@ -853,8 +976,8 @@ extern "C" int mdx_st_tail_f16(const mdx_st_tail_desc* d, mdx_stream_t s) {
     MDX_REQUIRE(mdx_st_tail_supported(d->C, d->heads, d->dim_head, d->tokens, d->tile_rows),
                 "mdx_st_tail_f16: unsupported shape C=%d heads=%d d=%d tokens=%d tile_rows=%d", d->C, d->heads, d->dim_head,
                 d->tokens, d->tile_rows);
-    MDX_REQUIRE(d->B > 0 && d->ctx_len > 0 && d->ctx_len <= d->ctx_cap && d->ctx_cap % 8 == 0 && d->ctx_cap <= 96,
-                "mdx_st_tail_f16: context length %d / capacity %d (capacity: multiple of 8, <= 96)", d->ctx_len, d->ctx_cap);
+    MDX_REQUIRE(d->B > 0 && d->ctx_len > 0 && d->ctx_len <= d->ctx_cap && d->ctx_cap % 8 == 0 && d->ctx_cap <= 1024,
+                "mdx_st_tail_f16: context length %d / capacity %d (capacity: multiple of 8, <= 1024)", d->ctx_len, d->ctx_cap);
     MDX_REQUIRE(d->out != d->attn_out && d->out != d->tok && d->out != d->x_in, "mdx_st_tail_f16: out must not alias an input");
     StTailParams p{};
     p.attn_o = (const f16*)d->attn_out;
@@ -889,10 +1012,14 @@ extern "C" int mdx_st_tail_f16(const mdx_st_tail_desc* d, mdx_stream_t s) {
     p.kc_bytes = (unsigned)((size_t)d->ctx_cap * d->C * 2);
     p.vtc_bytes = (unsigned)((size_t)d->C * d->ctx_cap * 2);
     hipStream_t st = (hipStream_t)s;
+    // ctx_len <= 96 keeps the one-pass instantiation (and its bits) whatever the capacity; longer contexts take the chunked one
+    const bool lng = d->ctx_len > 96;
     if (d->dim_head == 64) {
-        if (d->tile_rows == 64) launch_tail<320, 2, 64>(p, st); else launch_tail<320, 1, 64>(p, st);
+        if (d->tile_rows == 64) { if (lng) launch_tail<320, 2, 64, true>(p, st); else launch_tail<320, 2, 64, false>(p, st); }
+        else { if (lng) launch_tail<320, 1, 64, true>(p, st); else launch_tail<320, 1, 64, false>(p, st); }
     } else {
-        if (d->tile_rows == 64) launch_tail<320, 2, 40>(p, st); else launch_tail<320, 1, 40>(p, st);
+        if (d->tile_rows == 64) { if (lng) launch_tail<320, 2, 40, true>(p, st); else launch_tail<320, 2, 40, false>(p, st); }
+        else { if (lng) launch_tail<320, 1, 40, true>(p, st); else launch_tail<320, 1, 40, false>(p, st); }
     }
     MDX_LAUNCH_CHECK("mdx_st_tail_f16");
     return MDX_OK;

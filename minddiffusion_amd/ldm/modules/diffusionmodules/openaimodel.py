@@ -49,8 +49,9 @@ class UNetModel:
                  num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
                  use_new_attention_order=False, use_spatial_transformer=False, transformer_depth=1, context_dim=None,
                  n_embed=None, legacy=True, use_linear_in_transformer=False, enable_lora=False, lora_rank=4, lora_alpha=4,
-                 device="cuda:0"):
-        """enable_lora / lora_rank / lora_alpha (WK openaimodel.py:302-304): to_q, to_k, to_v and to_out.0 of every
+                 max_context_len=80, device="cuda:0"):
+        """max_context_len: capacity (keys) of the cached text context, rounded up to a multiple of 8; 80 holds one 77-token CLIP
+        window, a prompt of n chunks needs n * 77 (set_max_context_len changes it later).  enable_lora / lora_rank / lora_alpha (WK openaimodel.py:302-304): to_q, to_k, to_v and to_out.0 of every
         CrossAttention become LoRA targets (WK attention.py:118-126).  The reference wires these keywords for Wukong only;
         here they work for every configuration (SDv2 included).  The adapter is MERGED into the packed weights in place
         (load_lora_state_dict), so the denoising loop is the code that runs without it."""
@@ -98,7 +99,8 @@ class UNetModel:
         self._ctx_key = None
         self._ctx_ref = None
         self.use_graph = True
-        self.max_context_len = 80  # 77 CLIP tokens rounded up to a multiple of 8 (V^T rows are 16-B chunked)
+        # capacity of the cached context: 77 CLIP tokens rounded up to a multiple of 8 by default (V^T rows are 16-B chunked)
+        self.max_context_len = self._check_context_cap(max_context_len)
         self.last_launch_count = 0
         self.enable_lora = bool(enable_lora)
         self.lora_rank = int(lora_rank)
@@ -109,6 +111,26 @@ class UNetModel:
         self._lora_sites = {}     # target name -> the places the matrix lives in self.w (kwargs of ops.lora_merge)
         self._lora = None         # target name -> (A [rank, in], B [out, rank]) fp32 on the device
         self._lora_mult = 1.0
+
+    @staticmethod
+    def _check_context_cap(n):
+        n = int(n)
+        if not 1 <= n <= 1024:
+            raise MdxError(f"UNetModel: max_context_len must be in [1, 1024] (got {n})")
+        return round_up(n, 8)
+
+    def set_max_context_len(self, n):
+        """Capacity of the cached text context in keys (rounded up to a multiple of 8, at most 1024).  Plans size their
+        context buffers by it, so a CHANGE drops the plans, their captured graphs and the cached context projections; the same
+        value again is a no-op.  Call it between evaluations (never from inside a sampling loop: the next evaluation plans and
+        captures again).  On several ranks every rank must set the same value before conditioning is broadcast."""
+        n = self._check_context_cap(n)
+        if n != self.max_context_len:
+            self.max_context_len = n
+            self._plans = {}
+            self._ctx_key = None
+            self._ctx_ref = None
+        return self
 
     # ------------------------------------------------------------------ structure (openaimodel.py:351-526)
     def _heads(self, ch, num_heads):
@@ -716,6 +738,8 @@ class _UNetPlanner(PlanBuilder):
         self.net, self.w, self.H, self.W = net, net.w, H, W
         self.fuse_head, self.selfctx = fuse_head, selfctx
         self.TC = net.max_context_len
+        # keys the roofline metadata counts per query: one CLIP window at the default capacity, else the plan's capacity
+        self.ctx_flops = 77 if self.TC == 80 else self.TC
         self.mod_ld = net._emb_total
         self.P = UNetModel._Plan()
         self.ctxops = []
@@ -969,8 +993,8 @@ class _UNetPlanner(PlanBuilder):
         TC = self.TC
         if (t + "tail.stream") not in self.w or self.net.transformer_depth != 1 or self.selfctx:
             return 0
-        if TC > 96 or TC % 8:       # mdx_st_tail_f16 holds the context keys in registers: capacity <= 96, multiple of 8
-            return 0                # (a UNet built with a longer max_context_len keeps the unfused launches, any length)
+        if TC > 1024 or TC % 8:     # mdx_st_tail_f16: capacity a multiple of 8, <= 1024 (96-key chunks with online softmax past 96)
+            return 0
         forced = ops.get_option("unet_st_tail")
         cands = [forced] if forced in (32, 64) else ([] if forced == 0 else [64, 32])
         for r in cands:
@@ -1012,7 +1036,7 @@ class _UNetPlanner(PlanBuilder):
         def run_tail(td=td):
             td.ctx_len = P.ctx_len      # read at call time like the attention ops; a captured graph bakes it in
             ops.st_tail_run(td)
-        self.emit(run_tail, "gemm", 2 * B * n * 16 * inner * inner + 4 * B * heads * n * 77 * dh, 1,
+        self.emit(run_tail, "gemm", 2 * B * n * 16 * inner * inner + 4 * B * heads * n * self.ctx_flops * dh, 1,
                   f"st_tail M={B * n} C={inner} rows={rows_t} (to_out1..proj_out fused)")
         return out
 
@@ -1135,7 +1159,7 @@ class _UNetPlanner(PlanBuilder):
             # --- attn2 (cross): K / V^T of the context are produced by the context plan
             # (round 6) head dim 64 (SDv2): the 77-key attention rides on the query projection as its EPILOGUE -- one 64-column
             # tile is one head (mdx_gemm_desc.xattn_k): no attention launch, no fp16 round trip of q; bit-identical to the two launches
-            xfuse = (ops.get_option("unet_xattn_fuse") and not selfctx and dh == 64 and TC <= 128 and TC % 8 == 0
+            xfuse = (ops.get_option("unet_xattn_fuse") and not selfctx and dh == 64 and TC <= 1024 and TC % 8 == 0
                      and n % 64 == 0)
             xkw = {}
             if xfuse:
@@ -1151,7 +1175,7 @@ class _UNetPlanner(PlanBuilder):
                     layernorm(tok2, t, "norm2", ln)
             if xfuse:
                 self.xattn_descs.append(self.descs[-1])      # (their xattn_len follows the context: _ensure_context)
-                self.meta[-1]["flops"] += 4 * B * heads * n * 77 * dh
+                self.meta[-1]["flops"] += 4 * B * heads * n * self.ctx_flops * dh
                 self.meta[-1]["info"] += f" +cross-attention h={heads} d={dh}"
                 q2 = None
             if selfctx:
@@ -1171,7 +1195,7 @@ class _UNetPlanner(PlanBuilder):
                 emit(lambda q2=q2, kc=kc, vtc=vtc, o=o: ops.attention(
                     q2.data_ptr(), kc.data_ptr(), vtc.data_ptr(), o.data_ptr(), B, heads, dh, n, P.ctx_len, scale,
                     n * inner, inner, TC * inner, inner, inner * TC, TC, n * inner, inner),
-                    "attention", 4 * B * heads * n * 77 * dh, 1, f"cross B={B} h={heads} N={n} d={dh}")
+                    "attention", 4 * B * heads * n * self.ctx_flops * dh, 1, f"cross B={B} h={heads} N={n} d={dh}")
             tok3 = dense(o, B, n, inner, inner, w[t + "attn2.o.w"], bias=w[t + "attn2.o.b"], residual=tok2, stats_out=st)
             if q2 is not None:
                 self.release(q2)

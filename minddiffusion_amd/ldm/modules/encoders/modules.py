@@ -3,7 +3,8 @@ LatentDiffusion.get_learned_conditioning calls (``cond_stage_model.encode(list[s
 
 The tokenizer (BPE for SDv2, WordPiece for Wukong: ldm/models/clip_zh/simple_tokenizer.py) is host-side preprocessing
 outside SURVEY 8 and needs vocabulary files the repository does not ship; pass any callable ``tokenizer(list[str]) ->
-int array [B, 77]`` to use ``encode``; ``construct(token_ids)`` needs none.
+int array [B, 77]`` to use ``encode``; ``construct(token_ids)`` needs none.  Both also take ``[B, n, 77]`` -- a long prompt cut
+into n windows by ``encoders.chunk_token_ids`` -- and return ``[B, n * 77, width]``.
 """
 from ...._lib import MdxError
 from .text_encoder import TextEncoder

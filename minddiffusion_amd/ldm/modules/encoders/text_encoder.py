@@ -127,10 +127,16 @@ class TextEncoder:
 
     def construct(self, text):
         """text_encoder.py:141-153.  text: int token ids [B, context_length] (any integer tensor / array) ->
-        [B, context_length, width] fp16 on the GPU."""
+        [B, context_length, width] fp16 on the GPU.  A long prompt cut into n windows (encoders.chunk_token_ids) comes as
+        [B, n, context_length]: the B * n windows are encoded in ONE pass, each on its own (causal attention never crosses a
+        window), and returned side by side as [B, n * context_length, width]."""
         tok = torch.as_tensor(np.asarray(text) if not isinstance(text, torch.Tensor) else text)
+        if tok.dim() == 3 and tok.shape[2] == self.context_length and tok.shape[1] > 0:
+            b, n = tok.shape[0], tok.shape[1]
+            return self.construct(tok.reshape(b * n, self.context_length)).view(b, n * self.context_length, self.width)
         if tok.dim() != 2 or tok.shape[1] != self.context_length:
-            raise MdxError(f"TextEncoder: expected token ids [B, {self.context_length}], got {tuple(tok.shape)}")
+            raise MdxError(f"TextEncoder: expected token ids [B, {self.context_length}] or [B, n, {self.context_length}], "
+                           f"got {tuple(tok.shape)}")
         if not torch.cuda.is_available() or self.device.type != "cuda":
             raise MdxError("TextEncoder: the HIP device is required (no CPU fallback)")
         B = tok.shape[0]

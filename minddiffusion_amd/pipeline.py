@@ -18,6 +18,7 @@ from . import distributed as D
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
 from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
+from .ldm.modules.encoders import WINDOW, pad_conditioning
 
 
 class DiffusionPipeline:
@@ -39,6 +40,31 @@ class DiffusionPipeline:
         (wukong-huahua/inpaint.py:68-70); MindSpore's StandardNormal stream is not reproducible."""
         return torch.from_numpy(np.random.RandomState(seed).randn(batch, *shape).astype(np.float32))
 
+    def match_conditioning(self, c, uc, from_prompts=False):
+        """Long prompts ([B, n * 77, D], encoders.chunk_token_ids): the samplers run c and uc as ONE [2B, T, D] context, so both
+        need the same number of windows.  The shorter one is extended with the encoding of the empty window: with prompts= that
+        is uc's own row; with tensors the attached text encoder supplies it, and without one the caller has to
+        (encoders.pad_conditioning)."""
+        if c is None or uc is None or c.shape[1] == uc.shape[1]:
+            return c, uc
+        if from_prompts:
+            empty = uc[:1, :WINDOW]
+        elif getattr(self.model, "cond_stage_model", None) is not None:
+            empty = self.model.get_learned_conditioning([""])[:, :WINDOW]
+        else:
+            raise MdxError(f"DiffusionPipeline: c has {c.shape[1]} context tokens and uc {uc.shape[1]}, and no text encoder is "
+                           f"attached to encode the empty window: bring them to one length with "
+                           f"minddiffusion_amd.ldm.modules.encoders.pad_conditioning(c, uc, empty)")
+        return pad_conditioning(c, uc, empty)
+
+    def fit_context(self, c):
+        """Single rank: a context longer than the UNet's capacity raises the capacity to the next multiple of 80 (lengths in
+        between share plans; UNetModel.set_max_context_len drops the plans when the value changes)."""
+        unet = getattr(self.model, "unet", None)
+        T = int(c.shape[1])
+        if hasattr(unet, "set_max_context_len") and T > int(unet.max_context_len):
+            unet.set_max_context_len(80 * -(-T // 80))
+
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
                  decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
                  guidance_rescale=0.0):
@@ -51,7 +77,11 @@ class DiffusionPipeline:
         if prompts is not None and rank == 0:
             uc = self.model.get_learned_conditioning(len(prompts) * [""])   # txt2img.py:246-248
             c = self.model.get_learned_conditioning(list(prompts))            # txt2img.py:251
+        if rank == 0:
+            c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
         if n > 1:
+            # (the broadcast payload is sized by the UNet's capacity: for long prompts every rank calls
+            # unet.set_max_context_len beforehand; broadcast_conditioning's length check is the guard)
             B = len(prompts) if prompts is not None else (int(c.shape[0]) if c is not None else batch_size)
             if B is None:
                 raise MdxError("DiffusionPipeline: ranks without the conditioning tensor need prompts= or batch_size= "
@@ -76,6 +106,7 @@ class DiffusionPipeline:
             if uc is not None and uc.shape[0] == 1 and B > 1:
                 uc = uc.expand(B, -1, -1).contiguous()
             x_T = x_T.to(self.device)
+            self.fit_context(c)
         # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W
         local_b = int(c.shape[0])
         rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}   # (a caller's own sampler object)
@@ -120,11 +151,13 @@ class DiffusionPipeline:
             c = self.model.get_learned_conditioning(list(prompts))
         if c is None:
             raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
+        c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
         B = int(c.shape[0])
         c = c.to(self.device, torch.float16)
         uc = None if uc is None else uc.to(self.device, torch.float16)
         if uc is not None and uc.shape[0] == 1 and B > 1:
             uc = uc.expand(B, -1, -1).contiguous()
+        self.fit_context(c)
         # where the partial run starts: a grid index for PLMS / DDIM, a continuous time for DPM-Solver -- the last t_enc of the
         # full run's own `steps` intervals, t_0 + (T - t_0) * t_enc / steps
         if dpm:

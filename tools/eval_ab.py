@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ctx", type=int, default=77, help="context tokens (above 80 the UNet's max_context_len is raised to hold them)")
     ap.add_argument("--guidance", action="store_true", help="the batch is [uncond ; cond] of the same latents and the call says so "
                     "(forward_nhwc(cfg_dup=True)): arms can then differ in unet_cfg_dup")
     args = ap.parse_args()
@@ -52,7 +53,9 @@ def main():
         net = model.unet
         net.use_graph = True
         x = torch.randn(B, 4, h, h, device=dev)
-        ctx = torch.randn(B, 77, net.context_dim, device=dev, dtype=torch.float16)
+        if args.ctx > net.max_context_len:
+            net.set_max_context_len(args.ctx)
+        ctx = torch.randn(B, args.ctx, net.context_dim, device=dev, dtype=torch.float16)
         t = torch.full((B,), 501.0, device=dev)
         if args.guidance:
             x[B // 2:] = x[:B // 2]
@@ -77,7 +80,7 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / args.iters)
-    res = dict(model=args.model, batch=B, latent=h, arms={})
+    res = dict(model=args.model, batch=B, latent=h, ctx=args.ctx, arms={})
     base = None
     for name, opts in arms:
         ms = sorted(times[name])
@@ -85,7 +88,7 @@ def main():
         base = base or med
         res["arms"][name] = dict(options=opts, ms_per_eval_median=round(med, 4), ms_per_eval_min=round(ms[0], 4),
                                  all=[round(x, 4) for x in times[name]], launches=plans[name][3])
-        print(f"{args.model} B={B} latent={h}  {name:12s} {med:8.4f} ms / evaluation (min {ms[0]:.4f})  {100 * (med / base - 1):+.2f} %  "
+        print(f"{args.model} B={B} latent={h} ctx={args.ctx}  {name:12s} {med:8.4f} ms / evaluation (min {ms[0]:.4f})  {100 * (med / base - 1):+.2f} %  "
               f"ops {plans[name][3]}  {opts}", flush=True)
     if args.out:
         json.dump(res, open(args.out, "w"), indent=1)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Fused SpatialTransformer tail (mdx_st_tail_f16) vs the unfused launches it replaces, at a UNet level's real size, with COLD
 weights: NCOPY distinct weight sets are cycled (NCOPY x 3.3 MB > the 256 MB Infinity Cache), the whole cycle is one hipGraph,
-time = graph time / NCOPY.  Usage: stchain_bench.py [B tokens heads]"""
+time = graph time / NCOPY.  Usage: stchain_bench.py [B tokens heads]; CTX_LEN=154 sets the context length (default 77; the
+capacity is the length rounded up to a multiple of 8, at least 80)."""
 import os
 import sys
 
@@ -14,7 +15,8 @@ from minddiffusion_amd import ops  # noqa: E402
 
 DEV = "cuda:0"
 B, tokens, heads = (int(v) for v in (sys.argv[1:4] if len(sys.argv) >= 4 else (2, 4096, 5)))
-C, ctx_len, ctx_cap = 320, 77, 80
+C, ctx_len = 320, int(os.environ.get("CTX_LEN", "77"))
+ctx_cap = max(80, (ctx_len + 7) // 8 * 8)
 NCOPY = int(os.environ.get("NCOPY", "96"))
 REPS = int(os.environ.get("REPS", "1"))     # passes over the weight sets per graph (NCOPY=1 REPS=50: weights hot in L2)
 M = B * tokens
