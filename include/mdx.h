@@ -611,6 +611,28 @@ int mdx_q_sample_f32(const float* x0, const float* noise, float a, float b, cons
 int mdx_vae_encode_noised_f32(const void* moments, int ld, const float* post_noise, float scale_factor, float a, float b,
                               const float* noise, float* z0_out, float* xt_out, int B, int zc, int HW, mdx_stream_t s);
 
+/* ---- Per-sample seeded noise (not in the reference, whose draws are whole-batch ms.ops.StandardNormal calls).
+ * A counter-based generator: element e (0 <= e < n) of sample b is a pure function of (seeds[b], stream, draw, e) and of nothing
+ * else -- not B, not b, not the alignment of out, not the launch geometry.  seeds: B 64-bit values on the device; out: [B][n]
+ * contiguous, n = the elements of ONE sample (a latent: C * H * W, e = the NCHW flat index inside the sample).
+ *   words   Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53, 0xCD9E8D57; Weyl increments 0x9E3779B9,
+ *           0xBB67AE85; ten rounds), key = (seed & 0xffffffff, seed >> 32), counter = (e >> 2, draw, stream, 0); element e takes
+ *           word (e & 3) of the four output words.  mdx_philox_u32 stores that word as it is.
+ *   uniform U(w) = fmaf((float)(w >> 9), 2^-23, 2^-24) = (2 (w >> 9) + 1) * 2^-24: the 23-bit integer converts exactly and the
+ *           fma is exact, so 2^-24 <= U <= 1 - 2^-24 (the open interval) in fp32 and in fp64 alike.
+ *   normal  Box-Muller on the word pairs (0, 1) and (2, 3) of a counter: r = sqrtf(-2 logf(U(w_a))), (s, c) = sincospif(2 U(w_b))
+ *           with w_a the pair's first word; the EVEN element gets r * c (cosine), the ODD element r * s (sine).  |z| < 5.8.
+ *           mdx_randn_f32 stores scale * z.  Precise logf / sqrtf / sincospif: a float64 restatement agrees to 1e-5.
+ *   dropout (dropout_p > 0; plms.py:224-225 `ops.dropout(noise, p)`) element e is kept when U(word (e & 3) of the SAME counter
+ *           under stream | 0x80000000) >= dropout_p and then stores (scale * z) * (1 / (1 - dropout_p)); otherwise 0.
+ *           dropout_p == 0 runs a kernel without the second Philox call, so callers keep stream < 2^31.
+ * n % 4 == 0 with a 16-byte aligned out writes one 16-byte vector per lane, anything else one element per lane: the same bits for
+ * the same element.  MDX_E_INVALID (nothing launched) for a NULL pointer, B <= 0, n <= 0 or n > 2^34 (e >> 2 is a 32-bit counter
+ * word), dropout_p outside [0, 1), a scale that is not finite. */
+int mdx_philox_u32(const unsigned long long* seeds, unsigned stream, unsigned draw, unsigned* out, int B, long n, mdx_stream_t s);
+int mdx_randn_f32(const unsigned long long* seeds, unsigned stream, unsigned draw, float scale, float dropout_p, float* out, int B,
+                  long n, mdx_stream_t s);
+
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
  *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)

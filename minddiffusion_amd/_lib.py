@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("MDX_LIBRARY") or os.path.join(_HERE, "libmdx.so")
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
+c_uint = ctypes.c_uint
 c_long = ctypes.c_long
 c_float = ctypes.c_float
 c_size_t = ctypes.c_size_t
@@ -157,6 +158,8 @@ SIGNATURES = {
                                  c_int, c_void_p]),
     "mdx_vae_encode_noised_f32": (c_int, [c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
                                           c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_philox_u32": (c_int, [c_void_p, c_uint, c_uint, c_void_p, c_int, c_long, c_void_p]),
+    "mdx_randn_f32": (c_int, [c_void_p, c_uint, c_uint, c_float, c_float, c_void_p, c_int, c_long, c_void_p]),
     "mdx_softmax_rows_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_void_p]),
     "mdx_probe_mfma_32x32x16_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mdx_probe_mfma_16x16x32_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,176 @@
+// Per-sample seeded noise: Philox4x32-10 (Salmon et al., "Parallel Random Numbers: As Easy as 1, 2, 3", SC'11; the Random123
+// constants) as a counter-based generator, and Box-Muller normals on its words.  Every output element is a pure function of
+// (its sample's seed, stream, draw, its index inside the sample): the batch size, the row, the launch geometry and the
+// alignment of `out` do not enter (include/mdx.h has the counter layout and the uniform mapping).
+// One Philox call is ~40 integer instructions (ten rounds of two 32 x 32 -> 64 multiplies) for four elements, next to one
+// 16-byte store: the kernel stays bound by its stores.  Launch shape as qsample.hip: one-wave workgroups, a grid-stride loop,
+// one float4 per lane and iteration where n % 4 == 0 and `out` is 16-byte aligned, one float otherwise.
+// No fast-math flag and no fast intrinsic in this file: logf / sqrtf / sincospif are the precise ones, and the restatement in
+// tests/_seeded_util.py holds the result to 1e-5.
+#include <math.h>
+
+#include "mdx_common.h"
+
+namespace {
+
+constexpr int RNG_THREADS = 64;
+constexpr int RNG_MAX_BLOCKS = 4096;    // 256 CUs x 16 waves; larger tensors take further passes of the grid-stride loop
+
+constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
+constexpr unsigned PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+constexpr unsigned DROPOUT_STREAM_BIT = 0x80000000u;
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+struct Quad {
+    unsigned w[4];
+};
+
+// Philox4x32-10 of counter (c0, c1, c2, 0) under key (k0, k1)
+__device__ __forceinline__ Quad philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned k0, unsigned k1) {
+    unsigned c3 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+        const unsigned hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += PHILOX_W0;
+        k1 += PHILOX_W1;
+    }
+    Quad q;
+    q.w[0] = c0; q.w[1] = c1; q.w[2] = c2; q.w[3] = c3;
+    return q;
+}
+
+// word -> uniform in the open interval (0, 1): ((w >> 9) + 1/2) * 2^-23.  The conversion of a 23-bit integer and the fma are
+// both exact, so the value is (2 (w >> 9) + 1) * 2^-24 in every arithmetic: 2^-24 <= u <= 1 - 2^-24.
+__device__ __forceinline__ float uniform_open(unsigned w) {
+    return __builtin_fmaf((float)(w >> 9), 0x1p-23f, 0x1p-24f);
+}
+
+// Box-Muller on one word pair: the cosine branch is the even element's, the sine branch the odd one's
+__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& z_even, float& z_odd) {
+    const float r = sqrtf(-2.0f * logf(uniform_open(wa)));
+    float s, c;
+    sincospif(2.0f * uniform_open(wb), &s, &c);
+    z_even = r * c;
+    z_odd = r * s;
+}
+
+struct RngParams {
+    const unsigned long long* seeds;
+    void* out;              // [B][n] uint32 (MODE_U32) or fp32
+    unsigned stream, draw;
+    float scale, dropout_p, inv_keep;
+    unsigned long long n;   // elements of one sample
+    unsigned long long items;   // B * n / V
+};
+
+enum { MODE_U32 = 0, MODE_NORMAL = 1, MODE_NORMAL_DROPOUT = 2 };
+
+// The four elements 4 blk .. 4 blk + 3 of the sample with this seed; both launch forms go through here, so an element's bits do
+// not depend on the form that wrote it.
+template <int MODE>
+__device__ __forceinline__ void quad_values(const RngParams& p, unsigned long long seed, unsigned blk, unsigned (&bits)[4]) {
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    const Quad q = philox4x32_10(blk, p.draw, p.stream, k0, k1);
+    if constexpr (MODE == MODE_U32) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bits[e] = q.w[e];
+    } else {
+        float z[4], v[4];
+        box_muller(q.w[0], q.w[1], z[0], z[1]);
+        box_muller(q.w[2], q.w[3], z[2], z[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = p.scale * z[e];
+        if constexpr (MODE == MODE_NORMAL_DROPOUT) {
+            const Quad d = philox4x32_10(blk, p.draw, p.stream | DROPOUT_STREAM_BIT, k0, k1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = uniform_open(d.w[e]) >= p.dropout_p ? v[e] * p.inv_keep : 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bits[e] = __float_as_uint(v[e]);
+    }
+}
+
+// V == 4: item j is quad j % (n / 4) of sample j / (n / 4) (n % 4 == 0, out 16-byte aligned: the host decides);
+// V == 1: item j is element j % n of sample j / n, lane (element & 3) of its quad.
+template <int MODE, int V>
+__global__ __launch_bounds__(RNG_THREADS) void rng_kernel(const RngParams p) {
+    const unsigned long long per = p.n / V;
+    unsigned* out = reinterpret_cast<unsigned*>(p.out);     // fp32 results travel as their bit patterns
+    for (unsigned long long j = (unsigned long long)blockIdx.x * RNG_THREADS + threadIdx.x; j < p.items;
+         j += (unsigned long long)gridDim.x * RNG_THREADS) {
+        const unsigned long long b = j / per, i = j - b * per;
+        const unsigned long long seed = p.seeds[b];
+        unsigned v[4];
+        if constexpr (V == 4) {
+            quad_values<MODE>(p, seed, (unsigned)i, v);
+            u32x4 t;
+            t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
+            *reinterpret_cast<u32x4*>(out + j * 4) = t;
+        } else {
+            quad_values<MODE>(p, seed, (unsigned)(i >> 2), v);
+            const int lane = (int)(i & 3);
+            out[j] = lane == 0 ? v[0] : lane == 1 ? v[1] : lane == 2 ? v[2] : v[3];
+        }
+    }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+inline int rng_blocks(unsigned long long items) {
+    const unsigned long long blocks = (items + RNG_THREADS - 1) / RNG_THREADS;
+    return (int)(blocks < (unsigned long long)RNG_MAX_BLOCKS ? blocks : (unsigned long long)RNG_MAX_BLOCKS);
+}
+
+template <int MODE>
+void rng_launch(RngParams p, int B, hipStream_t s) {
+    if (p.n % 4 == 0 && aligned16(p.out)) {
+        p.items = (unsigned long long)B * (p.n / 4);
+        hipLaunchKernelGGL((rng_kernel<MODE, 4>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
+    } else {
+        p.items = (unsigned long long)B * p.n;
+        hipLaunchKernelGGL((rng_kernel<MODE, 1>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
+    }
+}
+
+constexpr long RNG_MAX_N = 1L << 34;    // element >> 2 is the counter's 32-bit word 0
+
+}  // namespace
+
+extern "C" int mdx_philox_u32(const unsigned long long* seeds, unsigned stream, unsigned draw, unsigned* out, int B, long n,
+                              mdx_stream_t s) {
+    MDX_REQUIRE(seeds && out, "mdx_philox_u32: null pointer");
+    MDX_REQUIRE(B > 0 && n > 0 && n <= RNG_MAX_N, "mdx_philox_u32: bad extents (B=%d n=%ld; 0 < n <= 2^34)", B, n);
+    RngParams p;
+    p.seeds = seeds; p.out = out;
+    p.stream = stream; p.draw = draw;
+    p.scale = 1.0f; p.dropout_p = 0.0f; p.inv_keep = 1.0f;
+    p.n = (unsigned long long)n; p.items = 0;
+    rng_launch<MODE_U32>(p, B, (hipStream_t)s);
+    MDX_LAUNCH_CHECK("mdx_philox_u32");
+    return MDX_OK;
+}
+
+extern "C" int mdx_randn_f32(const unsigned long long* seeds, unsigned stream, unsigned draw, float scale, float dropout_p,
+                             float* out, int B, long n, mdx_stream_t s) {
+    MDX_REQUIRE(seeds && out, "mdx_randn_f32: null pointer");
+    MDX_REQUIRE(B > 0 && n > 0 && n <= RNG_MAX_N, "mdx_randn_f32: bad extents (B=%d n=%ld; 0 < n <= 2^34)", B, n);
+    MDX_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "mdx_randn_f32: dropout_p must be in [0, 1), got %g", (double)dropout_p);
+    MDX_REQUIRE(isfinite(scale), "mdx_randn_f32: scale must be finite");
+    RngParams p;
+    p.seeds = seeds; p.out = out;
+    p.stream = stream; p.draw = draw;
+    p.scale = scale; p.dropout_p = dropout_p; p.inv_keep = 1.0f / (1.0f - dropout_p);
+    p.n = (unsigned long long)n; p.items = 0;
+    if (dropout_p > 0.0f)
+        rng_launch<MODE_NORMAL_DROPOUT>(p, B, (hipStream_t)s);
+    else
+        rng_launch<MODE_NORMAL>(p, B, (hipStream_t)s);
+    MDX_LAUNCH_CHECK("mdx_randn_f32");
+    return MDX_OK;
+}

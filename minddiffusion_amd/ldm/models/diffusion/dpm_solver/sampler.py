@@ -25,7 +25,7 @@ import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..plms import _first_tensor, check_guidance_rescale, noised_latent
+from ..plms import _first_tensor, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent
 from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
 
 
@@ -51,11 +51,12 @@ class DPMSolverSampler:
         t = self._check_t_start(t_start)
         return float(ns.marginal_alpha(t)), float(ns.marginal_std(t))
 
-    def stochastic_encode(self, x0, t_start, noise=None):
+    def stochastic_encode(self, x0, t_start, noise=None, seeds=None):
         """x0 noised to the continuous time t_start: marginal_alpha(t_start) x0 + marginal_std(t_start) noise.  One ops.q_sample
-        launch; a fresh tensor.  `noise` None: drawn from the sampler's generator."""
+        launch; a fresh tensor.  `noise` None: drawn per sample from `seeds` (ops.RNG_ENCODE), or without seeds from the sampler's
+        generator."""
         a, b = self.q_coefficients(t_start)
-        return noised_latent(x0, a, b, noise, self.generator)
+        return noised_latent(x0, a, b, noise, self.generator, seeds)
 
     def _eps_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
         if hasattr(self.model, "apply_model_nhwc"):
@@ -69,11 +70,14 @@ class DPMSolverSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, guidance_rescale=0., t_start=None, **kwargs):
+               unconditional_conditioning=None, guidance_rescale=0., t_start=None, seeds=None, **kwargs):
         """t_start: a continuous time in (1 / N, T] -- the S evaluations then cover [t_start, 1 / N] instead of [T, 1 / N], from
         x_T = stochastic_encode(., t_start) (the reference's DPM_Solver.sample(t_start=), dpm_solver.py:958-1075).  S == 1 is a
-        single first-order update."""
+        single first-order update.
+        seeds: `batch_size` ints, one per sample -- x_T (the only draw of this sampler) of sample b then depends on seeds[b]
+        alone (ops.randn_seeded); None: the sampler's generator."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        check_seed_sources(seeds, self.generator)
         if t_start is not None:
             t_start = self._check_t_start(t_start)
         if conditioning is None:
@@ -89,7 +93,10 @@ class DPMSolverSampler:
         dev = cond.device
         C, H, W = shape
         size = (batch_size, C, H, W)
-        if x_T is None:
+        seeds = check_seeds(seeds, batch_size, dev)
+        if x_T is None and seeds is not None:
+            img = ops.randn_seeded(seeds, ops.RNG_X_T, 0, (C, H, W))
+        elif x_T is None:
             img = torch.randn(size, device=dev, dtype=torch.float32, generator=self.generator)
         else:
             img = torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()

@@ -16,6 +16,9 @@ Results are identical in structure to the reference (S+1 UNet calls for PLMS, in
 callbacks once per step).
 img2img (not in the reference): ``stochastic_encode(x0, t_enc)`` + ``decode(x_t, cond, t_start)`` run the last t_start steps
 of the schedule through the same loop; the per-step mask blend of that path is one mdx_q_sample_f32 launch.
+Per-sample seeds (not in the reference): with ``seeds=`` every draw -- x_T, the eta > 0 step noise, the mask blend, the
+stochastic_encode noise -- is one mdx_randn_f32 launch keyed by the sample's own seed (ops.randn_seeded), so a sample does not
+depend on the batch it is served in; without it the sampler's generator draws for the whole batch, as before.
 """
 import os
 
@@ -42,13 +45,40 @@ def check_guidance_rescale(value):
     return phi
 
 
-def noised_latent(x0, a, b, noise, generator):
+def check_seed_sources(seeds, generator=None, **injected):
+    """A second source for the draws that `seeds=` covers -- the sampler's generator, or one of the test-injection keywords -- is a
+    caller's mistake: ValueError."""
+    if seeds is None:
+        return
+    if generator is not None:
+        raise ValueError("seeds= and a sampler generator are two sources for the same draws: pass one of them")
+    given = sorted(k for k, v in injected.items() if v is not None)
+    if given:
+        raise ValueError(f"seeds= and {', '.join(given)}= are two sources for the same draws: pass one of them")
+
+
+def check_seeds(seeds, batch, device):
+    """`seeds=` of the samplers: None stays None; otherwise the int64 device tensor of `batch` per-sample seeds
+    (ops.seeds_tensor)."""
+    if seeds is None:
+        return None
+    seeds = ops.seeds_tensor(seeds, device)
+    if seeds.shape[0] != batch:
+        raise MdxError(f"seeds: {seeds.shape[0]} seeds for a batch of {batch}")
+    return seeds
+
+
+def noised_latent(x0, a, b, noise, generator, seeds=None):
     """stochastic_encode of every sampler: a * x0 + b * noise as one ops.q_sample launch into a fresh tensor; `noise` None is
-    drawn from `generator`."""
+    drawn per sample from `seeds` (stream ops.RNG_ENCODE, draw 0), or without seeds from `generator`."""
     if not (isinstance(x0, torch.Tensor) and x0.is_cuda):
         raise MdxError("stochastic_encode: x0 must be a CUDA(HIP) tensor [B, C, H, W]")
     x0 = x0.to(torch.float32).contiguous()
-    if noise is None:
+    check_seed_sources(seeds, generator)
+    seeds = check_seeds(seeds, x0.shape[0], x0.device)
+    if noise is None and seeds is not None:
+        noise = ops.randn_seeded(seeds, ops.RNG_ENCODE, 0, tuple(x0.shape[1:]))
+    elif noise is None:
         noise = torch.randn(x0.shape, device=x0.device, dtype=torch.float32, generator=generator)
     noise = torch.as_tensor(noise).to(device=x0.device, dtype=torch.float32).contiguous()
     return ops.q_sample(x0, noise, a, b)
@@ -99,7 +129,9 @@ class _SamplerBase:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., **kwargs):
+               unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., seeds=None, **kwargs):
+        """seeds: `batch_size` ints, one per sample -- every draw of sample b (x_T, the eta > 0 step noise, the mask blend)
+        then depends on seeds[b] alone and not on the batch around it (ops.randn_seeded); None: the sampler's generator."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if conditioning is not None:
             cbs = _first_tensor(conditioning).shape[0]
@@ -122,7 +154,7 @@ class _SamplerBase:
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale)
+                                  blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale, seeds=seeds)
 
     # ---- img2img: upstream LDM's DDIMSampler.stochastic_encode / decode (neither reference tree has them).
     # t_enc / t_start count the model evaluations that REMAIN (1 .. S; PLMS spends one more on its first step): the partial run
@@ -149,19 +181,20 @@ class _SamplerBase:
             t = int(self.ddim_timesteps[self._check_t_start(t_enc, self.ddim_timesteps.shape[0]) - 1])
         return self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t]
 
-    def stochastic_encode(self, x0, t_enc, use_original_steps=False, noise=None):
+    def stochastic_encode(self, x0, t_enc, use_original_steps=False, noise=None, seeds=None):
         """x0 noised to where decode(t_start=t_enc) starts: sqrt(a) x0 + sqrt(1 - a) noise, a = ddim_alphas[t_enc - 1] (see the
         note above for the difference from upstream LDM, which uses index t_enc).  One ops.q_sample launch; a fresh tensor.
-        `noise` None: drawn from the sampler's generator."""
+        `noise` None: drawn per sample from `seeds` (ops.RNG_ENCODE), or without seeds from the sampler's generator."""
         a, b = self.q_coefficients(t_enc, use_original_steps)
-        return noised_latent(x0, a, b, noise, self.generator)
+        return noised_latent(x0, a, b, noise, self.generator, seeds)
 
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
                use_original_steps=False, callback=None, img_callback=None, mask=None, x0=None, guidance_rescale=0.,
-               log_every_t=100, **test_injection_kwargs):
+               log_every_t=100, seeds=None, **test_injection_kwargs):
         """The last t_start steps of the schedule make_schedule() set up (its eta included), from x_latent =
         stochastic_encode(., t_start): plms_sampling's loop on ts[:t_start].  t_start == S is sample(S, x_T=x_latent).
         mask / x0: 1 = keep x0 (the init latent), blended every step by one in-place ops.q_sample launch.
+        seeds: per-sample seeds of the step and blend draws, as sample() takes them.
         test_injection_kwargs: step_noises / blend_noises / dropout_masks, as sample() takes them.
         Returns (samples, intermediates)."""
         self._need_schedule("decode")
@@ -174,7 +207,7 @@ class _SamplerBase:
                                   callback=callback, img_callback=img_callback, mask=mask, x0=x0, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=False,
-                                  guidance_rescale=guidance_rescale, t_start=self._check_t_start(t_start, grid),
+                                  guidance_rescale=guidance_rescale, t_start=self._check_t_start(t_start, grid), seeds=seeds,
                                   **test_injection_kwargs)
 
     # ---- model call: prefer the NHWC fast path of our LatentDiffusion; any object with the reference's
@@ -195,11 +228,12 @@ class _SamplerBase:
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None):
+                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None):
         """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
         t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
         mask / x0 blend of every step is one ops.q_sample launch, in place."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        check_seed_sources(seeds, self.generator, step_noises=step_noises, blend_noises=blend_noises, dropout_masks=dropout_masks)
         if mask is not None and x0 is None:
             raise ValueError("mask blending needs x0 (plms.py:154)")
         # quantize_x0 / score_corrector (plms.py:199-201, 218-219) call into caller-supplied objects (a first stage with
@@ -255,7 +289,11 @@ class _SamplerBase:
             cond = torch.as_tensor(cond).to(dev)
             uc = None if uc is None else torch.as_tensor(uc).to(dev)
         b = shape[0]
-        if x_T is None:
+        # per-sample seeds: every draw below becomes one ops.randn_seeded launch, (stream, draw) = what it is for and which one
+        seeds = check_seeds(seeds, b, dev)
+        if x_T is None and seeds is not None:
+            img = ops.randn_seeded(seeds, ops.RNG_X_T, 0, tuple(shape[1:]))
+        elif x_T is None:
             img = torch.randn(shape, device=dev, dtype=torch.float32, generator=self.generator)
         else:
             img = torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()
@@ -385,7 +423,11 @@ class _SamplerBase:
                 eps_c = ops.nchw_to_nhwc(e_mod, (x.shape[1] + 7) // 8 * 8)
                 eps_u = None
             noise = None
-            if float(sigma_t) != 0.0:
+            if float(sigma_t) != 0.0 and seeds is not None:   # temperature and dropout inside the one launch
+                noise = ops.randn_seeded(seeds, ops.RNG_STEP, noise_count[0], tuple(x.shape[1:]), scale=temperature,
+                                         dropout=noise_dropout)
+                noise_count[0] += 1
+            elif float(sigma_t) != 0.0:
                 if step_noises is not None:   # tests inject the k-th N(0,1) draw to compare with the oracle (eta != 0)
                     noise = torch.as_tensor(step_noises[noise_count[0]]).to(device=dev, dtype=torch.float32) * temperature
                 else:
@@ -426,7 +468,9 @@ class _SamplerBase:
         for i, step_t in enumerate(time_range):
             index = total_steps - i - 1
             if mask is not None:                                     # plms.py:153-157 (WK: q_sample gets explicit noise)
-                if blend_noises is not None:                          # tests inject the draws to compare with the oracle
+                if seeds is not None:
+                    noise = ops.randn_seeded(seeds, ops.RNG_BLEND, i, tuple(shape[1:]))
+                elif blend_noises is not None:                        # tests inject the draws to compare with the oracle
                     noise = torch.as_tensor(blend_noises[i]).to(device=dev, dtype=torch.float32)
                 else:
                     noise = torch.randn(x0.shape, device=dev, dtype=torch.float32, generator=self.generator)

@@ -878,6 +878,70 @@ def vae_encode_noised(moments, zc, post_noise, scale_factor, a, b, noise, z0_out
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Per-sample seeded noise (include/mdx.h: mdx_philox_u32 / mdx_randn_f32, csrc/rng.hip).  `stream` says what a draw is for,
+# `draw` which one it is; these are the streams the samplers and the pipeline use (a stream is < 2^31: the top bit selects
+# the dropout decisions of the same stream).
+RNG_X_T = 0            # the start latent; draw 0
+RNG_STEP = 1           # the k-th stochastic step (eta > 0) of a run; draw k
+RNG_BLEND = 2          # the mask blend at loop index i; draw i
+RNG_ENCODE = 3         # the forward noise of stochastic_encode / img2img; draw 0
+RNG_POSTERIOR = 4      # the VAE posterior sample of img2img; draw 0
+
+
+def seeds_tensor(seeds, device):
+    """A sequence of Python ints in [-2^63, 2^64) (or an integer tensor) -> the int64 device tensor the kernels read.  A value
+    of 2^63 and above is stored as its two's-complement pattern: seed 2^64 - 1 and seed -1 are the same seed."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype.is_floating_point or seeds.dtype == torch.bool or seeds.dim() != 1:
+            raise _lib.MdxError(f"seeds: expected a 1-d integer tensor, got {seeds.dtype} {tuple(seeds.shape)}")
+        return seeds.to(device=device, dtype=torch.int64).contiguous()
+    vals = []
+    for s in seeds:
+        if isinstance(s, bool) or int(s) != s:
+            raise _lib.MdxError(f"seeds: {s!r} is not an integer")
+        s = int(s)
+        if not -(1 << 63) <= s < (1 << 64):
+            raise _lib.MdxError(f"seeds: {s} is outside [-2^63, 2^64)")
+        vals.append(s - (1 << 64) if s >= (1 << 63) else s)
+    return torch.tensor(vals, dtype=torch.int64, device=device)
+
+
+def _rng_args(name, seeds, stream, draw, sample_shape, out, dtype):
+    if not (isinstance(seeds, torch.Tensor) and seeds.dim() == 1):
+        raise _lib.MdxError(f"{name}: seeds must be a 1-d int64 device tensor (ops.seeds_tensor)")
+    _chk(seeds, torch.int64, "seeds"); _chk(out, dtype, "out")
+    if not (0 <= int(stream) < (1 << 31) and 0 <= int(draw) < (1 << 32)):
+        raise _lib.MdxError(f"{name}: stream must be in [0, 2^31) and draw in [0, 2^32), got {stream!r}, {draw!r}")
+    shape = (int(sample_shape),) if isinstance(sample_shape, int) else tuple(int(d) for d in sample_shape)
+    B, n = int(seeds.shape[0]), 1
+    for d in shape:
+        n *= d
+    if out is None:
+        out = torch.empty((B,) + shape, dtype=dtype, device=seeds.device)
+    elif tuple(out.shape) != (B,) + shape:
+        raise _lib.MdxError(f"{name}: out has shape {tuple(out.shape)}, expected {(B,) + shape}")
+    return out, B, n
+
+
+def philox_u32(seeds, stream, draw, sample_shape, out=None):
+    """The generator's raw 32-bit words, [B, *sample_shape] as int32 storage (bit patterns): element e of sample b is word
+    e & 3 of Philox4x32-10(counter (e >> 2, draw, stream, 0), key seeds[b])."""
+    out, B, n = _rng_args("philox_u32", seeds, stream, draw, sample_shape, out, torch.int32)
+    _lib.check(_lib.load().mdx_philox_u32(_ptr(seeds), int(stream), int(draw), _ptr(out), B, n, _stream()), "mdx_philox_u32")
+    return out
+
+
+def randn_seeded(seeds, stream, draw, sample_shape, scale=1.0, dropout=0.0, out=None):
+    """scale * N(0, 1) as [B, *sample_shape] fp32, sample b drawn from seeds[b] alone: the same (seed, stream, draw, element)
+    gives the same bits whatever the batch, the row or the rank.  dropout p > 0: zero with probability p, the rest scaled by
+    1 / (1 - p) (plms.py:224-225), decided by the same counter under stream | 2^31.  One launch."""
+    out, B, n = _rng_args("randn_seeded", seeds, stream, draw, sample_shape, out, f32)
+    _lib.check(_lib.load().mdx_randn_f32(_ptr(seeds), int(stream), int(draw), float(scale), float(dropout), _ptr(out), B, n,
+                                         _stream()), "mdx_randn_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Row-local fused SpatialTransformer tail (include/mdx.h: mdx_st_tail_f16, csrc/stchain.hip)
 def pack_frag_weight(w2d):
     """[N, K] nn.Dense weight -> MFMA-fragment-major pieces [N/32 column tiles][K/16 k-steps][64 lanes * 8 halves]:

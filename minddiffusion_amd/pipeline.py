@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import distributed as D
+from . import ops
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
 from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
@@ -39,6 +40,20 @@ class DiffusionPipeline:
         """numpy RandomState(seed).randn -- the reference's own practice for reproducible x_T
         (wukong-huahua/inpaint.py:68-70); MindSpore's StandardNormal stream is not reproducible."""
         return torch.from_numpy(np.random.RandomState(seed).randn(batch, *shape).astype(np.float32))
+
+    @staticmethod
+    def check_seeds(seeds, batch):
+        """`seeds=`: one int per sample of the GLOBAL batch (a sequence or a 1-d tensor); returned as a list, None stays None."""
+        if seeds is None:
+            return None
+        seeds = seeds.tolist() if isinstance(seeds, torch.Tensor) else list(seeds)
+        if len(seeds) != batch:
+            raise MdxError(f"DiffusionPipeline: {len(seeds)} seeds for a global batch of {batch}")
+        return seeds
+
+    def seeded_noise(self, seeds, stream, shape):
+        """N(0, 1) [len(seeds), *shape] on the pipeline's device, sample b from seeds[b] alone (ops.randn_seeded, draw 0)."""
+        return ops.randn_seeded(ops.seeds_tensor(seeds, self.device), stream, 0, tuple(shape))
 
     def match_conditioning(self, c, uc, from_prompts=False):
         """Long prompts ([B, n * 77, D], encoders.chunk_token_ids): the samplers run c and uc as ONE [2B, T, D] context, so both
@@ -67,9 +82,12 @@ class DiffusionPipeline:
 
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
                  decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
-                 guidance_rescale=0.0):
+                 guidance_rescale=0.0, seeds=None):
         """Multi-rank runs: every rank calls with the same `prompts` list (or the same `batch_size` when rank 0 passes
         precomputed (c, uc) tensors); only rank 0's c / uc / x_T are used, the other ranks may pass None.
+        seeds: one int per sample of the global batch, every rank the same list: sample b's x_T and step noise then depend on
+        seeds[b] alone -- not on the batch it is served in, its row or its rank (ops.randn_seeded).  None: `seed`, one
+        RandomState draw for the whole batch.
         guidance_rescale in [0, 1]: the samplers' keyword (CFG rescale for v-prediction checkpoints), every rank the same."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         rank, n = D.world()
@@ -87,8 +105,12 @@ class DiffusionPipeline:
                 raise MdxError("DiffusionPipeline: ranks without the conditioning tensor need prompts= or batch_size= "
                                "(the global batch) to size the broadcast")
             unet = self.model.unet
-            if rank == 0 and x_T is None:
-                x_T = self.start_noise(B, shape, seed)
+            seeds = self.check_seeds(seeds, B)
+            if rank == 0 and x_T is None:     # the global x_T rides the one broadcast, seeded or not
+                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
+            if seeds is not None:
+                lo, hi = D.shard_bounds(B, rank, n)
+                seeds = seeds[lo:hi]
             to_dev = lambda t: None if t is None else t.to(self.device)
             # exactly ONE collective: T, the uc form and the noise flag ride in the payload header (distributed.py)
             c, uc, x_T = D.broadcast_conditioning(
@@ -99,8 +121,9 @@ class DiffusionPipeline:
             if c is None:
                 raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
             B = int(c.shape[0])
+            seeds = self.check_seeds(seeds, B)
             if x_T is None:
-                x_T = self.start_noise(B, shape, seed)
+                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
             c = c.to(self.device, torch.float16)
             uc = None if uc is None else uc.to(self.device, torch.float16)
             if uc is not None and uc.shape[0] == 1 and B > 1:
@@ -110,10 +133,11 @@ class DiffusionPipeline:
         # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W
         local_b = int(c.shape[0])
         rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}   # (a caller's own sampler object)
+        seeds_kw = {} if seeds is None else {"seeds": seeds}        # this rank's samples: the eta > 0 step draws
         samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=local_b, shape=shape, verbose=False,
                                              unconditional_guidance_scale=scale, unconditional_conditioning=uc,
                                              eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
-                                             **rescale_kw)
+                                             **rescale_kw, **seeds_kw)
         if decode:
             x = self.model.decode_first_stage(samples)                # txt2img.py:265-266
             samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
@@ -123,7 +147,7 @@ class DiffusionPipeline:
 
     def img2img(self, init_image=None, init_latent=None, strength=0.75, prompts=None, c=None, uc=None, steps=50, scale=9.0,
                 eta=0.0, seed=42, noise=None, post_noise=None, sample_posterior=True, mask=None, decode=False, callback=None,
-                img_callback=None, guidance_rescale=0.0):
+                img_callback=None, guidance_rescale=0.0, seeds=None):
         """Start from an image instead of pure noise: encode it, noise the latent to the level `strength` selects, and run only
         the remaining t_enc = int(strength * steps) of the `steps`-step schedule (strength 1: all of them).
 
@@ -131,7 +155,9 @@ class DiffusionPipeline:
         (already scaled by model.scale_factor): exactly one of them.  noise / post_noise: the N(0, 1) draws of the forward
         process and of the VAE posterior at the latent's shape; None = numpy RandomState(seed) / RandomState(seed + 1), as
         start_noise().  sample_posterior False: the posterior's mode.  mask [B, 1, h, w] at latent resolution, 1 = keep the
-        init image there (PLMS / DDIM only).  Conditioning, decode and guidance_rescale as in __call__.  Single rank only."""
+        init image there (PLMS / DDIM only).  Conditioning, decode and guidance_rescale as in __call__.  Single rank only.
+        seeds: one int per sample; the forward noise (ops.RNG_ENCODE), the posterior noise (ops.RNG_POSTERIOR) and the step and
+        blend draws of sample b then depend on seeds[b] alone.  A passed noise / post_noise still wins."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
@@ -153,6 +179,7 @@ class DiffusionPipeline:
             raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
         c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
         B = int(c.shape[0])
+        seeds = self.check_seeds(seeds, B)
         c = c.to(self.device, torch.float16)
         uc = None if uc is None else uc.to(self.device, torch.float16)
         if uc is not None and uc.shape[0] == 1 and B > 1:
@@ -167,32 +194,44 @@ class DiffusionPipeline:
         else:
             self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
             a, b = self.sampler.q_coefficients(t_enc)
-        draw = lambda given, shape, sd: (torch.from_numpy(np.random.RandomState(sd).randn(*shape).astype(np.float32))
-                                         if given is None else given)
+        def draw(given, shape, sd, stream):
+            if given is not None:
+                return given
+            if seeds is not None:
+                return self.seeded_noise(seeds, stream, shape[1:])
+            return torch.from_numpy(np.random.RandomState(sd).randn(*shape).astype(np.float32))
         if init_image is not None:
             vae = self.model.first_stage_model
             if vae is None or not hasattr(vae, "encode_noised"):
                 raise MdxError("img2img(init_image=) needs a VAE with an encoder attached (model.first_stage_model)")
             x = init_image.to(device=self.device, dtype=torch.float32)
             shape = vae.latent_shape(x.shape)                         # the encoder's output size, not H // 8
-            z0, x_enc = vae.encode_noised(x, self.model.scale_factor, a, b, draw(noise, shape, seed),
-                                          post_noise=draw(post_noise, shape, seed + 1) if sample_posterior else None,
+            if seeds is not None and x.shape[0] != B:
+                raise MdxError(f"img2img: {x.shape[0]} init images but {B} conditionings")
+            z0, x_enc = vae.encode_noised(x, self.model.scale_factor, a, b, draw(noise, shape, seed, ops.RNG_ENCODE),
+                                          post_noise=(draw(post_noise, shape, seed + 1, ops.RNG_POSTERIOR)
+                                                      if sample_posterior else None),
                                           sample=sample_posterior)
         else:
             z0 = init_latent.to(device=self.device, dtype=torch.float32).contiguous()
-            x_enc = self.sampler.stochastic_encode(z0, start if dpm else t_enc, noise=draw(noise, z0.shape, seed))
+            if seeds is not None and z0.shape[0] != B:
+                raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
+            x_enc = self.sampler.stochastic_encode(z0, start if dpm else t_enc,
+                                                   noise=draw(noise, z0.shape, seed, ops.RNG_ENCODE))
         if z0.shape[0] != B:
             raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
         rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
+        seeds_kw = {} if seeds is None else {"seeds": seeds}
         if dpm:
             samples, _ = self.sampler.sample(S=t_enc, conditioning=c, batch_size=B, shape=list(z0.shape[1:]), verbose=False,
                                              unconditional_guidance_scale=scale, unconditional_conditioning=uc, x_T=x_enc,
-                                             callback=callback, img_callback=img_callback, t_start=start, **rescale_kw)
+                                             callback=callback, img_callback=img_callback, t_start=start, **rescale_kw,
+                                             **seeds_kw)
         else:
             blend_kw = {} if mask is None else {"mask": mask, "x0": z0}
             samples, _ = self.sampler.decode(x_enc, c, t_enc, unconditional_guidance_scale=scale,
                                              unconditional_conditioning=uc, callback=callback, img_callback=img_callback,
-                                             **blend_kw, **rescale_kw)
+                                             **blend_kw, **rescale_kw, **seeds_kw)
         if decode:
             x = self.model.decode_first_stage(samples)
             samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)

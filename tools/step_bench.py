@@ -9,6 +9,11 @@ Both in the steady state of a PLMS run (order 3: three eps histories read, e_t /
 `--launches` launches of each entry are captured into a hipGraph (so the host's enqueue rate is not what is measured), the two
 graphs are replayed alternately `--rounds` times after a warm-up, each replay between two hip events.  Reported per launch:
 median over rounds of (replay time / launches), and rescale - pred, which is what a step gains by turning the rescale on.
+
+--noise measures, the same way, what a stochastic step (eta > 0) spends on its noise tensor in front of the step launch:
+  torch_t / torch_td    the torch sequence of the samplers without seeds: randn, * temperature (t), and with noise_dropout
+                        rand, >=, cast, * keep, / (1 - p) on top (td): 2 and 7 launches
+  seeded_t / seeded_td  the one mdx_randn_f32 launch of ops.randn_seeded(scale=temperature[, dropout=p])
 Prints one JSON line (and writes --out)."""
 import argparse
 import json
@@ -37,6 +42,40 @@ def bench_shape(shape, launches, rounds, warmup):
     args = (x, None, out_u, out_c, 8, 7.5, ops.PRED_V, 0.8, 0.6, olds, coef, 0.55, 0.83, 0.6, 0.8, 0.0, None, e_out, x_prev,
             p_out)
     entries = {"pred": lambda: ops.sampler_step_pred(*args), "rescale": lambda: ops.sampler_step_rescale(*args, 0.7)}
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    res["extra_us"] = round(res["rescale_us"] - res["pred_us"], 3)
+    return res
+
+
+def bench_noise(shape, launches, rounds, warmup):
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    temperature, p = 0.8, 0.25
+    seeds = ops.seeds_tensor(list(range(100, 100 + shape[0])), dev)
+    out = torch.empty(shape, device=dev)
+    draw = [0]
+
+    def torch_t():
+        return torch.randn(shape, device=dev, dtype=torch.float32) * temperature
+
+    def torch_td():      # the statements of the samplers' step() (ldm/models/diffusion/plms.py)
+        noise = torch.randn(shape, device=dev, dtype=torch.float32) * temperature
+        keep = (torch.rand(shape, device=dev) >= p).to(torch.float32)
+        return noise * keep / (1. - p)
+
+    def seeded(dropout):
+        draw[0] += 1     # a new draw per launch, as in a run
+        return ops.randn_seeded(seeds, ops.RNG_STEP, draw[0], shape[1:], scale=temperature, dropout=dropout, out=out)
+    entries = {"torch_t": torch_t, "seeded_t": lambda: seeded(0.0), "torch_td": torch_td, "seeded_td": lambda: seeded(p)}
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    res["saved_t_us"] = round(res["torch_t_us"] - res["seeded_t_us"], 3)
+    res["saved_td_us"] = round(res["torch_td_us"] - res["seeded_td_us"], 3)
+    return res
+
+
+def time_entries(shape, entries, launches, rounds, warmup):
+    import torch
     graphs = {}
     for name, fn in entries.items():
         fn()
@@ -63,7 +102,6 @@ def bench_shape(shape, launches, rounds, warmup):
         res[name + "_us"] = round(statistics.median(v), 3)
         res[name + "_us_min"] = round(min(v), 3)
         res[name + "_us_max"] = round(max(v), 3)
-    res["extra_us"] = round(res["rescale_us"] - res["pred_us"], 3)
     return res
 
 
@@ -72,13 +110,16 @@ def main():
     ap.add_argument("--launches", type=int, default=300)
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--noise", action="store_true", help="measure the stochastic step's noise preparation instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("step_bench: needs a GPU")
     res = {"launches": a.launches, "rounds": a.rounds,
-           "shapes": [bench_shape(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
+           "shapes": [(bench_noise if a.noise else bench_shape)(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
+    if a.noise:
+        res["what"] = "noise preparation of a stochastic step, us per step"
     line = json.dumps(res)
     print(line)
     if a.out:
