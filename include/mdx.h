@@ -611,6 +611,46 @@ int mdx_q_sample_f32(const float* x0, const float* noise, float a, float b, cons
 int mdx_vae_encode_noised_f32(const void* moments, int ld, const float* post_noise, float scale_factor, float a, float b,
                               const float* noise, float* z0_out, float* xt_out, int B, int zc, int HW, mdx_stream_t s);
 
+/* ---- Inpainting: the work around the sampler (wukong-huahua/inpaint.py:39-63, 76-85, 110-115; csrc/inpaint.hip).
+ * Everything NCHW fp32 and contiguous unless said otherwise.  Mask convention (inpaint.py:51-55): a value >= 0.5 is the hole
+ * (repaint), m = (mask >= 0.5); a mask of batch mask_b == 1 is shared by all B samples (make_batch_sd repeats it).
+ * 16-byte accesses where the plane size is a multiple of 4 and the pointers are 16-byte aligned, scalar ones otherwise.
+ * Every entry refuses, before any launch: null pointers (other than the ones documented as optional), non-positive extents, a
+ * mask / alpha batch that is neither 1 nor B.  None of them writes outside its output.
+ *
+ * masked image (inpaint.py:55): out[b][c][p] = image[b][c][p] * (mask[mask_b == 1 ? 0 : b][0][p] < 0.5 ? 1 : 0), bit for bit the
+ * torch expression image * (mask < 0.5).  image, out [B][C][HW]; mask [mask_b][1][HW]. */
+int mdx_inpaint_mask_image_f32(const float* image, const float* mask, int mask_b, float* out, int B, int C, int HW,
+                               mdx_stream_t s);
+
+/* c_concat of the hybrid UNet, one launch after the encoder (inpaint.py:76-85): out [B][1 + zc][h][w] with
+ *   channel 0      = m[(i * H) / h][(j * W) / w]  (integer arithmetic: ResizeNearestNeighbor, align_corners = False, of the
+ *                    binarised [mask_b][1][H][W] mask; F.interpolate(mode="nearest") for integer ratios)
+ *   channels 1..zc = scale_factor * (mean + exp(0.5 * clip(logvar, -30, 20)) * post_noise)   (post_noise NULL: the mode)
+ * moments as mdx_vae_gaussian_sample_f32 takes them (NHWC fp16 [B][h * w][ld], ld >= 2 zc), post_noise [B][zc][h][w].
+ * Channels 1..zc are mdx_vae_encode_noised_f32's z0_out bit for bit (the same statements in the same order).  zc == 0 (moments
+ * may then be NULL) writes the resized mask alone, [B][1][h][w]. */
+int mdx_inpaint_concat_f32(const void* moments, int ld, const float* post_noise, float scale_factor, const float* mask,
+                           int mask_b, int H, int W, float* out, int B, int zc, int h, int w, mdx_stream_t s);
+
+/* Soft compositing weight: alpha = min(max(m, G * m), 1), m the binarised mask [Bm][1][H][W], G the separable Gaussian whose
+ * 2 * radius + 1 normalised taps `weights` (device fp32; the caller computes them in float64) are applied along rows, then along
+ * columns, with replicate edges.  Inside the hole alpha is exactly 1; the ramp extends outward only.  out [Bm][1][H][W] must not
+ * overlap mask.  0 <= radius <= 48.  One launch: a 32 x 32 output tile with its halo lives in LDS. */
+int mdx_mask_feather_f32(const float* mask, const float* weights, int radius, float* out, int Bm, int H, int W,
+                         mdx_stream_t s);
+
+/* Output stage after the decoder (inpaint.py:110-115), one launch:
+ *   t = alpha * decoded + (1 - alpha) * image   (computed as fma(alpha, decoded, (1 - alpha) * image); alpha NULL: t = decoded
+ *                                                and image is not read)
+ *   v = clamp((t + 1) / 2, 0, 1)
+ * out_f32 NCHW [B][C][H][W] = v;  out_u8 NHWC [B][H][W][C] = (uint8)(v * 255.0f) (truncation, inpaint.py:112-115).  Either
+ * output may be NULL, not both.  decoded, image [B][C][H][W]; alpha [alpha_b][1][H][W], alpha_b 1 or B.  Where alpha is 0 the
+ * result is clamp((image + 1) / 2, 0, 1) and where it is 1 (or NULL) clamp((decoded + 1) / 2, 0, 1), bit for bit.  out_f32
+ * must not overlap an input (refused). */
+int mdx_inpaint_composite_f32(const float* decoded, const float* image, const float* alpha, int alpha_b, float* out_f32,
+                              unsigned char* out_u8, int B, int C, int H, int W, mdx_stream_t s);
+
 /* ---- Per-sample seeded noise (not in the reference, whose draws are whole-batch ms.ops.StandardNormal calls).
  * A counter-based generator: element e (0 <= e < n) of sample b is a pure function of (seeds[b], stream, draw, e) and of nothing
  * else -- not B, not b, not the alignment of out, not the launch geometry.  seeds: B 64-bit values on the device; out: [B][n]

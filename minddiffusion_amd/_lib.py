@@ -158,6 +158,12 @@ SIGNATURES = {
                                  c_int, c_void_p]),
     "mdx_vae_encode_noised_f32": (c_int, [c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
                                           c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_inpaint_mask_image_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_inpaint_concat_f32": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                       c_int, c_int, c_int, c_void_p]),
+    "mdx_mask_feather_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mdx_inpaint_composite_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_int, c_void_p]),
     "mdx_philox_u32": (c_int, [c_void_p, c_uint, c_uint, c_void_p, c_int, c_long, c_void_p]),
     "mdx_randn_f32": (c_int, [c_void_p, c_uint, c_uint, c_float, c_float, c_void_p, c_int, c_long, c_void_p]),
     "mdx_softmax_rows_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_void_p]),

@@ -112,3 +112,16 @@ class AutoencoderKL:
         to_dev = lambda t: torch.as_tensor(t).to(device=mom.device, dtype=torch.float32).contiguous()
         return ops.vae_encode_noised(mom, self.embed_dim, to_dev(post_noise) if sample else None, scale_factor, a, b,
                                      to_dev(noise), z0, x_t)
+
+    def encode_concat(self, masked_image, mask, scale_factor, post_noise=None, sample=True):
+        """Inpainting conditioning (inpaint.py:76-85): the encoder on the masked image, then ONE launch (mdx_inpaint_concat_f32)
+        that writes c_concat [B, 1 + embed_dim, h, w] = cat(mask at the latent grid, scale_factor * posterior sample).  mask
+        [1 | B, 1, H, W], >= 0.5 = hole, resized by the integer nearest rule; post_noise / sample: encode()'s `noise` / `sample`.
+        The latent channels are encode_noised's z0 bit for bit.  A fresh tensor."""
+        mom = self.encoder(masked_image)
+        shape = self.latent_shape(masked_image.shape)
+        if sample and post_noise is None:
+            post_noise = torch.randn(shape, device=mom.device, dtype=torch.float32, generator=self.generator)
+        to_dev = lambda t: torch.as_tensor(t).to(device=mom.device, dtype=torch.float32).contiguous()
+        return ops.inpaint_concat(mom, self.embed_dim, to_dev(post_noise) if sample else None, scale_factor, to_dev(mask),
+                                  shape[2:])

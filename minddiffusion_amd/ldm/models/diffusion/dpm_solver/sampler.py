@@ -14,6 +14,9 @@ A `parameterization: "v"` model goes through ``mdx_sampler_step_pred_f32``, whic
 e = alpha_s v + sigma_s x (the reference's model_wrapper for model_type "v", dpm_solver.py:281-284) in the same launch.
 `guidance_rescale` != 0 with guidance on goes through ``mdx_sampler_step_rescale_f32``: the CFG-combined output (eps or v)
 is rescaled per sample to the conditional output's std in the same launch (not in the reference).
+Hybrid (inpainting) conditioning -- {"c_concat": ..., "c_crossattn": ...}, the dict forms PLMSSampler takes, an unconditional
+c_concat of its own included -- is not in the reference's DPM-Solver wiring: the c_concat channels are written into the UNet's
+input batch once, only the latent channels are refreshed per step.  `mask` / `x0` blending stays with PLMS / DDIM.
 Differences from the reference, both on the fp32 side of its fp16 arithmetic: the time grid and the schedule scalars
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
@@ -82,6 +85,16 @@ class DPMSolverSampler:
             t_start = self._check_t_start(t_start)
         if conditioning is None:
             raise MdxError("DPMSolverSampler: conditioning is required (classifier-free guidance on a text-conditional UNet)")
+        # hybrid (inpainting) conditioning, the dict forms PLMSSampler takes: {"c_concat": mask + masked-image latent,
+        # "c_crossattn": text}; the unconditional dict may carry a c_concat of its own (WK plms.py:191-201 concatenates every key)
+        c_cat = uc_cat = None
+        if isinstance(conditioning, dict) and "c_concat" in conditioning:
+            c_cat = _first_tensor(conditioning["c_concat"])
+            conditioning = conditioning["c_crossattn"]
+            if isinstance(unconditional_conditioning, dict):
+                if unconditional_conditioning.get("c_concat") is not None:
+                    uc_cat = _first_tensor(unconditional_conditioning["c_concat"])
+                unconditional_conditioning = unconditional_conditioning["c_crossattn"]
         cond = _first_tensor(conditioning)
         if cond.shape[0] != batch_size:
             print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
@@ -104,12 +117,20 @@ class DPMSolverSampler:
         scale = float(unconditional_guidance_scale)
         use_cfg = not (uc is None or scale == 1.)                   # model_wrapper :316-317
         b = batch_size
+        nb = 2 * b if use_cfg else b
         if use_cfg:
             c_in = torch.cat([uc.to(cond.dtype), cond], 0).contiguous()   # [uncond; cond] (:320-322), built once
             x_in = torch.empty((2 * b, C, H, W), device=dev, dtype=torch.float32)
         else:
             c_in, x_in = cond.contiguous(), None
-        nb = 2 * b if use_cfg else b
+        if c_cat is not None:       # DiffusionWrapper 'hybrid': cat(x, c_concat) -- written once, the C latent channels per step
+            cc = c_cat.to(device=dev, dtype=torch.float32)
+            x_in = torch.empty((nb, C + int(cc.shape[1]), H, W), device=dev, dtype=torch.float32)
+            x_in[nb - b:, C:] = cc                                        # batch = [uncond ; cond]
+            if use_cfg:
+                x_in[:b, C:] = cc if uc_cat is None else uc_cat.to(device=dev, dtype=torch.float32)
+        # the two halves of a guidance batch are the same UNet input unless the unconditional branch has its own c_concat
+        same_halves = c_cat is None or uc_cat is None
 
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
         plan = multistep_2m_plan(ns, S, order=2 if S >= 2 else 1, lower_order_final=True, t_start=t_start)
@@ -124,10 +145,17 @@ class DPMSolverSampler:
         v_pred = getattr(self.model, "parameterization", "eps") == "v"
         for k, p in enumerate(plan):
             if use_cfg:
-                x_in[:b].copy_(img)
-                x_in[b:].copy_(img)
-                eps = self._eps_nhwc(x_in, t_all[k], c_in, None if temb_all is None else temb_all[k], cfg_dup=True)
+                if c_cat is None:
+                    x_in[:b].copy_(img)
+                    x_in[b:].copy_(img)
+                else:
+                    x_in[:b, :C].copy_(img)
+                    x_in[b:, :C].copy_(img)
+                eps = self._eps_nhwc(x_in, t_all[k], c_in, None if temb_all is None else temb_all[k], cfg_dup=same_halves)
                 eps_u, eps_c = eps[:b], eps[b:]
+            elif c_cat is not None:
+                x_in[:, :C].copy_(img)
+                eps_u, eps_c = None, self._eps_nhwc(x_in, t_all[k], c_in, None if temb_all is None else temb_all[k])
             else:
                 eps_u, eps_c = None, self._eps_nhwc(img, t_all[k], c_in, None if temb_all is None else temb_all[k])
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]

@@ -1,8 +1,10 @@
 """Thin torch-tensor wrappers over the C-ABI (include/mdx.h).  torch supplies device memory and
 the current HIP stream; all arithmetic happens in libmdx.so.  No CPU fallbacks."""
 import ctypes
+import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -875,6 +877,140 @@ def vae_encode_noised(moments, zc, post_noise, scale_factor, a, b, noise, z0_out
                                                      float(b), _ptr(noise), _ptr(z0_out), _ptr(xt_out), B, zc, HW, _stream()),
                "mdx_vae_encode_noised_f32")
     return z0_out, xt_out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Inpainting: the work around the sampler (include/mdx.h: mdx_inpaint_* / mdx_mask_feather_f32, csrc/inpaint.hip).
+# A mask value >= 0.5 is the hole; a mask (or alpha) of batch 1 is shared by the whole batch.
+FEATHER_MAX_RADIUS = 48
+_FEATHER_TAPS = {}
+
+
+def _plane_mask(name, t, B, H, W):
+    """[1 | B, 1, H, W] fp32 -> its batch."""
+    _chk(t, f32, name)
+    if t.dim() != 4 or t.shape[0] not in (1, B) or tuple(t.shape[1:]) != (1, H, W):
+        raise _lib.MdxError(f"{name}: shape {tuple(t.shape)}, expected [1 or {B}, 1, {H}, {W}]")
+    return int(t.shape[0])
+
+
+def inpaint_mask_image(image, mask, out=None):
+    """image * (mask < 0.5) (inpaint.py:55): image [B, C, H, W], mask [1 | B, 1, H, W], NCHW fp32.  One launch."""
+    _chk(image, f32, "image"); _chk(out, f32, "out")
+    if image.dim() != 4:
+        raise _lib.MdxError(f"image: expected [B, C, H, W], got shape {tuple(image.shape)}")
+    B, C, H, W = image.shape
+    mask_b = _plane_mask("mask", mask, B, H, W)
+    if out is None:
+        out = torch.empty_like(image)
+    _same_shape(image, "out", out)
+    _lib.check(_lib.load().mdx_inpaint_mask_image_f32(_ptr(image), _ptr(mask), mask_b, _ptr(out), B, C, H * W, _stream()),
+               "mdx_inpaint_mask_image_f32")
+    return out
+
+
+def inpaint_concat(moments, zc, post_noise, scale_factor, mask, hw, out=None):
+    """c_concat [B, 1 + zc, h, w] of the hybrid UNet in one launch (inpaint.py:76-85): channel 0 the binarised mask
+    [1 | B, 1, H, W] at the latent grid hw = (h, w) (nearest, integer arithmetic), channels 1.. scale_factor * the posterior
+    sample of the encoder moments NHWC fp16 [B, h * w, ld] (post_noise [B, zc, h, w], None: the mode) -- bit for bit
+    vae_encode_noised's z0."""
+    _chk(moments, f16, "moments"); _chk(post_noise, f32, "post_noise"); _chk(out, f32, "out")
+    B, HW, ld = moments.shape
+    h, w = int(hw[0]), int(hw[1])
+    if h * w != HW:
+        raise _lib.MdxError(f"inpaint_concat: latent grid {h} x {w} does not match moments [{B}, {HW}, {ld}]")
+    if mask.dim() != 4:
+        raise _lib.MdxError(f"mask: expected [1 or {B}, 1, H, W], got shape {tuple(mask.shape)}")
+    H, W = int(mask.shape[2]), int(mask.shape[3])
+    mask_b = _plane_mask("mask", mask, B, H, W)
+    if out is None:
+        out = torch.empty((B, 1 + zc, h, w), dtype=f32, device=moments.device)
+    elif tuple(out.shape) != (B, 1 + zc, h, w):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(B, 1 + zc, h, w)}")
+    if post_noise is not None and tuple(post_noise.shape) != (B, zc, h, w):
+        raise _lib.MdxError(f"post_noise: shape {tuple(post_noise.shape)}, expected {(B, zc, h, w)}")
+    _lib.check(_lib.load().mdx_inpaint_concat_f32(_ptr(moments), ld, _ptr(post_noise), float(scale_factor), _ptr(mask), mask_b,
+                                                  H, W, _ptr(out), B, zc, h, w, _stream()), "mdx_inpaint_concat_f32")
+    return out
+
+
+def inpaint_resize_mask(mask, hw, out=None):
+    """The binarised mask [Bm, 1, H, W] at the grid hw = (h, w), [Bm, 1, h, w]: channel 0 of inpaint_concat alone (zc = 0)."""
+    if mask.dim() != 4:
+        raise _lib.MdxError(f"mask: expected [B, 1, H, W], got shape {tuple(mask.shape)}")
+    Bm, _, H, W = mask.shape
+    _plane_mask("mask", mask, Bm, H, W); _chk(out, f32, "out")
+    h, w = int(hw[0]), int(hw[1])
+    if out is None:
+        out = torch.empty((Bm, 1, h, w), dtype=f32, device=mask.device)
+    elif tuple(out.shape) != (Bm, 1, h, w):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(Bm, 1, h, w)}")
+    _lib.check(_lib.load().mdx_inpaint_concat_f32(None, 0, None, 1.0, _ptr(mask), Bm, H, W, _ptr(out), Bm, 0, h, w, _stream()),
+               "mdx_inpaint_concat_f32")
+    return out
+
+
+def feather_weights(sigma):
+    """(radius, taps): radius = ceil(3 sigma), the 2 radius + 1 normalised Gaussian taps computed in float64, as fp32."""
+    sigma = float(sigma)
+    if not 0.0 < sigma < float("inf"):
+        raise ValueError(f"mask_blur (the Gaussian's sigma, in pixels) must be positive and finite, got {sigma!r}")
+    radius = int(math.ceil(3.0 * sigma))
+    if radius > FEATHER_MAX_RADIUS:
+        raise ValueError(f"mask_blur {sigma!r} needs a radius of {radius} pixels; the feather kernel takes at most "
+                         f"{FEATHER_MAX_RADIUS} (sigma <= {FEATHER_MAX_RADIUS // 3})")
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    wts = np.exp(-0.5 * (k / sigma) ** 2)
+    return radius, (wts / wts.sum()).astype(np.float32)
+
+
+def mask_feather(mask, sigma, out=None):
+    """alpha = max(m, G * m) [Bm, 1, H, W]: the binarised mask, widened outward by a separable Gaussian of `sigma` pixels with
+    replicate edges (exactly 1 on the hole).  One launch."""
+    _chk(mask, f32, "mask"); _chk(out, f32, "out")
+    if mask.dim() != 4 or mask.shape[1] != 1:
+        raise _lib.MdxError(f"mask: expected [B, 1, H, W], got shape {tuple(mask.shape)}")
+    radius, wts = feather_weights(sigma)
+    Bm, _, H, W = mask.shape
+    if out is None:
+        out = torch.empty_like(mask)
+    _same_shape(mask, "out", out)
+    key = (float(sigma), mask.device)
+    if key not in _FEATHER_TAPS:        # the taps of a sigma are uploaded once per device
+        _FEATHER_TAPS[key] = torch.from_numpy(wts).to(mask.device)
+    wts = _FEATHER_TAPS[key]
+    _lib.check(_lib.load().mdx_mask_feather_f32(_ptr(mask), _ptr(wts), radius, _ptr(out), Bm, H, W, _stream()),
+               "mdx_mask_feather_f32")
+    return out
+
+
+def inpaint_composite(decoded, image=None, alpha=None, output="float", out_f32=None, out_u8=None):
+    """The output stage after the decoder, one launch: clamp((alpha * decoded + (1 - alpha) * image + 1) / 2, 0, 1) as
+    [B, C, H, W] fp32 (output "float"), as its truncation to [B, H, W, C] uint8 (output "uint8", inpaint.py:112-115), or as
+    the pair (output "both").  alpha [1 | B, 1, H, W], None: 1 everywhere (image is then not needed).  out_f32 / out_u8: write
+    into these instead of fresh tensors."""
+    if output not in ("float", "uint8", "both"):
+        raise ValueError(f"output must be 'float', 'uint8' or 'both', got {output!r}")
+    _chk(decoded, f32, "decoded"); _chk(image, f32, "image")
+    if decoded.dim() != 4:
+        raise _lib.MdxError(f"decoded: expected [B, C, H, W], got shape {tuple(decoded.shape)}")
+    B, C, H, W = decoded.shape
+    alpha_b = 0
+    if alpha is not None:
+        if image is None:
+            raise _lib.MdxError("inpaint_composite: alpha needs the image to composite with")
+        _same_shape(decoded, "image", image)
+        alpha_b = _plane_mask("alpha", alpha, B, H, W)
+    _chk(out_f32, f32, "out_f32"); _chk(out_u8, torch.uint8, "out_u8")
+    _same_shape(decoded, "out_f32", out_f32)
+    if out_u8 is not None and tuple(out_u8.shape) != (B, H, W, C):
+        raise _lib.MdxError(f"out_u8: shape {tuple(out_u8.shape)}, expected {(B, H, W, C)}")
+    out_f = None if output == "uint8" else (torch.empty_like(decoded) if out_f32 is None else out_f32)
+    out_u = None if output == "float" else (torch.empty((B, H, W, C), dtype=torch.uint8, device=decoded.device)
+                                            if out_u8 is None else out_u8)
+    _lib.check(_lib.load().mdx_inpaint_composite_f32(_ptr(decoded), _ptr(image), _ptr(alpha), alpha_b, _ptr(out_f), _ptr(out_u),
+                                                     B, C, H, W, _stream()), "mdx_inpaint_composite_f32")
+    return (out_f, out_u) if output == "both" else (out_f if out_u is None else out_u)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -236,3 +236,176 @@ class DiffusionPipeline:
             x = self.model.decode_first_stage(samples)
             samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
         return samples
+
+    # ---- inpainting: wukong-huahua/inpaint.py, image and mask in, composited image out
+    @staticmethod
+    def _check_inpaint_inputs(image, mask, batch=None):
+        """image [B | 1, 3, H, W], mask [B | 1, 1, H, W] of one size; returns the batch they imply (`batch` when given)."""
+        if not (isinstance(image, torch.Tensor) and image.dim() == 4):
+            raise MdxError("inpaint: image must be a tensor [B, 3, H, W] in [-1, 1]")
+        if not (isinstance(mask, torch.Tensor) and mask.dim() == 4 and mask.shape[1] == 1):
+            raise MdxError("inpaint: mask must be a tensor [B, 1, H, W] (>= 0.5 = repaint)")
+        if tuple(mask.shape[2:]) != tuple(image.shape[2:]):
+            raise MdxError(f"inpaint: mask is {tuple(mask.shape[2:])}, image {tuple(image.shape[2:])}")
+        bi, bm = int(image.shape[0]), int(mask.shape[0])
+        B = max(bi, bm) if batch is None else int(batch)
+        if bi not in (1, B) or bm not in (1, B):
+            raise MdxError(f"inpaint: {bi} images and {bm} masks for a batch of {B} (each must be 1 or the batch)")
+        return B
+
+    def _inpaint_to_device(self, image, mask, B):
+        """fp32 on the device; a batch-1 image is repeated (make_batch_sd, inpaint.py:57-62), a batch-1 mask stays one plane
+        (the kernels share it).  The mask is binarised where it arrives, as make_batch_sd does on the host (inpaint.py:51-52)."""
+        image = image.to(device=self.device, dtype=torch.float32)
+        if image.shape[0] != B:
+            image = image.expand(B, -1, -1, -1)
+        mask = (mask >= 0.5).to(torch.float32).to(self.device)
+        return image.contiguous(), mask.contiguous()
+
+    def _inpaint_vae(self):
+        vae = getattr(self.model, "first_stage_model", None)
+        if vae is None or not hasattr(vae, "encode_concat"):
+            raise MdxError("inpaint needs a VAE with an encoder attached (model.first_stage_model)")
+        return vae
+
+    def inpaint_conditioning(self, image, mask, post_noise=None, sample_posterior=True, seed=42, seeds=None, batch_size=None):
+        """c_concat [B, 5, h, w] of the hybrid (9-channel) UNet as inpaint.py:76-85 builds it: cat(mask at the latent grid,
+        scale_factor * encode(image * (mask < 0.5))).  Three steps on the device: the masked-image launch, the VAE encoder, the
+        concat launch.  image [B | 1, 3, H, W] in [-1, 1]; mask [B | 1, 1, H, W], >= 0.5 = repaint.  The posterior draw:
+        post_noise [B, 4, h, w], else per sample from `seeds` (ops.RNG_POSTERIOR), else RandomState(seed + 1) as img2img;
+        sample_posterior False: the mode.  batch_size: the batch to repeat batch-1 inputs to (default: what the inputs imply)."""
+        vae = self._inpaint_vae()
+        if batch_size is None and seeds is not None:
+            batch_size = len(seeds)
+        B = self._check_inpaint_inputs(image, mask, batch_size)
+        seeds = self.check_seeds(seeds, B)
+        image, mask = self._inpaint_to_device(image, mask, B)
+        shape = vae.latent_shape(image.shape)                         # the encoder's output size, not H // 8
+        if not sample_posterior:
+            post_noise = None
+        elif post_noise is None and seeds is not None:
+            post_noise = self.seeded_noise(seeds, ops.RNG_POSTERIOR, shape[1:])
+        elif post_noise is None:
+            post_noise = torch.from_numpy(np.random.RandomState(seed + 1).randn(*shape).astype(np.float32))
+        return self._inpaint_c_concat(vae, image, mask, post_noise, sample_posterior)
+
+    def _inpaint_c_concat(self, vae, image, mask, post_noise, sample_posterior):
+        """image / mask as _inpaint_to_device leaves them: one masked-image launch, the encoder, one concat launch."""
+        masked = ops.inpaint_mask_image(image, mask)
+        return vae.encode_concat(masked, mask, self.model.scale_factor, post_noise=post_noise, sample=sample_posterior)
+
+    def inpaint(self, image, mask, prompts=None, c=None, uc=None, steps=30, scale=7.5, eta=0.0, strength=1.0, seed=42,
+                seeds=None, x_T=None, noise=None, post_noise=None, sample_posterior=True, mask_blur=0.0, composite=True,
+                decode=True, output="float", guidance_rescale=0.0, callback=None, img_callback=None):
+        """Repaint the masked region of an image (wukong-huahua/inpaint.py:65-117; its CLI defaults: PLMS, 30 steps, scale 7.5).
+
+        image [B | 1, 3, H, W] in [-1, 1]; mask [B | 1, 1, H, W], >= 0.5 = repaint; batch-1 inputs are repeated to the
+        conditioning's batch.  Conditioning (prompts, or c / uc), guidance_rescale and seeds as in img2img.  Single rank only.
+        A hybrid model (LatentInpaintDiffusion, 9 input channels) follows the reference: c_concat = inpaint_conditioning(),
+        the same c_concat in the conditional and the unconditional dict, x_T = start_noise(B, shape, seed) (ops.RNG_X_T with
+        seeds), a full `steps`-step run.  strength < 1 starts instead from the encoded unmasked image noised to the level
+        int(strength * steps) selects, as img2img (noise: the forward draw).  A plain 4-channel model takes the blend path:
+        img2img(init_image=image, mask=1 - mask at the latent grid) (PLMS / DDIM only).
+        decode False: the final latent.  Otherwise the VAE decoder and ONE output launch: with composite, the original image
+        is kept outside the mask, alpha * decoded + (1 - alpha) * image with alpha = the binarised mask, or with mask_blur
+        (a Gaussian sigma in pixels, > 0) alpha = max(m, G * m) -- the mask widened outward, exactly 1 on the hole; composite
+        False returns the decoder's picture as the reference does.  output "float": [B, 3, H, W] in [0, 1]; "uint8":
+        [B, H, W, 3], (uint8)(255 v) as inpaint.py:112-115."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if output not in ("float", "uint8"):
+            raise ValueError(f"inpaint: output must be 'float' or 'uint8', got {output!r}")
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"inpaint: strength must be in (0, 1], got {strength!r}")
+        t_enc = int(float(strength) * steps)
+        if t_enc == 0:
+            raise ValueError(f"inpaint: strength {strength!r} leaves no step of {steps} to run")
+        mask_blur = float(mask_blur)
+        if not mask_blur >= 0.0:
+            raise ValueError(f"inpaint: mask_blur must be >= 0, got {mask_blur!r}")
+        if mask_blur > 0.0:
+            ops.feather_weights(mask_blur)                            # (the radius cap, before any work)
+        if D.world()[1] > 1:
+            raise MdxError("inpaint runs on a single rank (the sharded form is not built)")
+        if prompts is not None:
+            uc = self.model.get_learned_conditioning(len(prompts) * [""])
+            c = self.model.get_learned_conditioning(list(prompts))
+        if c is None:
+            raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
+        c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
+        B = int(c.shape[0])
+        seeds = self.check_seeds(seeds, B)
+        try:
+            self._check_inpaint_inputs(image, mask, B)
+        except MdxError as e:
+            raise MdxError(f"{e} -- the batch is the conditioning's, {B}") from None
+        hybrid = getattr(getattr(self.model, "model", None), "conditioning_key", "crossattn") == "hybrid"
+        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        dpm = isinstance(self.sampler, DPMSolverSampler)
+        if not hybrid and dpm:
+            raise NotImplementedError("inpaint with a 4-channel model blends under the mask every step: implemented by "
+                                      "PLMSSampler / DDIMSampler")
+        vae = self._inpaint_vae()
+        image, mask = self._inpaint_to_device(image, mask, B)
+        if hybrid:
+            samples = self._inpaint_hybrid(vae, dpm, image, mask, c, uc, B, steps, scale, eta, float(strength), t_enc, seed, seeds,
+                                           x_T, noise, post_noise, sample_posterior, guidance_rescale, callback, img_callback)
+        else:
+            # the blend path: img2img's mask means KEEP
+            keep = 1.0 - ops.inpaint_resize_mask(mask, vae.latent_shape(image.shape)[2:])
+            samples = self.img2img(init_image=image, strength=strength, c=c, uc=uc, steps=steps, scale=scale, eta=eta, seed=seed,
+                                   noise=noise, post_noise=post_noise, sample_posterior=sample_posterior, mask=keep,
+                                   callback=callback, img_callback=img_callback, guidance_rescale=guidance_rescale, seeds=seeds)
+        if not decode:
+            return samples
+        x = self.model.decode_first_stage(samples).to(torch.float32).contiguous()
+        alpha = None
+        if composite:
+            alpha = ops.mask_feather(mask, mask_blur) if mask_blur > 0.0 else mask
+        return ops.inpaint_composite(x, image if composite else None, alpha, output=output)
+
+    def _inpaint_hybrid(self, vae, dpm, image, mask, c, uc, B, steps, scale, eta, strength, t_enc, seed, seeds, x_T, noise,
+                        post_noise, sample_posterior, guidance_rescale, callback, img_callback):
+        """inpaint()'s sampling on a hybrid model: the final latent."""
+        c = c.to(self.device, torch.float16)
+        uc = None if uc is None else uc.to(self.device, torch.float16)
+        if uc is not None and uc.shape[0] == 1 and B > 1:
+            uc = uc.expand(B, -1, -1).contiguous()
+        self.fit_context(c)
+        lat = vae.latent_shape(image.shape)
+        shape = list(lat[1:])
+
+        def draw(given, sd, stream):
+            if given is not None:
+                return given
+            if seeds is not None:
+                return self.seeded_noise(seeds, stream, shape)
+            return torch.from_numpy(np.random.RandomState(sd).randn(*lat).astype(np.float32))
+        post = draw(post_noise, seed + 1, ops.RNG_POSTERIOR) if sample_posterior else None
+        c_cat = self._inpaint_c_concat(vae, image, mask, post, sample_posterior)
+        cond = {"c_concat": c_cat, "c_crossattn": c}                  # inpaint.py:88
+        uc_full = None if uc is None else {"c_concat": c_cat, "c_crossattn": uc}      # inpaint.py:91-92
+        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
+        seeds_kw = {} if seeds is None else {"seeds": seeds}
+        common = dict(unconditional_guidance_scale=scale, unconditional_conditioning=uc_full, callback=callback,
+                      img_callback=img_callback, **rescale_kw, **seeds_kw)
+        if strength >= 1.0:
+            # the reference's run: pure noise, every step; neither mask nor x0 goes to the sampler (inpaint.py's x0= without a
+            # mask is inert)
+            if x_T is None:
+                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
+            return self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=shape, verbose=False, eta=eta,
+                                       x_T=x_T.to(self.device), **common)[0]
+        # strength < 1: start from the (unmasked) image's own latent, noised to where the last t_enc steps begin -- img2img
+        if dpm:
+            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
+            start = t_0 + (1.0 - t_0) * t_enc / steps
+            a, b = self.sampler.q_coefficients(start)
+        else:
+            self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
+            a, b = self.sampler.q_coefficients(t_enc)
+        _, x_enc = vae.encode_noised(image, self.model.scale_factor, a, b, draw(noise, seed, ops.RNG_ENCODE), post_noise=post,
+                                     sample=sample_posterior)
+        if dpm:
+            return self.sampler.sample(S=t_enc, conditioning=cond, batch_size=B, shape=shape, verbose=False, x_T=x_enc,
+                                       t_start=start, **common)[0]
+        return self.sampler.decode(x_enc, cond, t_enc, **common)[0]
