@@ -384,6 +384,7 @@ class UNetModel:
         w["out.cb"] = L.vec(conv + ".bias", pad=self.cout_pad)
         self._frag_w = {}
         self._geglu80 = {}
+        self._ff_proj = {}
         self._plans = {}
         self._ctx_key = None
         self._ctx_ref = None
@@ -411,8 +412,8 @@ class UNetModel:
     # ------------------------------------------------------------------ LoRA
     def _find_lora_sites(self):
         """Every place a LoRA target matrix lives in self.w, as keyword arguments of ops.lora_merge.  The plan-time copies
-        self._frag_w (3x3 conv weights in fragment-major form) and self._geglu80 (ff.net.0.proj re-packed at unit 80) hold no
-        LoRA target -- conv and feed-forward weights are not adapted (WK attention.py:118-126) -- so they are left alone."""
+        self._frag_w (3x3 conv weights in fragment-major form), self._geglu80 (ff.net.0.proj re-packed at unit 80) and self._ff_proj
+        (proj_out composed with ff.net.2) hold no LoRA target -- conv and feed-forward weights are not adapted (WK attention.py:118-126) -- so they are left alone."""
         w = self.w
         T, F = ops.LORA_TILED, ops.LORA_FRAG
         sites = {}
@@ -985,6 +986,21 @@ class _UNetPlanner(PlanBuilder):
         else:
             d.bias = g80[t + "ff1.b"].data_ptr()
 
+    def ff_proj_weights(self, pre, t, ch, inner, n):
+        """[Wc | W_p] packed as one [ch, 5 inner] dense weight and bc = b_p + W_p b_f2 (ops.compose_ff_proj) for the last block `t`
+        of the SpatialTransformer `pre`, or None below the gate (ops option unet_ff_proj_fuse = smallest inner, 0 = never; M >= 128).
+        Made once per weight on first need and kept for every later plan; the originals stay for the plans below the gate."""
+        w, fp = self.w, self.net._ff_proj
+        thr = ops.get_option("unet_ff_proj_fuse")
+        if not thr or inner < thr or inner % 64 or self.B * n < 128:
+            return None
+        if t not in fp:
+            w_p = ops.unpack_gemm_weight(w[pre + "proj_out.w"], ch, inner)
+            w_f2 = ops.unpack_gemm_weight(w[t + "ff2.w"], inner, 4 * inner)
+            comp, bc = ops.compose_ff_proj(w_p, w[pre + "proj_out.b"], w_f2, w[t + "ff2.b"])
+            fp[t] = (ops.pack_gemm_weight(comp), bc)
+        return fp[t]
+
     def tail_rows(self, t, n, heads, dh):
         """Rows per block of the fused SpatialTransformer tail for this block, or 0 = unfused launches.  The fused launch
         needs enough row blocks to fill the chip: 32-row blocks from 192 blocks up (UNet batch 2 at a 64 x 64 latent = 256),
@@ -1207,6 +1223,14 @@ class _UNetPlanner(PlanBuilder):
             else:
                 g = dense(tok3, B, n, inner, 8 * inner, w[t + "ff1.w"], epilogue=ops.EPI_GEGLU, **consumer(t + "ff1"))
             self.geglu_tile160(self.descs[-1], t, inner)
+            fpw = self.ff_proj_weights(pre, t, ch, inner, n) if last else None
+            if fpw is not None:
+                # ff2 + proj_out of the last block as ONE launch over [g | tok3] (ops.compose_ff_proj): the producer of `out`,
+                # as proj_out is, so the next GroupNorm still gets its column statistics from this epilogue
+                out = dense(g, B, n, 5 * inner, ch, fpw[0], bias=fpw[1], src2=tok3, c2=inner, residual=x)
+                self.meta[-1]["info"] += " (ff2 + proj_out fused)"
+                self.release(g, tok3, ln)
+                return out
             # the next block's norm1 reads its row statistics from this block's last producer
             tok = dense(g, B, n, 4 * inner, inner, w[t + "ff2.w"], bias=w[t + "ff2.b"], residual=tok3,
                         stats_out=st if (fold1 and not last) else None)
@@ -1272,7 +1296,10 @@ class _UNetPlanner(PlanBuilder):
             if (c["x2"] is None and not c["film"] and L <= 64 and HW * L * 16 <= (64 << 10) and isinstance(d, ops.GemmDesc)
                     and d.N == C1
                     and d.out_ld == C1 and self.op_index.get(ctypes.addressof(d)) == c["meta"] - 1
-                    and ops.gemm_query(d)[2] > 1 and ops.groupnorm_from_splitk_ok(d)):
+                    and ops.gemm_query(d)[2] > 1 and ops.groupnorm_from_splitk_ok(d)
+                    # (a two-source launch that reduces its split in the kernel keeps doing so: deferring the reduce would move it
+                    # from the lean dense kernel to slabs on the generic one, which is what the ff2 + proj_out fusion must not pay)
+                    and not (d.c2 and ops.gemm_query(d)[6])):
                 d.defer_reduce = 1
                 c["fs"] = d
                 self.meta[c["meta"] - 1]["launches"] = 1

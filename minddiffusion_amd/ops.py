@@ -62,6 +62,14 @@ _OPTIONS = {"unet_st_tail": int(os.environ.get("MDX_UNET_ST_TAIL", "-1")),
             # they differ: a host synchronisation per call, for bringing up a new sampler -- the shipped samplers build both halves
             # from one tensor
             "unet_cfg_dup_check": int(os.environ.get("MDX_UNET_CFG_DUP_CHECK", "0")),
+            # The last ff2 of an unfused SpatialTransformer and its proj_out have no non-linearity between them: from this `inner`
+            # on (0 = never; the launch must also have M >= 128) they run as ONE dense launch over the K-concatenated operand
+            # [g | tok3] with the composite weight [W_p W_f2 | W_p] (compose_ff_proj; same FLOPs, same weight bytes, one launch and
+            # one [M, C] round trip fewer; needs the K-segmented lean dense kernel).  The default keeps the tiny / small test
+            # models (inner <= 320) on the launches their bit-exact fixtures were recorded with.  Measured at UNet batch 2 (profiles/ff_proj_fuse_*): per block
+            # 30.3 -> 23.3 us (M = 2048), 31.8 -> 23.9 us (M = 512), 23.0 -> 14.4 us (M = 128); 227 -> 216 ops; bench.py six alternating
+            # pairs 5.390-5.405 -> 5.490-5.501 latents/s (+1.9 %, ranges disjoint)
+            "unet_ff_proj_fuse": int(os.environ.get("MDX_UNET_FF_PROJ_FUSE", "640")),
             # Taichu-GLIDE AttentionBlock (unet.py:267-297): 1 = q | k | v of the image tokens in ONE launch (q | k row-major into a
             # [B, text + image, 2 C] buffer, V transposed: mdx_gemm_desc.n_split with out_bs) instead of three -- 44 launches fewer
             # per base evaluation.  0 = three launches (A/B)
@@ -426,6 +434,17 @@ def geglu_deinterleave(t, unit=64):
 def geglu_repack(t, unit_from, unit_to):
     """A GEGLU-interleaved tensor (rows of the weight, bias, S[n]) from one packing unit to another: a row permutation, done once."""
     return geglu_interleave(*geglu_deinterleave(t, unit_from), unit_to)
+
+
+def compose_ff_proj(w_p, b_p, w_f2, b_f2):
+    """proj_out folded into the feed-forward's second Dense (option unet_ff_proj_fuse): with g the GEGLU hidden and tok3 the
+    residual stream,  x + b_p + W_p (tok3 + b_f2 + W_f2 g) = x + bc + [g | tok3] [Wc | W_p]^T.  w_p [ch, inner] and w_f2
+    [inner, 4 inner] are the stored fp16 matrices, b_p / b_f2 their fp32 biases.  Returns ([ch, 5 inner] fp16 = [Wc | W_p] with
+    Wc = fp16(W_p W_f2), the product taken in fp64; bc = b_p + W_p b_f2 in fp32)."""
+    wp64 = w_p.to(torch.float64)
+    wc = (wp64 @ w_f2.to(torch.float64)).to(f16)
+    bc = (b_p.to(torch.float64) + wp64 @ b_f2.to(torch.float64)).to(f32)
+    return torch.cat([wc, w_p.to(f16)], 1).contiguous(), bc.contiguous()
 
 
 def make_gemm_desc(a, w, N, B, H, W, c1, out, out_ld, a2=None, c2=0, bias=None, rowbias=None, rowbias_ld=0,

@@ -23,7 +23,7 @@ def family(name):
         return None   # torch's weight-initialisation / copy kernels
     if "nchw_to_nhwc_kernel" in name:
         return "eval_marker"      # exactly one launch per UNet evaluation (LatentDiffusion.apply_model's layout boundary)
-    if ("gemm_kernel" in name or "dense_kernel" in name or "conv3x3_halo_kernel" in name or "st_tail_kernel" in name
+    if ("gemm_kernel" in name or "dense_kernel" in name or "dense_seg_kernel" in name or "conv3x3_halo_kernel" in name or "st_tail_kernel" in name
             or "st_head_kernel" in name or "conv8p_kernel" in name):
         return "gemm"      # (the fused SpatialTransformer head / tail launches are chains of dense GEMMs)
     if "splitk_reduce" in name:

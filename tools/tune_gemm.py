@@ -61,6 +61,7 @@ def main():
     ap.add_argument("--log", default=None)
     ap.add_argument("--only-m", type=int, default=0, help="tune only the shapes with this M")
     ap.add_argument("--only-ks", type=int, default=0, help="tune only the shapes with this kernel size")
+    ap.add_argument("--only-k", type=int, default=0, help="tune only the shapes with this K (ksize * ksize * Cin)")
     ap.add_argument("--tile160-only", action="store_true",
                     help="dense shapes only, and only the 128 x 160 tile (ring 2 | 3) against the present choice: the A/B of that form")
     ap.add_argument("--insitu", type=int, default=2,
@@ -141,7 +142,7 @@ def main():
         return True
     lines, log = [], []
     for (M, N, K, ks, var), d0 in sorted(shapes.items()):
-        if (args.only_m and M != args.only_m) or (args.only_ks and ks != args.only_ks):
+        if (args.only_m and M != args.only_m) or (args.only_ks and ks != args.only_ks) or (args.only_k and K != args.only_k):
             continue
         if d0.xattn_k:      # a query projection that carries its cross-attention: the planner fixes its tiles (one head per 64-column tile)
             continue
