@@ -21,14 +21,13 @@ Differences from the reference, both on the fp32 side of its fp16 arithmetic: th
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
 """
-import os
-
 import numpy as np
 import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..plms import _first_tensor, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent
+from ..guided import GuidedModel, split_conditioning, start_latent
+from ..plms import check_guidance_rescale, check_seed_sources, check_seeds, noised_latent
 from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
 
 
@@ -61,15 +60,6 @@ class DPMSolverSampler:
         a, b = self.q_coefficients(t_start)
         return noised_latent(x0, a, b, noise, self.generator, seeds)
 
-    def _eps_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
-        if hasattr(self.model, "apply_model_nhwc"):
-            kw = {} if temb is None else {"temb": temb}
-            if cfg_dup:     # both halves of the batch are the same x and t: only the contexts differ
-                kw["cfg_dup"] = True
-            return self.model.apply_model_nhwc(x, t, cond, **kw)
-        e = self.model.apply_model(x, t, cond).to(torch.float32).contiguous()
-        return ops.nchw_to_nhwc(e, (e.shape[1] + 7) // 8 * 8)
-
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
@@ -85,92 +75,34 @@ class DPMSolverSampler:
             t_start = self._check_t_start(t_start)
         if conditioning is None:
             raise MdxError("DPMSolverSampler: conditioning is required (classifier-free guidance on a text-conditional UNet)")
-        # hybrid (inpainting) conditioning, the dict forms PLMSSampler takes: {"c_concat": mask + masked-image latent,
-        # "c_crossattn": text}; the unconditional dict may carry a c_concat of its own (WK plms.py:191-201 concatenates every key)
-        c_cat = uc_cat = None
-        if isinstance(conditioning, dict) and "c_concat" in conditioning:
-            c_cat = _first_tensor(conditioning["c_concat"])
-            conditioning = conditioning["c_crossattn"]
-            if isinstance(unconditional_conditioning, dict):
-                if unconditional_conditioning.get("c_concat") is not None:
-                    uc_cat = _first_tensor(unconditional_conditioning["c_concat"])
-                unconditional_conditioning = unconditional_conditioning["c_crossattn"]
-        cond = _first_tensor(conditioning)
-        if cond.shape[0] != batch_size:
-            print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
         if mask is not None or x0 is not None:
             raise NotImplementedError("mask/x0 blending is implemented by PLMSSampler / DDIMSampler (WK inpaint.py uses PLMS); "
                                       "the reference never passes it to DPMSolverSampler")
-        if not (isinstance(cond, torch.Tensor) and cond.is_cuda):
-            raise MdxError("conditioning must be a CUDA(HIP) tensor [B, T, context_dim]")
-        dev = cond.device
-        C, H, W = shape
-        size = (batch_size, C, H, W)
-        seeds = check_seeds(seeds, batch_size, dev)
-        if x_T is None and seeds is not None:
-            img = ops.randn_seeded(seeds, ops.RNG_X_T, 0, (C, H, W))
-        elif x_T is None:
-            img = torch.randn(size, device=dev, dtype=torch.float32, generator=self.generator)
-        else:
-            img = torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()
-        uc = _first_tensor(unconditional_conditioning) if unconditional_conditioning is not None else None
+        # bare or hybrid (inpainting) conditioning, the forms PLMSSampler takes
+        cond, uc, c_cat, uc_cat, dev = split_conditioning(self.model, conditioning, unconditional_conditioning, x_T)
+        if cond is not None and cond.shape[0] != batch_size:
+            print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
+        size = (batch_size,) + tuple(shape)
+        img = start_latent(x_T, check_seeds(seeds, batch_size, dev), size, dev, self.generator)
         scale = float(unconditional_guidance_scale)
-        use_cfg = not (uc is None or scale == 1.)                   # model_wrapper :316-317
-        b = batch_size
-        nb = 2 * b if use_cfg else b
-        if use_cfg:
-            c_in = torch.cat([uc.to(cond.dtype), cond], 0).contiguous()   # [uncond; cond] (:320-322), built once
-            x_in = torch.empty((2 * b, C, H, W), device=dev, dtype=torch.float32)
-        else:
-            c_in, x_in = cond.contiguous(), None
-        if c_cat is not None:       # DiffusionWrapper 'hybrid': cat(x, c_concat) -- written once, the C latent channels per step
-            cc = c_cat.to(device=dev, dtype=torch.float32)
-            x_in = torch.empty((nb, C + int(cc.shape[1]), H, W), device=dev, dtype=torch.float32)
-            x_in[nb - b:, C:] = cc                                        # batch = [uncond ; cond]
-            if use_cfg:
-                x_in[:b, C:] = cc if uc_cat is None else uc_cat.to(device=dev, dtype=torch.float32)
-        # the two halves of a guidance batch are the same UNet input unless the unconditional branch has its own c_concat
-        same_halves = c_cat is None or uc_cat is None
 
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
         plan = multistep_2m_plan(ns, S, order=2 if S >= 2 else 1, lower_order_final=True, t_start=t_start)
-        t_all = torch.tensor([p["t_input"] for p in plan], dtype=torch.float32, device=dev)
-        # timestep-only part of the UNet for all S (fractional) timesteps in one batched pass (see PLMSSampler)
-        temb_all = None
-        if hasattr(self.model, "time_embedding_table") and os.environ.get("MDX_SAMPLER_TEMB_TABLE", "1") != "0":
-            temb_all = self.model.time_embedding_table(t_all)
-        t_all = t_all[:, None].expand(S, nb).contiguous()
+        # (S fractional timesteps; model_wrapper :316-322 builds the [uncond; cond] batch)
+        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
+                             [p["t_input"] for p in plan])
         x0_bufs = [torch.empty_like(img), torch.empty_like(img)]    # data predictions at the last two grid points
         x_next = torch.empty_like(img)
-        v_pred = getattr(self.model, "parameterization", "eps") == "v"
+        # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, in the step launch
+        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
+        f = np.float32
         for k, p in enumerate(plan):
-            if use_cfg:
-                if c_cat is None:
-                    x_in[:b].copy_(img)
-                    x_in[b:].copy_(img)
-                else:
-                    x_in[:b, :C].copy_(img)
-                    x_in[b:, :C].copy_(img)
-                eps = self._eps_nhwc(x_in, t_all[k], c_in, None if temb_all is None else temb_all[k], cfg_dup=same_halves)
-                eps_u, eps_c = eps[:b], eps[b:]
-            elif c_cat is not None:
-                x_in[:, :C].copy_(img)
-                eps_u, eps_c = None, self._eps_nhwc(x_in, t_all[k], c_in, None if temb_all is None else temb_all[k])
-            else:
-                eps_u, eps_c = None, self._eps_nhwc(img, t_all[k], c_in, None if temb_all is None else temb_all[k])
+            eps_u, eps_c = guided(img, k)
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
-            f = np.float32
             update = (f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]),
                       f(p["c1"]), prev if p["c1"] != 0.0 else None, None, x_next, cur)
-            if use_cfg and guidance_rescale != 0.:
-                ops.sampler_step_rescale(img, None, eps_u, eps_c, eps_c.shape[-1], scale,
-                                         ops.PRED_V if v_pred else ops.PRED_EPS, f(p["alpha"]) if v_pred else 1.,
-                                         f(p["sigma"]) if v_pred else 0., [], (1., 0., 0., 0.), *update, guidance_rescale)
-            elif v_pred:    # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, same launch
-                ops.sampler_step_pred(img, None, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V, f(p["alpha"]),
-                                      f(p["sigma"]), [], (1., 0., 0., 0.), *update)
-            else:
-                ops.sampler_step(img, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.), *update)
+            ops.sampler_update(img, eps_u, eps_c, scale, pred_type, [], (1., 0., 0., 0.), update, guidance_rescale, None,
+                               f(p["alpha"]), f(p["sigma"]))
             img, x_next = x_next, img
             if callback:
                 callback(k)

@@ -1,0 +1,137 @@
+"""What PLMSSampler, DDIMSampler and DPMSolverSampler do before and inside their loops in the same way: the conditioning a
+caller may hand over (split_conditioning), the start latent (start_latent), and the model call of one step on the
+classifier-free-guidance batch (GuidedModel)."""
+import os
+
+import numpy as np
+import torch
+
+from .... import ops
+from ...._lib import MdxError
+
+
+def _first_tensor(c):
+    while isinstance(c, (dict, list, tuple)):
+        c = c[list(c.keys())[0]] if isinstance(c, dict) else c[0]
+    return c
+
+
+def split_conditioning(model, cond, uc, x_T=None):
+    """(cond, uc, c_cat, uc_cat, device) from what sample() was given, bare or as a dict, by the DiffusionWrapper key of the
+    model (WK ddpm.py:361-374), handed over the way plms.py:188-195 does it: a bare conditioning goes to the keyword the key
+    reads -- 'crossattn': the text context; 'concat': extra input channels (cond and uncond halves may differ); 'adm': class
+    labels [B] (concatenated [uncond; cond] like a text context); None: no conditioning at all.
+    Hybrid (inpainting) conditioning is {"c_concat": mask + masked-image latent, "c_crossattn": text} (inpaint.py:84-88, WK
+    plms.py:188-205).  WK plms.py:191-201 concatenates [uncond[k]; cond[k]] for EVERY dict key: an unconditional c_concat that
+    differs from the conditional one goes into the unconditional half (inpaint.py passes the same tensor in both)."""
+    key = getattr(getattr(model, "model", None), "conditioning_key", "crossattn")
+    c_cat = uc_cat = None
+    if key == "concat":
+        c_cat = _first_tensor(cond["c_concat"] if isinstance(cond, dict) else cond)
+        if uc is not None:
+            uc_cat = _first_tensor(uc["c_concat"] if isinstance(uc, dict) else uc)
+        cond = uc = None
+    elif isinstance(cond, dict) and "c_concat" in cond:
+        c_cat = _first_tensor(cond["c_concat"])
+        cond = cond["c_crossattn"]
+        if isinstance(uc, dict):
+            if uc.get("c_concat") is not None:
+                uc_cat = _first_tensor(uc["c_concat"])
+            uc = uc["c_crossattn"]
+    if key is None:
+        cond = uc = None
+    cond = _first_tensor(cond) if cond is not None else None
+    uc = _first_tensor(uc) if uc is not None else None
+    if key in ("crossattn", "hybrid") and not (isinstance(cond, torch.Tensor) and cond.is_cuda):
+        raise MdxError("conditioning must be a CUDA(HIP) tensor [B, T, context_dim]")
+    if key == "adm" and cond is None:
+        raise MdxError("'adm' conditioning needs the class labels [B] as `conditioning`")
+    if key == "concat" and c_cat is None:
+        raise MdxError("'concat' conditioning needs the extra input channels [B, C', H, W] as `conditioning`")
+    if isinstance(cond, torch.Tensor) and cond.is_cuda:
+        dev = cond.device
+    elif isinstance(c_cat, torch.Tensor) and c_cat.is_cuda:
+        dev = c_cat.device
+    elif isinstance(x_T, torch.Tensor) and x_T.is_cuda:
+        dev = x_T.device
+    else:
+        dev = model.unet.device
+    if cond is not None:
+        cond = torch.as_tensor(cond).to(dev)
+        uc = None if uc is None else torch.as_tensor(uc).to(dev)
+    return cond, uc, c_cat, uc_cat, dev
+
+
+def start_latent(x_T, seeds, size, dev, generator):
+    """The latent a run starts from, [B, C, H, W] fp32: a copy of x_T, else one ops.randn_seeded launch from the per-sample
+    `seeds` (stream ops.RNG_X_T, draw 0), else the sampler's generator."""
+    if x_T is None and seeds is not None:
+        return ops.randn_seeded(seeds, ops.RNG_X_T, 0, tuple(size[1:]))
+    if x_T is None:
+        return torch.randn(size, device=dev, dtype=torch.float32, generator=generator)
+    return torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()
+
+
+class GuidedModel:
+    """The model call of step i on the guidance batch [uncond; cond] (plms.py:192-195): ``guided(x, i) -> (out_u, out_c)``,
+    NHWC fp16 halves of one UNet output (out_u None without guidance).  Everything that does not change over the run is made
+    here, once: the [2B, T, D] context (plms.py:194 rebuilds the concat every step), the UNet's input batch with the c_concat
+    channels of a hybrid model written into it (step i copies only the latent channels), the timestep rows, and the
+    timestep-only part of the UNet for all steps.
+
+    scale: the guidance scale; 1, or neither an unconditional context nor an unconditional c_concat, means no guidance batch.
+    t_steps: the model-input timestep of every step, in loop order (the UNet's sinusoid takes float timesteps,
+    util.py:111-131)."""
+
+    def __init__(self, model, b, shape, cond, uc, c_cat, uc_cat, scale, dev, t_steps):
+        self.model, self.b, self.cx = model, b, shape[0]
+        self.use_cfg = not ((uc is None and uc_cat is None) or scale == 1.)
+        nb = self.nb = 2 * b if self.use_cfg else b
+        if cond is None:
+            self.c_in = None
+        else:
+            self.c_in = torch.cat([uc.to(cond.dtype), cond], 0).contiguous() if self.use_cfg else cond.contiguous()
+        self.x_in = None
+        if self.use_cfg or c_cat is not None:
+            ccat = 0 if c_cat is None else int(c_cat.shape[1])
+            self.x_in = torch.empty((nb, self.cx + ccat) + tuple(shape[1:]), device=dev, dtype=torch.float32)
+            if c_cat is not None:                                    # DiffusionWrapper 'hybrid': cat(x, c_concat), written once
+                cc = c_cat.to(device=dev, dtype=torch.float32)
+                self.x_in[nb - b:, self.cx:] = cc                    # batch = [uncond ; cond]
+                if self.use_cfg:
+                    self.x_in[:b, self.cx:] = cc if uc_cat is None else uc_cat.to(device=dev, dtype=torch.float32)
+        # the two halves of a guidance batch are the same UNet input unless the unconditional branch has its own c_concat
+        self.same_halves = self.use_cfg and self.c_in is not None and (c_cat is None or uc_cat is None)
+        # (a fresh array: the flipped view of a ONE-step grid still counts as contiguous and keeps its negative stride)
+        t_all = torch.as_tensor(np.array(t_steps, dtype=np.float32), device=dev)
+        # the timestep-only part of the UNet (time_embed MLP + the ResBlock emb_layers, openaimodel.py:550-551,188) for
+        # ALL steps in one batched pass; step i then hands row i to the UNet instead of recomputing it.
+        # Not for a class-conditional UNet: label_emb(y) joins emb per call.
+        self.temb_all = None
+        if (hasattr(model, "time_embedding_table") and os.environ.get("MDX_SAMPLER_TEMB_TABLE", "1") != "0"
+                and getattr(getattr(model, "unet", None), "num_classes", None) is None):
+            self.temb_all = model.time_embedding_table(t_all)
+        self.t_all = t_all[:, None].expand(t_all.shape[0], nb).contiguous()
+
+    def _eps_nhwc(self, x, i, cfg_dup=False):
+        """Prefer the NHWC fast path of our LatentDiffusion; any object with the reference's apply_model(x, t, cond) -> NCHW
+        eps still works (its output is re-laid-out by a HIP kernel)."""
+        if hasattr(self.model, "apply_model_nhwc"):
+            kw = {} if self.temb_all is None else {"temb": self.temb_all[i]}
+            if cfg_dup:     # both halves of the batch are the same x and t: only the contexts differ
+                kw["cfg_dup"] = True
+            return self.model.apply_model_nhwc(x, self.t_all[i], self.c_in, **kw)
+        e = self.model.apply_model(x, self.t_all[i], self.c_in).to(torch.float32).contiguous()
+        return ops.nchw_to_nhwc(e, (e.shape[1] + 7) // 8 * 8)
+
+    def __call__(self, x, i):
+        b, cx, x_in = self.b, self.cx, self.x_in
+        if self.use_cfg:
+            x_in[:b, :cx].copy_(x)
+            x_in[b:, :cx].copy_(x)
+            out = self._eps_nhwc(x_in, i, cfg_dup=self.same_halves)
+            return out[:b], out[b:]
+        if x_in is not None:
+            x_in[:, :cx].copy_(x)
+            return None, self._eps_nhwc(x_in, i)
+        return None, self._eps_nhwc(x, i)

@@ -20,20 +20,13 @@ Per-sample seeds (not in the reference): with ``seeds=`` every draw -- x_T, the 
 stochastic_encode noise -- is one mdx_randn_f32 launch keyed by the sample's own seed (ops.randn_seeded), so a sample does not
 depend on the batch it is served in; without it the sampler's generator draws for the whole batch, as before.
 """
-import os
-
 import numpy as np
 import torch
 
 from .... import ops
 from ...._lib import MdxError
 from ...modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps
-
-
-def _first_tensor(c):
-    while isinstance(c, (dict, list, tuple)):
-        c = c[list(c.keys())[0]] if isinstance(c, dict) else c[0]
-    return c
+from .guided import GuidedModel, _first_tensor, split_conditioning, start_latent
 
 
 def check_guidance_rescale(value):
@@ -82,6 +75,45 @@ def noised_latent(x0, a, b, noise, generator, seeds=None):
         noise = torch.randn(x0.shape, device=x0.device, dtype=torch.float32, generator=generator)
     noise = torch.as_tensor(noise).to(device=x0.device, dtype=torch.float32).contiguous()
     return ops.q_sample(x0, noise, a, b)
+
+
+class _Draws:
+    """The N(0, 1) draws inside the loop: per sample from `seeds` (one ops.randn_seeded launch each), else the injected
+    tensors (tests feed the oracle the same ones), else the sampler's generator."""
+
+    def __init__(self, seeds, generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout):
+        self.seeds, self.generator, self.dev, self.shape = seeds, generator, dev, tuple(shape)
+        self.step_noises, self.dropout_masks, self.blend_noises = step_noises, dropout_masks, blend_noises
+        self.temperature, self.noise_dropout = temperature, noise_dropout
+        self.steps_drawn = 0
+
+    def step(self):
+        """temperature * N(0, 1) of the next eta > 0 step, after plms.py:224-225 `ops.dropout(noise, p=noise_dropout)`: zero
+        with probability p, the rest scaled by 1 / (1 - p) -- with seeds inside the one launch; dropout_masks[k] (1 = keep)
+        injects the mask of the k-th draw."""
+        k, p = self.steps_drawn, self.noise_dropout
+        self.steps_drawn += 1
+        if self.seeds is not None:
+            return ops.randn_seeded(self.seeds, ops.RNG_STEP, k, self.shape[1:], scale=self.temperature, dropout=p)
+        if self.step_noises is not None:
+            noise = torch.as_tensor(self.step_noises[k]).to(device=self.dev, dtype=torch.float32) * self.temperature
+        else:
+            noise = torch.randn(self.shape, device=self.dev, dtype=torch.float32, generator=self.generator) * self.temperature
+        if p > 0.:
+            if self.dropout_masks is not None:
+                keep = torch.as_tensor(self.dropout_masks[k]).to(device=self.dev, dtype=torch.float32)
+            else:
+                keep = (torch.rand(self.shape, device=self.dev, generator=self.generator) >= p).to(torch.float32)
+            noise = noise * keep / (1. - float(p))
+        return noise
+
+    def blend(self, i, x0):
+        """The q_sample noise of the mask blend at loop index i (plms.py:153-157; WK: q_sample gets explicit noise)."""
+        if self.seeds is not None:
+            return ops.randn_seeded(self.seeds, ops.RNG_BLEND, i, self.shape[1:])
+        if self.blend_noises is not None:
+            return torch.as_tensor(self.blend_noises[i]).to(device=self.dev, dtype=torch.float32)
+        return torch.randn(x0.shape, device=self.dev, dtype=torch.float32, generator=self.generator)
 
 
 class _SamplerBase:
@@ -210,94 +242,10 @@ class _SamplerBase:
                                   guidance_rescale=guidance_rescale, t_start=self._check_t_start(t_start, grid), seeds=seeds,
                                   **test_injection_kwargs)
 
-    # ---- model call: prefer the NHWC fast path of our LatentDiffusion; any object with the reference's
-    #      apply_model(x, t, cond) -> NCHW eps still works (its output is re-laid-out by a HIP kernel).
-    def _eps_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
-        if hasattr(self.model, "apply_model_nhwc"):
-            kw = {} if temb is None else {"temb": temb}
-            if cfg_dup:     # both halves of the batch are the same x and t: only the contexts differ
-                kw["cfg_dup"] = True
-            return self.model.apply_model_nhwc(x, t, cond, **kw), None
-        e = self.model.apply_model(x, t, cond)
-        e = e.to(torch.float32).contiguous()
-        buf = ops.nchw_to_nhwc(e, (e.shape[1] + 7) // 8 * 8)
-        return buf, buf
-
-    # ---- plms.py:124-179 + 182-247
-    def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
-                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
-                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None):
-        """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
-        t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
-        mask / x0 blend of every step is one ops.q_sample launch, in place."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
-        check_seed_sources(seeds, self.generator, step_noises=step_noises, blend_noises=blend_noises, dropout_masks=dropout_masks)
-        if mask is not None and x0 is None:
-            raise ValueError("mask blending needs x0 (plms.py:154)")
-        # quantize_x0 / score_corrector (plms.py:199-201, 218-219) call into caller-supplied objects (a first stage with
-        # .quantize, a corrector with .modify_score) between the pieces of the fused step; see step() below
-        if score_corrector is not None and self.model.parameterization != "eps":
-            raise AssertionError('score_corrector needs parameterization == "eps" (plms.py:200)')
-        if quantize_denoised and not hasattr(getattr(self.model, "first_stage_model", None), "quantize"):
-            raise MdxError("quantize_x0 needs model.first_stage_model.quantize (plms.py:219)")
-        corrector_kwargs = corrector_kwargs or {}
-        if not 0. <= float(noise_dropout) < 1.:
-            raise ValueError("noise_dropout must be in [0, 1)")
-        # hybrid (inpainting) conditioning: {"c_concat": mask + masked-image latent, "c_crossattn": text} (inpaint.py:84-88,
-        # WK plms.py:188-205); the concat part is the same for the cond and uncond halves
-        # The other DiffusionWrapper keys (WK ddpm.py:361-374) arrive the way plms.py:188-195 hands them over: a bare conditioning
-        # goes to the keyword the key reads -- 'concat': extra input channels (cond and uncond halves may differ), 'adm': class
-        # labels [B] (concatenated [uncond; cond] like a text context), None: no conditioning at all.
-        key = getattr(getattr(self.model, "model", None), "conditioning_key", "crossattn")
-        c_cat = uc_cat = None
-        if key == "concat":
-            c_cat = _first_tensor(cond["c_concat"] if isinstance(cond, dict) else cond)
-            if unconditional_conditioning is not None:
-                uc_cat = _first_tensor(unconditional_conditioning["c_concat"] if isinstance(unconditional_conditioning, dict)
-                                       else unconditional_conditioning)
-            cond = unconditional_conditioning = None
-        elif isinstance(cond, dict) and "c_concat" in cond:
-            c_cat = _first_tensor(cond["c_concat"])
-            cond = cond["c_crossattn"]
-            if isinstance(unconditional_conditioning, dict):
-                # WK plms.py:191-201 concatenates [uncond[k]; cond[k]] for EVERY dict key: an unconditional c_concat that differs from
-                # the conditional one goes into the unconditional half (inpaint.py passes the same tensor in both)
-                if unconditional_conditioning.get("c_concat") is not None:
-                    uc_cat = _first_tensor(unconditional_conditioning["c_concat"])
-                unconditional_conditioning = unconditional_conditioning["c_crossattn"]
-        if key is None:
-            cond = unconditional_conditioning = None
-        cond = _first_tensor(cond) if cond is not None else None
-        uc = _first_tensor(unconditional_conditioning) if unconditional_conditioning is not None else None
-        if key in ("crossattn", "hybrid") and not (isinstance(cond, torch.Tensor) and cond.is_cuda):
-            raise MdxError("conditioning must be a CUDA(HIP) tensor [B, T, context_dim]")
-        if key == "adm" and cond is None:
-            raise MdxError("'adm' conditioning needs the class labels [B] as `conditioning`")
-        if key == "concat" and c_cat is None:
-            raise MdxError("'concat' conditioning needs the extra input channels [B, C', H, W] as `conditioning`")
-        if isinstance(cond, torch.Tensor) and cond.is_cuda:
-            dev = cond.device
-        elif isinstance(c_cat, torch.Tensor) and c_cat.is_cuda:
-            dev = c_cat.device
-        elif isinstance(x_T, torch.Tensor) and x_T.is_cuda:
-            dev = x_T.device
-        else:
-            dev = self.model.unet.device
-        if cond is not None:
-            cond = torch.as_tensor(cond).to(dev)
-            uc = None if uc is None else torch.as_tensor(uc).to(dev)
-        b = shape[0]
-        # per-sample seeds: every draw below becomes one ops.randn_seeded launch, (stream, draw) = what it is for and which one
-        seeds = check_seeds(seeds, b, dev)
-        if x_T is None and seeds is not None:
-            img = ops.randn_seeded(seeds, ops.RNG_X_T, 0, tuple(shape[1:]))
-        elif x_T is None:
-            img = torch.randn(shape, device=dev, dtype=torch.float32, generator=self.generator)
-        else:
-            img = torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()
-        # ---- which timesteps, and which tables `index` selects from (plms.py:134-142, 205-208)
+    # ---- which timesteps, and which tables `index` selects from (plms.py:134-142, 205-208)
+    def _time_grid(self, ddim_use_original_steps, timesteps, t_start):
+        """(time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas): the timesteps in loop order (descending) and the
+        tables the grid index selects from.  t_start keeps the last t_start steps."""
         if ddim_use_original_steps:
             # every DDPM step (or the first `timesteps` of them): tables are the model's alphas_cumprod themselves.  The
             # reference reads `self.model.ddim_sigmas_for_original_num_steps` (plms.py:208), an attribute make_schedule
@@ -307,45 +255,57 @@ class _SamplerBase:
                 raise ValueError(f"timesteps must be in (0, {self.ddpm_num_timesteps}] with ddim_use_original_steps")
             if t_start is not None:
                 n_orig = self._check_t_start(t_start, n_orig)
-            time_range = np.arange(n_orig - 1, -1, -1, dtype=np.int64)
-            alphas, alphas_prev = self.alphas_cumprod, self.alphas_cumprod_prev
-            sqrt_one_minus_alphas = self.sqrt_one_minus_alphas_cumprod
-            sigmas = np.asarray(self.ddim_sigmas_for_original_num_steps, dtype=np.float32)
-        else:
-            ts = self.ddim_timesteps
-            if timesteps is not None:                                # plms.py:137-139: a prefix of the DDIM grid
-                n_ddim = ts.shape[0]
-                subset_end = int(min(timesteps / n_ddim, 1) * n_ddim) - 1
-                ts = ts[:subset_end]
-                if ts.shape[0] == 0:
-                    raise ValueError(f"timesteps={timesteps} selects an empty subset of the {n_ddim}-step DDIM grid")
-            if t_start is not None:
-                ts = ts[:self._check_t_start(t_start, ts.shape[0])]
-            time_range = np.flip(ts)
-            alphas, alphas_prev = self.ddim_alphas, self.ddim_alphas_prev
-            sqrt_one_minus_alphas, sigmas = self.ddim_sqrt_one_minus_alphas, self.ddim_sigmas
+            return (np.arange(n_orig - 1, -1, -1, dtype=np.int64), self.alphas_cumprod, self.alphas_cumprod_prev,
+                    self.sqrt_one_minus_alphas_cumprod, np.asarray(self.ddim_sigmas_for_original_num_steps, dtype=np.float32))
+        ts = self.ddim_timesteps
+        if timesteps is not None:                                    # plms.py:137-139: a prefix of the DDIM grid
+            n_ddim = ts.shape[0]
+            subset_end = int(min(timesteps / n_ddim, 1) * n_ddim) - 1
+            ts = ts[:subset_end]
+            if ts.shape[0] == 0:
+                raise ValueError(f"timesteps={timesteps} selects an empty subset of the {n_ddim}-step DDIM grid")
+        if t_start is not None:
+            ts = ts[:self._check_t_start(t_start, ts.shape[0])]
+        return np.flip(ts), self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas, self.ddim_sigmas
+
+    def _check_options(self, mask, x0, score_corrector, quantize_denoised, noise_dropout):
+        if mask is not None and x0 is None:
+            raise ValueError("mask blending needs x0 (plms.py:154)")
+        # quantize_x0 / score_corrector (plms.py:199-201, 218-219) call into caller-supplied objects (a first stage with
+        # .quantize, a corrector with .modify_score) between the pieces of the fused step; see step() in plms_sampling
+        if score_corrector is not None and self.model.parameterization != "eps":
+            raise AssertionError('score_corrector needs parameterization == "eps" (plms.py:200)')
+        if quantize_denoised and not hasattr(getattr(self.model, "first_stage_model", None), "quantize"):
+            raise MdxError("quantize_x0 needs model.first_stage_model.quantize (plms.py:219)")
+        if not 0. <= float(noise_dropout) < 1.:
+            raise ValueError("noise_dropout must be in [0, 1)")
+
+    # ---- plms.py:124-179 + 182-247
+    def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
+                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
+                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None):
+        """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
+        t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
+        mask / x0 blend of every step is one ops.q_sample launch, in place.
+        In order: validate, normalise the conditioning and draw the start latent, select the time grid, build the guided model
+        call, loop."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        check_seed_sources(seeds, self.generator, step_noises=step_noises, blend_noises=blend_noises, dropout_masks=dropout_masks)
+        self._check_options(mask, x0, score_corrector, quantize_denoised, noise_dropout)
+        corrector_kwargs = corrector_kwargs or {}
+        cond, uc, c_cat, uc_cat, dev = split_conditioning(self.model, cond, unconditional_conditioning, x_T)
+        b = shape[0]
+        # per-sample seeds: every draw below becomes one ops.randn_seeded launch, (stream, draw) = what it is for and which one
+        seeds = check_seeds(seeds, b, dev)
+        img = start_latent(x_T, seeds, shape, dev, self.generator)
+        time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas = self._time_grid(ddim_use_original_steps, timesteps,
+                                                                                         t_start)
         total_steps = int(time_range.shape[0])
         if verbose:
             print(f"Running {type(self).__name__} Sampling with {total_steps} timesteps")
         scale = float(unconditional_guidance_scale)
-        use_cfg = not ((uc is None and uc_cat is None) or scale == 1.)
-        nb = 2 * b if use_cfg else b
-        if cond is None:
-            c_in = None
-        else:
-            c_in = torch.cat([uc.to(cond.dtype), cond], 0).contiguous() if use_cfg else cond.contiguous()   # built ONCE
-        x_in = None                                                  # (plms.py:194 rebuilds the concat every step)
-        cx = shape[1]
-        if use_cfg or c_cat is not None:
-            ccat = 0 if c_cat is None else int(c_cat.shape[1])
-            x_in = torch.empty((nb, cx + ccat) + tuple(shape[2:]), device=dev, dtype=torch.float32)
-            if c_cat is not None:                                    # DiffusionWrapper 'hybrid': cat(x, c_concat), written once
-                cc = c_cat.to(device=dev, dtype=torch.float32)
-                x_in[nb - b:, cx:] = cc                              # batch = [uncond ; cond]
-                if use_cfg:
-                    x_in[:b, cx:] = cc if uc_cat is None else uc_cat.to(device=dev, dtype=torch.float32)
-        # the two halves of a guidance batch are the same UNet input unless the unconditional branch has its own c_concat
-        same_halves = use_cfg and c_in is not None and (c_cat is None or uc_cat is None)
         if mask is not None:
             mask = torch.as_tensor(mask).to(device=dev, dtype=torch.float32)
             x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32)
@@ -354,48 +314,22 @@ class _SamplerBase:
                 if mask.dim() != 4 or mask.shape[1] not in (1, shape[1]):
                     raise MdxError(f"mask must be [B, 1, H, W] or [B, C, H, W], got {tuple(mask.shape)}")
                 mask = mask.expand((b, mask.shape[1]) + tuple(shape[2:])).contiguous()
-        # per-step timestep vectors, fp32 on the device (the UNet's sinusoid takes float timesteps, util.py:111-131)
-        # (a fresh array: the flipped view of a ONE-step grid still counts as contiguous and keeps its negative stride)
-        t_all = torch.as_tensor(np.array(time_range, dtype=np.float32), device=dev)
-        # the timestep-only part of the UNet (time_embed MLP + the ResBlock emb_layers, openaimodel.py:550-551,188) for
-        # ALL steps in one batched pass; step i then hands row i to the UNet instead of recomputing it
-        temb_all = None
-        if (hasattr(self.model, "time_embedding_table") and os.environ.get("MDX_SAMPLER_TEMB_TABLE", "1") != "0"
-                and getattr(getattr(self.model, "unet", None), "num_classes", None) is None):     # (label_emb(y) joins emb per call)
-            temb_all = self.model.time_embedding_table(t_all)
-        t_all = t_all[:, None].expand(total_steps, nb).contiguous()
+        guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, time_range)
+        draws = _Draws(seeds, self.generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout)
 
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
         pool = [torch.empty_like(img) for _ in range(4)]  # eps history buffers (3 live + 1 being written)
         hist = []                                         # newest first; at most 3 (plms.py:169-171)
         pred_x0 = torch.empty_like(img)
         x_next = torch.empty_like(img)
-
-        def model_eps(x, i):
-            t_row, temb = t_all[i], (None if temb_all is None else temb_all[i])
-            if use_cfg:
-                x_in[:b, :cx].copy_(x)
-                x_in[b:, :cx].copy_(x)
-                eps, keep = self._eps_nhwc(x_in, t_row, c_in, temb, cfg_dup=same_halves)
-                return eps[:b], eps[b:], keep           # batch = [uncond ; cond] (plms.py:192-195)
-            if x_in is not None:
-                x_in[:, :cx].copy_(x)
-                eps, keep = self._eps_nhwc(x_in, t_row, c_in, temb)
-                return None, eps, keep
-            eps, keep = self._eps_nhwc(x, t_row, c_in, temb)
-            return None, eps, keep
-
-        drop_count, noise_count = [0], [0]
-
         hook_e = torch.empty_like(img) if score_corrector is not None else None
         hook_x = torch.empty_like(img) if score_corrector is not None else None
         hook_p = torch.empty_like(img) if quantize_denoised else None
         # a v-prediction model (SD 2.x 768-v): the step kernel converts the UNet's output to eps at the point (xm, tm) the model
-        # was evaluated at; everything after that -- history, pred_x0, x_prev -- is the eps path.  "eps" / "x0" keep the old entry.
-        v_pred = getattr(self.model, "parameterization", "eps") == "v"
-        # guidance rescale: the CFG-combined output of every model evaluation is pulled back to the conditional output's
-        # per-sample std inside the step launch; without guidance (or at 0) the calls below are the ones always made
-        rescale = use_cfg and guidance_rescale != 0.
+        # was evaluated at; everything after that -- history, pred_x0, x_prev -- is the eps path.  Guidance rescale: the
+        # CFG-combined output of every model evaluation is pulled back to the conditional output's per-sample std inside the
+        # step launch.  ops.sampler_update picks the entry.
+        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
 
         def step(x, eps_u, eps_c, index, coef, olds, e_out, x_out, p_out, xm=None, tm=None):
             """One get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] * olds[k-1], e_t = the
@@ -404,16 +338,12 @@ class _SamplerBase:
             a_t, a_prev = np.float32(alphas[index]), np.float32(alphas_prev[index])
             sigma_t = np.float32(sigmas[index])
             if score_corrector is not None:
-                # e_t leaves the fused kernel (pass 1: CFG combine only), goes through the caller's modify_score, and
-                # re-enters as a single NHWC fp16 model output (pass 2: multistep mix + update)
-                # (a corrector implies an eps model -- asserted above -- so hook_e holds eps and PRED_EPS is the whole story)
-                if rescale:     # the rescale belongs to the combine that produces e_t, so to this pass
-                    ops.sampler_step_rescale(x, None, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_EPS, 1., 0., [],
-                                             (1., 0., 0., 0.), 1., 0., 1., 0., 0., None, hook_e, hook_x, None,
-                                             guidance_rescale)
-                else:
-                    ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, [], (1., 0., 0., 0.), 1., 0., 1., 0., 0.,
-                                     None, hook_e, hook_x, None)
+                # e_t leaves the fused kernel (pass 1: CFG combine only -- the rescale belongs to the combine that produces
+                # e_t, so to this pass), goes through the caller's modify_score, and re-enters as a single NHWC fp16 model
+                # output (pass 2: multistep mix + update)
+                # (a corrector implies an eps model -- _check_options -- so hook_e holds eps and PRED_EPS is the whole story)
+                ops.sampler_update(x, eps_u, eps_c, scale, ops.PRED_EPS, [], (1., 0., 0., 0.),
+                                   (1., 0., 1., 0., 0., None, hook_e, hook_x, None), guidance_rescale)
                 tvec = torch.full((b,), int(tm), device=dev, dtype=torch.long)
                 e_mod = score_corrector.modify_score(self.model, hook_e, x if xm is None else xm, tvec, cond,
                                                      **corrector_kwargs)
@@ -422,42 +352,13 @@ class _SamplerBase:
                     raise MdxError(f"score_corrector returned shape {tuple(e_mod.shape)}, expected {tuple(x.shape)}")
                 eps_c = ops.nchw_to_nhwc(e_mod, (x.shape[1] + 7) // 8 * 8)
                 eps_u = None
-            noise = None
-            if float(sigma_t) != 0.0 and seeds is not None:   # temperature and dropout inside the one launch
-                noise = ops.randn_seeded(seeds, ops.RNG_STEP, noise_count[0], tuple(x.shape[1:]), scale=temperature,
-                                         dropout=noise_dropout)
-                noise_count[0] += 1
-            elif float(sigma_t) != 0.0:
-                if step_noises is not None:   # tests inject the k-th N(0,1) draw to compare with the oracle (eta != 0)
-                    noise = torch.as_tensor(step_noises[noise_count[0]]).to(device=dev, dtype=torch.float32) * temperature
-                else:
-                    noise = torch.randn(x.shape, device=dev, dtype=torch.float32, generator=self.generator) * temperature
-                noise_count[0] += 1
-                if noise_dropout > 0.:
-                    # plms.py:224-225 `ops.dropout(noise, p=noise_dropout)`: zero with probability p, scale the rest by
-                    # 1 / (1 - p).  dropout_masks[k] (1 = keep) injects the k-th draw so that tests can feed the oracle
-                    # the same mask; otherwise it comes from the sampler's generator.
-                    if dropout_masks is not None:
-                        keep = torch.as_tensor(dropout_masks[drop_count[0]]).to(device=dev, dtype=torch.float32)
-                    else:
-                        keep = (torch.rand(x.shape, device=dev, generator=self.generator) >= noise_dropout).to(torch.float32)
-                    drop_count[0] += 1
-                    noise = noise * keep / (1. - float(noise_dropout))
+            noise = draws.step() if float(sigma_t) != 0.0 else None
             if quantize_denoised and p_out is None:
                 p_out = hook_p
             update = (np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
                       np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t, noise, e_out, x_out, p_out)
-            if rescale and eps_u is not None:
-                am, bm = ((self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)]) if v_pred
-                          else (1., 0.))
-                ops.sampler_step_rescale(x, xm, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V if v_pred else ops.PRED_EPS,
-                                         am, bm, olds, coef, *update, guidance_rescale)
-            elif v_pred:
-                ops.sampler_step_pred(x, xm, eps_u, eps_c, eps_c.shape[-1], scale, ops.PRED_V,
-                                      self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)],
-                                      olds, coef, *update)
-            else:
-                ops.sampler_step(x, eps_u, eps_c, eps_c.shape[-1], scale, olds, coef, *update)
+            ops.sampler_update(x, eps_u, eps_c, scale, pred_type, olds, coef, update, guidance_rescale, xm,
+                               self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)])
             if quantize_denoised:
                 # pred_x0, _, *_ = first_stage_model.quantize(pred_x0) (plms.py:218-219); x_prev is linear in pred_x0
                 q = self.model.first_stage_model.quantize(p_out)[0]
@@ -467,13 +368,8 @@ class _SamplerBase:
 
         for i, step_t in enumerate(time_range):
             index = total_steps - i - 1
-            if mask is not None:                                     # plms.py:153-157 (WK: q_sample gets explicit noise)
-                if seeds is not None:
-                    noise = ops.randn_seeded(seeds, ops.RNG_BLEND, i, tuple(shape[1:]))
-                elif blend_noises is not None:                        # tests inject the draws to compare with the oracle
-                    noise = torch.as_tensor(blend_noises[i]).to(device=dev, dtype=torch.float32)
-                else:
-                    noise = torch.randn(x0.shape, device=dev, dtype=torch.float32, generator=self.generator)
+            if mask is not None:
+                noise = draws.blend(i, x0)
                 if t_start is not None:                               # q_sample + blend, one launch, in place
                     ops.q_sample(x0, noise.contiguous(), self.sqrt_alphas_cumprod[int(step_t)],
                                  self.sqrt_one_minus_alphas_cumprod[int(step_t)], out=img, mask=mask, img=img)
@@ -481,7 +377,7 @@ class _SamplerBase:
                     ts = torch.full((b,), int(step_t), device=dev, dtype=torch.long)
                     img_orig = self.model.q_sample(x0, ts, noise)
                     img = img_orig * mask + (1. - mask) * img
-            eps_u, eps_c, _keep = model_eps(img, i)
+            eps_u, eps_c = guided(img, i)
             if not self.multistep:
                 step(img, eps_u, eps_c, index, (1., 0., 0., 0.), [], None, x_next, pred_x0, tm=step_t)
             else:
@@ -491,7 +387,7 @@ class _SamplerBase:
                     # Pseudo Improved Euler (2nd order), plms.py:231-235: S+1 UNet calls in total
                     step(img, eps_u, eps_c, index, (1., 0., 0., 0.), [], e_buf, x_next, None, tm=step_t)
                     i_next = min(i + 1, total_steps - 1)
-                    eps_u2, eps_c2, _keep2 = model_eps(x_next, i_next)
+                    eps_u2, eps_c2 = guided(x_next, i_next)
                     step(img, eps_u2, eps_c2, index, (.5, .5, 0., 0.), [e_buf], None, x_next, pred_x0,
                          xm=x_next, tm=time_range[i_next])
                 elif n_old == 1:  # Adams-Bashforth 2, plms.py:236-238

@@ -788,6 +788,25 @@ def sampler_step_rescale(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
         B, C, H, W, _stream()), "mdx_sampler_step_rescale_f32")
 
 
+def sampler_update(x, out_u, out_c, cfg_scale, pred_type, olds, coef, update, guidance_rescale=0., x_model=None,
+                   sqrt_at_model=1., sqrt_one_minus_at_model=0.):
+    """The one fused step launch of every LDM sampler, through the entry that does no more than the step needs: the rescale
+    entry iff guidance_rescale != 0 and there is an unconditional half to combine, else the pred entry iff the model output
+    is v, else the plain entry (bit-identical where they overlap, include/mdx.h).  out_u / out_c: the halves of the model
+    output (out_u None: no guidance); (x_model, sqrt_at_model, sqrt_one_minus_at_model): the point the model was evaluated
+    at, read for a v output only (x_model None = x); update: (sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise,
+    e_t_out, x_prev, pred_x0) of sampler_step."""
+    v = pred_type == PRED_V
+    if guidance_rescale != 0. and out_u is not None:
+        sampler_step_rescale(x, x_model, out_u, out_c, out_c.shape[-1], cfg_scale, pred_type, sqrt_at_model if v else 1.,
+                             sqrt_one_minus_at_model if v else 0., olds, coef, *update, guidance_rescale)
+    elif v:
+        sampler_step_pred(x, x_model, out_u, out_c, out_c.shape[-1], cfg_scale, pred_type, sqrt_at_model,
+                          sqrt_one_minus_at_model, olds, coef, *update)
+    else:
+        sampler_step(x, out_u, out_c, out_c.shape[-1], cfg_scale, olds, coef, *update)
+
+
 def probe_mfma(a, b):
     c = torch.empty((64, 16), dtype=f32, device=a.device)
     _lib.check(_lib.load().mdx_probe_mfma_32x32x16_f16(_ptr(a), _ptr(b), _ptr(c), _stream()), "mdx_probe_mfma")

@@ -80,6 +80,83 @@ class DiffusionPipeline:
         if hasattr(unet, "set_max_context_len") and T > int(unet.max_context_len):
             unet.set_max_context_len(80 * -(-T // 80))
 
+    # ---- what every entry point does around its sampler call
+    @property
+    def _dpm(self):
+        """DPM-Solver starts a partial run at a continuous time and has no decode(); PLMS / DDIM count grid steps."""
+        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        return isinstance(self.sampler, DPMSolverSampler)
+
+    def _encoded(self, prompts, c, uc, required=True):
+        """(c, uc) with one number of context windows: the prompts encoded (txt2img.py:246-251), or the tensors given."""
+        if prompts is not None:
+            uc = self.model.get_learned_conditioning(len(prompts) * [""])   # txt2img.py:246-248
+            c = self.model.get_learned_conditioning(list(prompts))            # txt2img.py:251
+        if c is None and required:
+            raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
+        return self.match_conditioning(c, uc, from_prompts=prompts is not None)
+
+    def _on_device(self, c, uc, B):
+        """Single rank: c and uc fp16 on the device, a batch-1 uc repeated, the UNet's context capacity fitted to them."""
+        c = c.to(self.device, torch.float16)
+        uc = None if uc is None else uc.to(self.device, torch.float16)
+        if uc is not None and uc.shape[0] == 1 and B > 1:
+            uc = uc.expand(B, -1, -1).contiguous()
+        self.fit_context(c)
+        return c, uc
+
+    def _draw(self, given, seeds, stream, shape, sd):
+        """N(0, 1) [B, ...]: the tensor a caller passed, else sample b from seeds[b] alone, else RandomState(sd) as start_noise."""
+        if given is not None:
+            return given
+        if seeds is not None:
+            return self.seeded_noise(seeds, stream, shape[1:])
+        return self.start_noise(shape[0], shape[1:], sd)
+
+    @staticmethod
+    def _sampler_kw(guidance_rescale, seeds):
+        """The keywords only a run that uses them hands its sampler (a caller's own sampler object may not take them)."""
+        kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
+        if seeds is not None:
+            kw["seeds"] = seeds
+        return kw
+
+    @staticmethod
+    def _check_strength(what, strength, steps):
+        """t_enc = int(strength * steps), the steps of the `steps`-step schedule that remain to run."""
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"{what}: strength must be in (0, 1], got {strength!r}")
+        t_enc = int(float(strength) * steps)
+        if t_enc == 0:
+            raise ValueError(f"{what}: strength {strength!r} leaves no step of {steps} to run")
+        return t_enc
+
+    def _partial_start(self, steps, t_enc, eta):
+        """(start, a, b): where the last t_enc of `steps` steps begin -- a grid index for PLMS / DDIM, for DPM-Solver the
+        continuous time t_0 + (T - t_0) * t_enc / steps of the full run's own intervals -- and the forward-process coefficients
+        a * x0 + b * noise of that level."""
+        if self._dpm:
+            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
+            start = t_0 + (1.0 - t_0) * t_enc / steps
+        else:
+            self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
+            start = t_enc
+        return (start,) + tuple(self.sampler.q_coefficients(start))
+
+    def _run_partial(self, x_enc, cond, uc, start, t_enc, scale, callback, img_callback, kw, mask=None, x0=None):
+        """The last t_enc steps from x_enc, a latent noised to `start` (_partial_start): the final latent."""
+        common = dict(unconditional_guidance_scale=scale, unconditional_conditioning=uc, callback=callback,
+                      img_callback=img_callback, **kw)
+        if self._dpm:
+            return self.sampler.sample(S=t_enc, conditioning=cond, batch_size=int(x_enc.shape[0]), shape=list(x_enc.shape[1:]),
+                                       verbose=False, x_T=x_enc, t_start=start, **common)[0]
+        blend_kw = {} if mask is None else {"mask": mask, "x0": x0}
+        return self.sampler.decode(x_enc, cond, t_enc, **blend_kw, **common)[0]
+
+    def _decoded(self, samples):
+        x = self.model.decode_first_stage(samples)                    # txt2img.py:265-266
+        return torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
+
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
                  decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
                  guidance_rescale=0.0, seeds=None):
@@ -92,11 +169,8 @@ class DiffusionPipeline:
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         rank, n = D.world()
         shape = [4, H // 8, W // 8]                                   # txt2img.py:253
-        if prompts is not None and rank == 0:
-            uc = self.model.get_learned_conditioning(len(prompts) * [""])   # txt2img.py:246-248
-            c = self.model.get_learned_conditioning(list(prompts))            # txt2img.py:251
         if rank == 0:
-            c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
+            c, uc = self._encoded(prompts, c, uc, required=n == 1)
         if n > 1:
             # (the broadcast payload is sized by the UNet's capacity: for long prompts every rank calls
             # unet.set_max_context_len beforehand; broadcast_conditioning's length check is the guard)
@@ -106,8 +180,8 @@ class DiffusionPipeline:
                                "(the global batch) to size the broadcast")
             unet = self.model.unet
             seeds = self.check_seeds(seeds, B)
-            if rank == 0 and x_T is None:     # the global x_T rides the one broadcast, seeded or not
-                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
+            if rank == 0:                     # the global x_T rides the one broadcast, seeded or not
+                x_T = self._draw(x_T, seeds, ops.RNG_X_T, [B] + shape, seed)
             if seeds is not None:
                 lo, hi = D.shard_bounds(B, rank, n)
                 seeds = seeds[lo:hi]
@@ -118,29 +192,19 @@ class DiffusionPipeline:
                 B, (int(getattr(unet, "max_context_len", 80)), int(unet.context_dim)), shape, self.device,
                 per_sample_uc=per_sample_uc)
         else:
-            if c is None:
-                raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
             B = int(c.shape[0])
             seeds = self.check_seeds(seeds, B)
-            if x_T is None:
-                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
-            c = c.to(self.device, torch.float16)
-            uc = None if uc is None else uc.to(self.device, torch.float16)
-            if uc is not None and uc.shape[0] == 1 and B > 1:
-                uc = uc.expand(B, -1, -1).contiguous()
+            x_T = self._draw(x_T, seeds, ops.RNG_X_T, [B] + shape, seed)
+            c, uc = self._on_device(c, uc, B)
             x_T = x_T.to(self.device)
-            self.fit_context(c)
-        # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W
-        local_b = int(c.shape[0])
-        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}   # (a caller's own sampler object)
-        seeds_kw = {} if seeds is None else {"seeds": seeds}        # this rank's samples: the eta > 0 step draws
-        samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=local_b, shape=shape, verbose=False,
+        # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W;
+        # the seeds are this rank's samples': the eta > 0 step draws
+        samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=int(c.shape[0]), shape=shape, verbose=False,
                                              unconditional_guidance_scale=scale, unconditional_conditioning=uc,
                                              eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
-                                             **rescale_kw, **seeds_kw)
+                                             **self._sampler_kw(guidance_rescale, seeds))
         if decode:
-            x = self.model.decode_first_stage(samples)                # txt2img.py:265-266
-            samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
+            samples = self._decoded(samples)
         if gather and n > 1:
             samples = D.gather_latents(samples)
         return samples
@@ -161,45 +225,16 @@ class DiffusionPipeline:
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
-        if not 0.0 < float(strength) <= 1.0:
-            raise ValueError(f"img2img: strength must be in (0, 1], got {strength!r}")
-        t_enc = int(float(strength) * steps)
-        if t_enc == 0:
-            raise ValueError(f"img2img: strength {strength!r} leaves no step of {steps} to run")
+        t_enc = self._check_strength("img2img", strength, steps)
         if D.world()[1] > 1:
             raise MdxError("img2img runs on a single rank (the sharded form is not built)")
-        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
-        dpm = isinstance(self.sampler, DPMSolverSampler)
-        if mask is not None and dpm:
+        if mask is not None and self._dpm:
             raise NotImplementedError("img2img: mask blending is implemented by PLMSSampler / DDIMSampler")
-        if prompts is not None:
-            uc = self.model.get_learned_conditioning(len(prompts) * [""])
-            c = self.model.get_learned_conditioning(list(prompts))
-        if c is None:
-            raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
-        c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
+        c, uc = self._encoded(prompts, c, uc)
         B = int(c.shape[0])
         seeds = self.check_seeds(seeds, B)
-        c = c.to(self.device, torch.float16)
-        uc = None if uc is None else uc.to(self.device, torch.float16)
-        if uc is not None and uc.shape[0] == 1 and B > 1:
-            uc = uc.expand(B, -1, -1).contiguous()
-        self.fit_context(c)
-        # where the partial run starts: a grid index for PLMS / DDIM, a continuous time for DPM-Solver -- the last t_enc of the
-        # full run's own `steps` intervals, t_0 + (T - t_0) * t_enc / steps
-        if dpm:
-            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
-            start = t_0 + (1.0 - t_0) * t_enc / steps
-            a, b = self.sampler.q_coefficients(start)
-        else:
-            self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
-            a, b = self.sampler.q_coefficients(t_enc)
-        def draw(given, shape, sd, stream):
-            if given is not None:
-                return given
-            if seeds is not None:
-                return self.seeded_noise(seeds, stream, shape[1:])
-            return torch.from_numpy(np.random.RandomState(sd).randn(*shape).astype(np.float32))
+        c, uc = self._on_device(c, uc, B)
+        start, a, b = self._partial_start(steps, t_enc, eta)
         if init_image is not None:
             vae = self.model.first_stage_model
             if vae is None or not hasattr(vae, "encode_noised"):
@@ -208,34 +243,20 @@ class DiffusionPipeline:
             shape = vae.latent_shape(x.shape)                         # the encoder's output size, not H // 8
             if seeds is not None and x.shape[0] != B:
                 raise MdxError(f"img2img: {x.shape[0]} init images but {B} conditionings")
-            z0, x_enc = vae.encode_noised(x, self.model.scale_factor, a, b, draw(noise, shape, seed, ops.RNG_ENCODE),
-                                          post_noise=(draw(post_noise, shape, seed + 1, ops.RNG_POSTERIOR)
+            z0, x_enc = vae.encode_noised(x, self.model.scale_factor, a, b, self._draw(noise, seeds, ops.RNG_ENCODE, shape, seed),
+                                          post_noise=(self._draw(post_noise, seeds, ops.RNG_POSTERIOR, shape, seed + 1)
                                                       if sample_posterior else None),
                                           sample=sample_posterior)
         else:
             z0 = init_latent.to(device=self.device, dtype=torch.float32).contiguous()
             if seeds is not None and z0.shape[0] != B:
                 raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
-            x_enc = self.sampler.stochastic_encode(z0, start if dpm else t_enc,
-                                                   noise=draw(noise, z0.shape, seed, ops.RNG_ENCODE))
+            x_enc = self.sampler.stochastic_encode(z0, start, noise=self._draw(noise, seeds, ops.RNG_ENCODE, z0.shape, seed))
         if z0.shape[0] != B:
             raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
-        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
-        seeds_kw = {} if seeds is None else {"seeds": seeds}
-        if dpm:
-            samples, _ = self.sampler.sample(S=t_enc, conditioning=c, batch_size=B, shape=list(z0.shape[1:]), verbose=False,
-                                             unconditional_guidance_scale=scale, unconditional_conditioning=uc, x_T=x_enc,
-                                             callback=callback, img_callback=img_callback, t_start=start, **rescale_kw,
-                                             **seeds_kw)
-        else:
-            blend_kw = {} if mask is None else {"mask": mask, "x0": z0}
-            samples, _ = self.sampler.decode(x_enc, c, t_enc, unconditional_guidance_scale=scale,
-                                             unconditional_conditioning=uc, callback=callback, img_callback=img_callback,
-                                             **blend_kw, **rescale_kw, **seeds_kw)
-        if decode:
-            x = self.model.decode_first_stage(samples)
-            samples = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
-        return samples
+        samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, callback, img_callback,
+                                    self._sampler_kw(guidance_rescale, seeds), mask=mask, x0=z0)
+        return self._decoded(samples) if decode else samples
 
     # ---- inpainting: wukong-huahua/inpaint.py, image and mask in, composited image out
     @staticmethod
@@ -280,19 +301,16 @@ class DiffusionPipeline:
         B = self._check_inpaint_inputs(image, mask, batch_size)
         seeds = self.check_seeds(seeds, B)
         image, mask = self._inpaint_to_device(image, mask, B)
-        shape = vae.latent_shape(image.shape)                         # the encoder's output size, not H // 8
-        if not sample_posterior:
-            post_noise = None
-        elif post_noise is None and seeds is not None:
-            post_noise = self.seeded_noise(seeds, ops.RNG_POSTERIOR, shape[1:])
-        elif post_noise is None:
-            post_noise = torch.from_numpy(np.random.RandomState(seed + 1).randn(*shape).astype(np.float32))
-        return self._inpaint_c_concat(vae, image, mask, post_noise, sample_posterior)
+        return self._inpaint_c_concat(vae, image, mask, post_noise, sample_posterior, seeds, seed)[0]
 
-    def _inpaint_c_concat(self, vae, image, mask, post_noise, sample_posterior):
-        """image / mask as _inpaint_to_device leaves them: one masked-image launch, the encoder, one concat launch."""
+    def _inpaint_c_concat(self, vae, image, mask, post_noise, sample_posterior, seeds, seed):
+        """image / mask as _inpaint_to_device leaves them: the posterior draw (None for the mode), one masked-image launch, the
+        encoder, one concat launch.  Returns (c_concat, the posterior draw)."""
+        post = None
+        if sample_posterior:                                          # (the encoder's output size, not H // 8)
+            post = self._draw(post_noise, seeds, ops.RNG_POSTERIOR, vae.latent_shape(image.shape), seed + 1)
         masked = ops.inpaint_mask_image(image, mask)
-        return vae.encode_concat(masked, mask, self.model.scale_factor, post_noise=post_noise, sample=sample_posterior)
+        return vae.encode_concat(masked, mask, self.model.scale_factor, post_noise=post, sample=sample_posterior), post
 
     def inpaint(self, image, mask, prompts=None, c=None, uc=None, steps=30, scale=7.5, eta=0.0, strength=1.0, seed=42,
                 seeds=None, x_T=None, noise=None, post_noise=None, sample_posterior=True, mask_blur=0.0, composite=True,
@@ -314,11 +332,7 @@ class DiffusionPipeline:
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if output not in ("float", "uint8"):
             raise ValueError(f"inpaint: output must be 'float' or 'uint8', got {output!r}")
-        if not 0.0 < float(strength) <= 1.0:
-            raise ValueError(f"inpaint: strength must be in (0, 1], got {strength!r}")
-        t_enc = int(float(strength) * steps)
-        if t_enc == 0:
-            raise ValueError(f"inpaint: strength {strength!r} leaves no step of {steps} to run")
+        t_enc = self._check_strength("inpaint", strength, steps)
         mask_blur = float(mask_blur)
         if not mask_blur >= 0.0:
             raise ValueError(f"inpaint: mask_blur must be >= 0, got {mask_blur!r}")
@@ -326,12 +340,7 @@ class DiffusionPipeline:
             ops.feather_weights(mask_blur)                            # (the radius cap, before any work)
         if D.world()[1] > 1:
             raise MdxError("inpaint runs on a single rank (the sharded form is not built)")
-        if prompts is not None:
-            uc = self.model.get_learned_conditioning(len(prompts) * [""])
-            c = self.model.get_learned_conditioning(list(prompts))
-        if c is None:
-            raise MdxError("DiffusionPipeline: pass prompts (with a text encoder attached) or (c, uc) tensors")
-        c, uc = self.match_conditioning(c, uc, from_prompts=prompts is not None)
+        c, uc = self._encoded(prompts, c, uc)
         B = int(c.shape[0])
         seeds = self.check_seeds(seeds, B)
         try:
@@ -339,22 +348,39 @@ class DiffusionPipeline:
         except MdxError as e:
             raise MdxError(f"{e} -- the batch is the conditioning's, {B}") from None
         hybrid = getattr(getattr(self.model, "model", None), "conditioning_key", "crossattn") == "hybrid"
-        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
-        dpm = isinstance(self.sampler, DPMSolverSampler)
-        if not hybrid and dpm:
+        if not hybrid and self._dpm:
             raise NotImplementedError("inpaint with a 4-channel model blends under the mask every step: implemented by "
                                       "PLMSSampler / DDIMSampler")
         vae = self._inpaint_vae()
         image, mask = self._inpaint_to_device(image, mask, B)
-        if hybrid:
-            samples = self._inpaint_hybrid(vae, dpm, image, mask, c, uc, B, steps, scale, eta, float(strength), t_enc, seed, seeds,
-                                           x_T, noise, post_noise, sample_posterior, guidance_rescale, callback, img_callback)
-        else:
+        if not hybrid:
             # the blend path: img2img's mask means KEEP
             keep = 1.0 - ops.inpaint_resize_mask(mask, vae.latent_shape(image.shape)[2:])
             samples = self.img2img(init_image=image, strength=strength, c=c, uc=uc, steps=steps, scale=scale, eta=eta, seed=seed,
                                    noise=noise, post_noise=post_noise, sample_posterior=sample_posterior, mask=keep,
                                    callback=callback, img_callback=img_callback, guidance_rescale=guidance_rescale, seeds=seeds)
+        else:
+            c, uc = self._on_device(c, uc, B)
+            lat = vae.latent_shape(image.shape)
+            c_cat, post = self._inpaint_c_concat(vae, image, mask, post_noise, sample_posterior, seeds, seed)
+            cond = {"c_concat": c_cat, "c_crossattn": c}                  # inpaint.py:88
+            uc_full = None if uc is None else {"c_concat": c_cat, "c_crossattn": uc}      # inpaint.py:91-92
+            kw = self._sampler_kw(guidance_rescale, seeds)
+            if t_enc == steps:
+                # the reference's run (strength 1): pure noise, every step; neither mask nor x0 goes to the sampler (inpaint.py's
+                # x0= without a mask is inert)
+                x_T = self._draw(x_T, seeds, ops.RNG_X_T, lat, seed)
+                samples = self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=list(lat[1:]), verbose=False,
+                                              eta=eta, x_T=x_T.to(self.device), unconditional_guidance_scale=scale,
+                                              unconditional_conditioning=uc_full, callback=callback, img_callback=img_callback,
+                                              **kw)[0]
+            else:
+                # strength < 1: start from the (unmasked) image's own latent, noised to where the last t_enc steps begin -- img2img
+                start, a, b = self._partial_start(steps, t_enc, eta)
+                _, x_enc = vae.encode_noised(image, self.model.scale_factor, a, b,
+                                             self._draw(noise, seeds, ops.RNG_ENCODE, lat, seed), post_noise=post,
+                                             sample=sample_posterior)
+                samples = self._run_partial(x_enc, cond, uc_full, start, t_enc, scale, callback, img_callback, kw)
         if not decode:
             return samples
         x = self.model.decode_first_stage(samples).to(torch.float32).contiguous()
@@ -362,50 +388,3 @@ class DiffusionPipeline:
         if composite:
             alpha = ops.mask_feather(mask, mask_blur) if mask_blur > 0.0 else mask
         return ops.inpaint_composite(x, image if composite else None, alpha, output=output)
-
-    def _inpaint_hybrid(self, vae, dpm, image, mask, c, uc, B, steps, scale, eta, strength, t_enc, seed, seeds, x_T, noise,
-                        post_noise, sample_posterior, guidance_rescale, callback, img_callback):
-        """inpaint()'s sampling on a hybrid model: the final latent."""
-        c = c.to(self.device, torch.float16)
-        uc = None if uc is None else uc.to(self.device, torch.float16)
-        if uc is not None and uc.shape[0] == 1 and B > 1:
-            uc = uc.expand(B, -1, -1).contiguous()
-        self.fit_context(c)
-        lat = vae.latent_shape(image.shape)
-        shape = list(lat[1:])
-
-        def draw(given, sd, stream):
-            if given is not None:
-                return given
-            if seeds is not None:
-                return self.seeded_noise(seeds, stream, shape)
-            return torch.from_numpy(np.random.RandomState(sd).randn(*lat).astype(np.float32))
-        post = draw(post_noise, seed + 1, ops.RNG_POSTERIOR) if sample_posterior else None
-        c_cat = self._inpaint_c_concat(vae, image, mask, post, sample_posterior)
-        cond = {"c_concat": c_cat, "c_crossattn": c}                  # inpaint.py:88
-        uc_full = None if uc is None else {"c_concat": c_cat, "c_crossattn": uc}      # inpaint.py:91-92
-        rescale_kw = {"guidance_rescale": guidance_rescale} if guidance_rescale != 0. else {}
-        seeds_kw = {} if seeds is None else {"seeds": seeds}
-        common = dict(unconditional_guidance_scale=scale, unconditional_conditioning=uc_full, callback=callback,
-                      img_callback=img_callback, **rescale_kw, **seeds_kw)
-        if strength >= 1.0:
-            # the reference's run: pure noise, every step; neither mask nor x0 goes to the sampler (inpaint.py's x0= without a
-            # mask is inert)
-            if x_T is None:
-                x_T = self.start_noise(B, shape, seed) if seeds is None else self.seeded_noise(seeds, ops.RNG_X_T, shape)
-            return self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=shape, verbose=False, eta=eta,
-                                       x_T=x_T.to(self.device), **common)[0]
-        # strength < 1: start from the (unmasked) image's own latent, noised to where the last t_enc steps begin -- img2img
-        if dpm:
-            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
-            start = t_0 + (1.0 - t_0) * t_enc / steps
-            a, b = self.sampler.q_coefficients(start)
-        else:
-            self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
-            a, b = self.sampler.q_coefficients(t_enc)
-        _, x_enc = vae.encode_noised(image, self.model.scale_factor, a, b, draw(noise, seed, ops.RNG_ENCODE), post_noise=post,
-                                     sample=sample_posterior)
-        if dpm:
-            return self.sampler.sample(S=t_enc, conditioning=cond, batch_size=B, shape=shape, verbose=False, x_T=x_enc,
-                                       t_start=start, **common)[0]
-        return self.sampler.decode(x_enc, cond, t_enc, **common)[0]
