@@ -523,6 +523,48 @@ int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const voi
                                  const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
                                  float guidance_rescale, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
 
+/* ---- the same fused update with every per-sample scalar read from a device table: requests with different guidance
+ * scales, rescale strengths and step counts (so different schedule points) share ONE launch.  Neither reference tree has it.
+ * table: device [B][MDX_STEP_ROW] fp32, row b = the scalars of sample b:
+ *   [MDX_STEP_ACTIVE]                   1 = update this sample, 0 = its schedule has ended (below)
+ *   [MDX_STEP_CFG_SCALE]                cfg_scale
+ *   [MDX_STEP_RESCALE]                  guidance_rescale (phi), in [0, 1]
+ *   [MDX_STEP_SQRT_AT_MODEL], [MDX_STEP_SQRT_ONE_MINUS_AT_MODEL]     read for MDX_PRED_V only
+ *   [MDX_STEP_C0 + k], k = 0..3         coef4[k]
+ *   [MDX_STEP_SQRT_AT], [MDX_STEP_SQRT_ONE_MINUS_AT], [MDX_STEP_SQRT_A_PREV], [MDX_STEP_DIR_COEF], [MDX_STEP_SIGMA]
+ *   [14], [15]                          reserved, 0
+ * An ACTIVE row b computes what the scalar entry for its scalars computes on sample b alone, bit for bit:
+ * mdx_sampler_step_rescale_f32 if phi != 0 and out_u is given, else mdx_sampler_step_pred_f32 (with MDX_PRED_EPS:
+ * mdx_sampler_step_f32).  A term is skipped -- its tensor not read -- when its pointer is NULL OR the row's coefficient is
+ * exactly 0 (coef4[1..3] for old1..3, sigma for noise): one sample of a batch may be on a lower-order step while the pointer
+ * is live for the others.  A row with phi == 0 has f = 1 exactly, reads no statistics, and factor_out[b] = 1.
+ * An INACTIVE row b: x_prev[b] = x[b], copied (nothing to do where x_prev aliases x); pred_x0[b], e_t_out[b] and
+ * factor_out[b] are NOT written.
+ * any_rescale: non-zero iff some active row has phi != 0.  Then a workgroup owns a sample (as in
+ * mdx_sampler_step_rescale_f32) and out_u must be given; with 0 every row runs with f = 1 whatever its phi says, and a
+ * sample is spread over several workgroups.
+ * Aliasing as mdx_sampler_step_pred_f32: x_prev may alias x and / or x_model element for element; the outputs alias no
+ * other input, and nothing aliases the table.  Only x_prev, pred_x0, e_t_out and factor_out are written.
+ * Refused before any launch: everything mdx_sampler_step_pred_f32 refuses, table == NULL, any_rescale with out_u == NULL or
+ * with C * H * W < 2, C * H * W above 31 bits, B above 65535 without any_rescale.  The table's VALUES are on the device and are
+ * not checked here: whoever builds the table checks them (finite, phi in [0, 1], sqrt_at != 0 on active rows). */
+#define MDX_STEP_ROW 16
+#define MDX_STEP_ACTIVE 0
+#define MDX_STEP_CFG_SCALE 1
+#define MDX_STEP_RESCALE 2
+#define MDX_STEP_SQRT_AT_MODEL 3
+#define MDX_STEP_SQRT_ONE_MINUS_AT_MODEL 4
+#define MDX_STEP_C0 5
+#define MDX_STEP_SQRT_AT 9
+#define MDX_STEP_SQRT_ONE_MINUS_AT 10
+#define MDX_STEP_SQRT_A_PREV 11
+#define MDX_STEP_DIR_COEF 12
+#define MDX_STEP_SIGMA 13
+int mdx_sampler_step_table_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                               int pred_type, const float* old1, const float* old2, const float* old3,
+                               const float* noise, float* e_t_out, float* x_prev, float* pred_x0, const float* table,
+                               int any_rescale, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

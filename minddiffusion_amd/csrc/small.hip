@@ -162,6 +162,28 @@ struct StepParams {
 // the PLMS first step writes the latent its model output was computed on).  The outputs may alias no other input, so what
 // matters is that x_model[i] is read before the first store for i and x[i] before x_prev[i] is stored -- both hold below.
 // MDX_PRED_EPS compiles to exactly the statements mdx_sampler_step_f32 has always launched.
+// sampler_step_element is the update of ONE element, the body of sampler_step_kernel and of sampler_step_table_kernel.
+template <int PRED>
+__device__ __forceinline__ void sampler_step_element(const StepParams& p, size_t i, size_t ei) {
+    float e_t = (float)p.eps_c[ei];
+    if (p.eps_u) {
+        const float eu = (float)p.eps_u[ei];
+        e_t = eu + p.cfg_scale * (e_t - eu);
+    }
+    if constexpr (PRED == MDX_PRED_V) e_t = p.am * e_t + p.bm * p.x_model[i];   // eps = a v + b x_m (dpm_solver.py:281-284)
+    if (p.e_t_out) p.e_t_out[i] = e_t;
+    float ep = p.c0 * e_t;
+    if (p.old1) ep += p.c1 * p.old1[i];
+    if (p.old2) ep += p.c2 * p.old2[i];
+    if (p.old3) ep += p.c3 * p.old3[i];
+    const float xv = p.x[i];
+    const float px0 = (xv - p.sqrt_one_minus_at * ep) / p.sqrt_at;
+    float xp = p.sqrt_a_prev * px0 + p.dir_coef * ep;
+    if (p.noise) xp += p.sigma * p.noise[i];
+    if (p.pred_x0) p.pred_x0[i] = px0;
+    p.x_prev[i] = xp;
+}
+
 template <int PRED>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
     mdx_kernarg_touch<sizeof(StepParams)>();
@@ -171,24 +193,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
         const size_t bc = i / p.HW;
         const int c = (int)(bc % p.C);
         const int b = (int)(bc / p.C);
-        const size_t ei = ((size_t)b * p.HW + pix) * p.eps_ld + c;
-        float e_t = (float)p.eps_c[ei];
-        if (p.eps_u) {
-            const float eu = (float)p.eps_u[ei];
-            e_t = eu + p.cfg_scale * (e_t - eu);
-        }
-        if constexpr (PRED == MDX_PRED_V) e_t = p.am * e_t + p.bm * p.x_model[i];   // eps = a v + b x_m (dpm_solver.py:281-284)
-        if (p.e_t_out) p.e_t_out[i] = e_t;
-        float ep = p.c0 * e_t;
-        if (p.old1) ep += p.c1 * p.old1[i];
-        if (p.old2) ep += p.c2 * p.old2[i];
-        if (p.old3) ep += p.c3 * p.old3[i];
-        const float xv = p.x[i];
-        const float px0 = (xv - p.sqrt_one_minus_at * ep) / p.sqrt_at;
-        float xp = p.sqrt_a_prev * px0 + p.dir_coef * ep;
-        if (p.noise) xp += p.sigma * p.noise[i];
-        if (p.pred_x0) p.pred_x0[i] = px0;
-        p.x_prev[i] = xp;
+        sampler_step_element<PRED>(p, i, ((size_t)b * p.HW + pix) * p.eps_ld + c);
     }
 }
 
@@ -207,12 +212,9 @@ constexpr int RESCALE_THREADS = 1024;
 
 // Sums are taken of d = v - K with K = the mean of the sample's first 64 values (the same bits in every wave), so that
 // sum(d^2) - sum(d)^2 / N cancels nothing to speak of when the outputs sit on an offset far above their spread.
-template <int PRED>
-__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(const RescaleParams rp) {
-    mdx_kernarg_touch<sizeof(RescaleParams)>();
-    const StepParams& p = rp.s;
-    __shared__ float part[RESCALE_THREADS / 64][4];
-    const int b = blockIdx.x;
+// The two passes are device functions of (parameters, sample): sampler_step_rescale_kernel runs them on its kernel arguments,
+// sampler_step_table_kernel on the parameters of the sample's table row.
+__device__ __forceinline__ float rescale_factor(const StepParams& p, float phi, int b, float (*part)[4]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned N = (unsigned)p.C * (unsigned)p.HW;      // per sample: the host refuses what does not fit 31 bits
     const unsigned C = p.C, HW = p.HW;
@@ -262,9 +264,16 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(c
     const float std_c = sqrtf(fmaxf(scc - sc * sc / n, 0.f) / (n - 1.f));
     const float std_m = sqrtf(fmaxf(smm - sm * sm / n, 0.f) / (n - 1.f));
     float f = 1.f;
-    if (std_m > 0.f && std_m <= 3.402823466e38f) f = rp.phi * std_c / std_m + (1.f - rp.phi);   // NaN fails both tests
-    if (rp.factor_out && threadIdx.x == 0) rp.factor_out[b] = f;
+    if (std_m > 0.f && std_m <= 3.402823466e38f) f = phi * std_c / std_m + (1.f - phi);   // NaN fails both tests
+    return f;
+}
 
+template <int PRED>
+__device__ __forceinline__ void rescale_apply(const StepParams& p, float f, int b) {
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW;
+    const unsigned HW = p.HW;
+    const f16* ou = p.eps_u + (size_t)b * HW * p.eps_ld;
+    const f16* oc = p.eps_c + (size_t)b * HW * p.eps_ld;
     // ---- pass 2: the step (sampler_step_kernel's statements on m' = f m), U elements of a thread at a time: all their
     // loads first, then the arithmetic and the stores.  The outputs may alias x / x_model only element for element, so a
     // thread that has read its own U elements may store them; without the batching every trip of the loop waits out one
@@ -318,6 +327,104 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(c
             }
         }
     }
+}
+
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(const RescaleParams rp) {
+    mdx_kernarg_touch<sizeof(RescaleParams)>();
+    const StepParams& p = rp.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    const int b = blockIdx.x;
+    const float f = rescale_factor(p, rp.phi, b, part);
+    if (rp.factor_out && threadIdx.x == 0) rp.factor_out[b] = f;
+    rescale_apply<PRED>(p, f, b);
+}
+
+// ------------------------------------------------------------------ fused sampler update, per-sample scalars from a table
+// Every scalar the three kernels above take as a kernel argument comes from row b of a device table (MDX_STEP_* of mdx.h),
+// so samples with different guidance scales, rescale strengths and schedules share one launch.  A workgroup works on ONE
+// sample: its row is the same address in every lane.  table_row fills the StepParams of that sample, with the pointers the
+// scalar entries' host code would have kept (a term whose coefficient is exactly 0 is skipped, not multiplied: what it
+// points to may be NaN); the kernels then run the very bodies of the scalar kernels on them.
+struct TableParams {
+    StepParams s;
+    const float* table;
+    float* factor_out;
+};
+
+__device__ __forceinline__ bool table_row(StepParams& p, const float* table, int b, float& phi) {
+    const float* row = table + (size_t)b * MDX_STEP_ROW;
+    if (row[MDX_STEP_ACTIVE] == 0.f) return false;
+    p.cfg_scale = row[MDX_STEP_CFG_SCALE];
+    phi = row[MDX_STEP_RESCALE];
+    p.am = row[MDX_STEP_SQRT_AT_MODEL];
+    p.bm = row[MDX_STEP_SQRT_ONE_MINUS_AT_MODEL];
+    p.c0 = row[MDX_STEP_C0];
+    p.c1 = row[MDX_STEP_C0 + 1];
+    p.c2 = row[MDX_STEP_C0 + 2];
+    p.c3 = row[MDX_STEP_C0 + 3];
+    p.sqrt_at = row[MDX_STEP_SQRT_AT];
+    p.sqrt_one_minus_at = row[MDX_STEP_SQRT_ONE_MINUS_AT];
+    p.sqrt_a_prev = row[MDX_STEP_SQRT_A_PREV];
+    p.dir_coef = row[MDX_STEP_DIR_COEF];
+    p.sigma = row[MDX_STEP_SIGMA];
+    if (p.c1 == 0.f) p.old1 = nullptr;
+    if (p.c2 == 0.f) p.old2 = nullptr;
+    if (p.c3 == 0.f) p.old3 = nullptr;
+    if (p.sigma == 0.f) p.noise = nullptr;
+    return true;
+}
+
+// An inactive row (a request whose schedule has ended): the latent travels to the other buffer, nothing else is written.
+__device__ __forceinline__ void table_copy_row(const StepParams& p, int b, unsigned first, unsigned stride) {
+    if (p.x_prev == p.x) return;
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW;
+    const size_t base = (size_t)b * N;
+    for (unsigned j = first + threadIdx.x; j < N; j += stride) p.x_prev[base + j] = p.x[base + j];
+}
+
+// No row rescales: gridDim.x workgroups share sample blockIdx.y, sampler_step_kernel's statements per element.
+template <int PRED>
+__global__ __launch_bounds__(256) void sampler_step_table_kernel(const TableParams tp) {
+    mdx_kernarg_touch<sizeof(TableParams)>();
+    StepParams p = tp.s;
+    const int b = blockIdx.y;
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW, HW = p.HW;      // the host refuses what does not fit 31 bits
+    const unsigned first = blockIdx.x * 256u, stride = gridDim.x * 256u;
+    float phi;
+    if (!table_row(p, tp.table, b, phi)) {
+        table_copy_row(p, b, first, stride);
+        return;
+    }
+    if (tp.factor_out && blockIdx.x == 0 && threadIdx.x == 0) tp.factor_out[b] = 1.f;
+    const size_t base = (size_t)b * N;
+    for (unsigned j = first + threadIdx.x; j < N; j += stride) {
+        const unsigned c = j / HW;
+        sampler_step_element<PRED>(p, base + j, ((size_t)b * HW + (j - c * HW)) * p.eps_ld + c);
+    }
+}
+
+// Some row rescales: a workgroup owns a sample, as in sampler_step_rescale_kernel; a row with phi == 0 reads no statistics
+// and runs pass 2 with f = 1, which is sampler_step_kernel's result to the bit.  That equality is NOT by construction:
+// rescale_apply spells out by hand (__builtin_fmaf, fp contract(off)) the contraction the compiler currently chooses for
+// sampler_step_element, so it is coupled to the compiler's choices.  tests/test_step_table_gpu.py (phi == 0 rows of a mixed
+// launch against the plain entry) and test_constant_outputs_give_factor_one hold it on hardware; if a toolchain update makes
+// them fail, respell rescale_apply -- do not loosen the tests.
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_table_rescale_kernel(const TableParams tp) {
+    mdx_kernarg_touch<sizeof(TableParams)>();
+    StepParams p = tp.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    const int b = blockIdx.x;
+    float phi;
+    if (!table_row(p, tp.table, b, phi)) {
+        table_copy_row(p, b, 0u, (unsigned)RESCALE_THREADS);
+        return;
+    }
+    float f = 1.f;
+    if (phi != 0.f) f = rescale_factor(p, phi, b, part);      // the row is the workgroup's: every thread takes the same side
+    if (tp.factor_out && threadIdx.x == 0) tp.factor_out[b] = f;
+    rescale_apply<PRED>(p, f, b);
 }
 
 // ------------------------------------------------------------------ MFMA layout probe
@@ -518,6 +625,48 @@ extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model
         hipLaunchKernelGGL(sampler_step_rescale_kernel<MDX_PRED_V>, dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, rp);
     else
         hipLaunchKernelGGL(sampler_step_rescale_kernel<MDX_PRED_EPS>, dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, rp);
+    MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
+}
+
+extern "C" int mdx_sampler_step_table_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
+                                          int out_ld, int pred_type, const float* old1, const float* old2,
+                                          const float* old3, const float* noise, float* e_t_out, float* x_prev,
+                                          float* pred_x0, const float* table, int any_rescale, float* factor_out, int B,
+                                          int C, int H, int W, mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_table_f32";
+    TableParams tp;
+    // the coefficients live on the device: the pointer and extent checks of the scalar entries, on coefficients that need none
+    const float no_history[4] = {1.f, 0.f, 0.f, 0.f};
+    const int rc = sampler_step_params(tp.s, fn, x, x_model, out_u, out_c, out_ld, 1.f, pred_type, 1.f, 0.f, old1, old2, old3,
+                                       no_history, 1.f, 0.f, 1.f, 0.f, 0.f, noise, e_t_out, x_prev, pred_x0, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(table, "%s: null table", fn);
+    MDX_REQUIRE(!any_rescale || out_u, "%s: any_rescale needs the unconditional output out_u", fn);
+    MDX_REQUIRE(!any_rescale || (size_t)C * H * W >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
+    MDX_REQUIRE((size_t)C * H * W <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
+    MDX_REQUIRE(any_rescale || B <= 65535, "%s: bad extents (B exceeds 65535 samples)", fn);
+    tp.s.old1 = old1;      // table_row keeps or drops them by the row's coefficient
+    tp.s.old2 = old2;
+    tp.s.old3 = old3;
+    tp.s.noise = noise;
+    tp.table = table;
+    tp.factor_out = factor_out;
+    const hipStream_t st = (hipStream_t)s;
+    if (any_rescale) {
+        if (pred_type == MDX_PRED_V)
+            hipLaunchKernelGGL(sampler_step_table_rescale_kernel<MDX_PRED_V>, dim3(B), dim3(RESCALE_THREADS), 0, st, tp);
+        else
+            hipLaunchKernelGGL(sampler_step_table_rescale_kernel<MDX_PRED_EPS>, dim3(B), dim3(RESCALE_THREADS), 0, st, tp);
+    } else {
+        // the workgroups of sampler_step_kernel's grid for the same batch, dealt to the samples
+        const int per_sample = (grid_for((size_t)B * C * H * W) + B - 1) / B;
+        const dim3 grid(per_sample, B);
+        if (pred_type == MDX_PRED_V)
+            hipLaunchKernelGGL(sampler_step_table_kernel<MDX_PRED_V>, grid, dim3(256), 0, st, tp);
+        else
+            hipLaunchKernelGGL(sampler_step_table_kernel<MDX_PRED_EPS>, grid, dim3(256), 0, st, tp);
+    }
     MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
 }

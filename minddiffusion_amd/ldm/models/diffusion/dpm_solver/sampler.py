@@ -26,7 +26,8 @@ import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..guided import GuidedModel, split_conditioning, start_latent
+from ..guided import (GuidedModel, StepTable, dpm_model_point, dpm_step_scalars, per_request, split_conditioning,
+                      start_latent)
 from ..plms import check_guidance_rescale, check_seed_sources, check_seeds, noised_latent
 from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
 
@@ -68,8 +69,24 @@ class DPMSolverSampler:
         x_T = stochastic_encode(., t_start) (the reference's DPM_Solver.sample(t_start=), dpm_solver.py:958-1075).  S == 1 is a
         single first-order update.
         seeds: `batch_size` ints, one per sample -- x_T (the only draw of this sampler) of sample b then depends on seeds[b]
-        alone (ops.randn_seeded); None: the sampler's generator."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        alone (ops.randn_seeded); None: the sampler's generator.
+        Per request: S, unconditional_guidance_scale and guidance_rescale each take a scalar or `batch_size` values; with any
+        sequence every step is one ops.sampler_step_table launch on the rows of a StepTable built and uploaded before the
+        loop.  Sample b runs its own multistep_2m_plan of S[b] steps -- its order and its lower-order final step included -- on
+        loop iterations 0 .. S[b] - 1 and is carried along unchanged afterwards; the loop runs max(S) iterations, callbacks
+        fire once per iteration, and in the data prediction handed to img_callback a finished sample holds its last value.  The
+        guidance batch is used if any scale differs from 1; a sample whose scale is exactly 1.0 then goes through the
+        combine eu + 1 * (ec - eu) and is not promised bit-equal to an unguided run.  Refused: an S list whose values DIFFER with
+        t_start (a list that repeats one value is one grid and passes); any sequence with score_corrector or quantize_x0."""
+        per = per_request(S, unconditional_guidance_scale, guidance_rescale, batch_size)
+        if per is None:
+            guidance_rescale = check_guidance_rescale(guidance_rescale)
+        else:
+            if score_corrector is not None or quantize_x0:
+                raise ValueError("per-sample guidance scale / rescale / steps run inside the fused step launch: not with "
+                                 "score_corrector or quantize_x0")
+            if len(set(per[0])) > 1 and t_start is not None:
+                raise ValueError("per-sample S with different values runs every sample's own full schedule: not with t_start")
         check_seed_sources(seeds, self.generator)
         if t_start is not None:
             t_start = self._check_t_start(t_start)
@@ -84,9 +101,11 @@ class DPMSolverSampler:
             print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
         size = (batch_size,) + tuple(shape)
         img = start_latent(x_T, check_seeds(seeds, batch_size, dev), size, dev, self.generator)
-        scale = float(unconditional_guidance_scale)
-
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
+        if per is not None:
+            return self._sample_per_request(ns, per, img, batch_size, shape, cond, uc, c_cat, uc_cat, dev, t_start, callback,
+                                            img_callback)
+        scale = float(unconditional_guidance_scale)
         plan = multistep_2m_plan(ns, S, order=2 if S >= 2 else 1, lower_order_final=True, t_start=t_start)
         # (S fractional timesteps; model_wrapper :316-322 builds the [uncond; cond] batch)
         guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
@@ -95,14 +114,55 @@ class DPMSolverSampler:
         x_next = torch.empty_like(img)
         # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, in the step launch
         pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
-        f = np.float32
         for k, p in enumerate(plan):
             eps_u, eps_c = guided(img, k)
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
-            update = (f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]),
-                      f(p["c1"]), prev if p["c1"] != 0.0 else None, None, x_next, cur)
+            update = dpm_step_scalars(p) + (prev if p["c1"] != 0.0 else None, None, x_next, cur)
             ops.sampler_update(img, eps_u, eps_c, scale, pred_type, [], (1., 0., 0., 0.), update, guidance_rescale, None,
-                               f(p["alpha"]), f(p["sigma"]))
+                               *dpm_model_point(p))
+            img, x_next = x_next, img
+            if callback:
+                callback(k)
+            if img_callback:
+                img_callback(cur, k)
+        return img, None
+
+    @staticmethod
+    def _step_table(ns, steps, scales, rescales, guided, t_start=None):
+        """(StepTable, model-input timesteps [n_calls, B], loop iterations) of a per-request run: sample b's rows are the
+        scalars of its own S[b]-step plan on iterations 0 .. S[b] - 1, inactive afterwards."""
+        by_steps = {s: multistep_2m_plan(ns, s, order=2 if s >= 2 else 1, lower_order_final=True, t_start=t_start)
+                    for s in sorted(set(steps))}
+        plans = [by_steps[s] for s in steps]
+        total = max(steps)
+        table = StepTable(scales, rescales, guided)
+        for k in range(total):
+            table.append([(dpm_model_point(pl[k]), (1., 0., 0., 0.), dpm_step_scalars(pl[k])) if k < len(pl) else None
+                          for pl in plans])
+        t_rows = [[pl[min(k, len(pl) - 1)]["t_input"] for pl in plans] for k in range(total)]      # ended: its last timestep
+        return table, np.array(t_rows, dtype=np.float32), total
+
+    def _sample_per_request(self, ns, per, img, batch_size, shape, cond, uc, c_cat, uc_cat, dev, t_start, callback,
+                            img_callback):
+        """sample() with per-sample S / scale / rescale (`per`, checked): the same loop on a StepTable.  Sample b's rows are
+        the scalars of its own plan (one multistep_2m_plan per distinct S); its previous data prediction is read only while
+        its row's c1 is non-zero, so a sample on its first-order final step ignores the pointer that is live for the others.
+        The data predictions ping-pong between two buffers and the launch writes only active rows, so on the iteration a
+        sample ends its last prediction is copied into the other buffer too: from then on both hold it, and whichever one
+        img_callback is handed shows the finished sample's last value."""
+        table, t_rows, total = self._step_table(ns, *per, not (uc is None and uc_cat is None), t_start)
+        ending = {k: [b for b, s in enumerate(per[0]) if s - 1 == k] for k in range(total - 1)}
+        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, per[1], dev, t_rows)
+        table.upload(dev)
+        x0_bufs = [torch.empty_like(img), torch.empty_like(img)]
+        x_next = torch.empty_like(img)
+        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
+        for k in range(total):
+            eps_u, eps_c = guided(img, k)
+            cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
+            table.launch(k, img, eps_u, eps_c, pred_type, [], prev if table.any_sigma[k] else None, None, x_next, cur)
+            for b in ending.get(k, ()):
+                prev[b].copy_(cur[b])
             img, x_next = x_next, img
             if callback:
                 callback(k)

@@ -19,14 +19,20 @@ of the schedule through the same loop; the per-step mask blend of that path is o
 Per-sample seeds (not in the reference): with ``seeds=`` every draw -- x_T, the eta > 0 step noise, the mask blend, the
 stochastic_encode noise -- is one mdx_randn_f32 launch keyed by the sample's own seed (ops.randn_seeded), so a sample does not
 depend on the batch it is served in; without it the sampler's generator draws for the whole batch, as before.
+Per-request parameters (not in the reference): S, unconditional_guidance_scale and guidance_rescale given as one value per
+sample -- every step is then ONE mdx_sampler_step_table_f32 launch that reads each sample's scalars from its row of a table
+built and uploaded once before the loop (guided.StepTable); scalars keep the three entries above.
 """
+import itertools
+
 import numpy as np
 import torch
 
 from .... import ops
 from ...._lib import MdxError
 from ...modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps
-from .guided import GuidedModel, _first_tensor, split_conditioning, start_latent
+from .guided import (PLMS_AB, PLMS_FIRST, PLMS_SECOND, GuidedModel, StepTable, _first_tensor, ddim_step_scalars, per_request,
+                     split_conditioning, start_latent)
 
 
 def check_guidance_rescale(value):
@@ -163,13 +169,38 @@ class _SamplerBase:
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., seeds=None, **kwargs):
         """seeds: `batch_size` ints, one per sample -- every draw of sample b (x_T, the eta > 0 step noise, the mask blend)
-        then depends on seeds[b] alone and not on the batch around it (ops.randn_seeded); None: the sampler's generator."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        then depends on seeds[b] alone and not on the batch around it (ops.randn_seeded); None: the sampler's generator.
+        Per request: S, unconditional_guidance_scale and guidance_rescale each take a scalar or `batch_size` values (list,
+        tuple, 1-d array or tensor).  With any sequence the run reads its step scalars from a StepTable (one
+        ops.sampler_step_table launch per model evaluation).  Sample b runs its own complete S[b]-step schedule on loop
+        iterations 0 .. S[b] - 1 and is carried along unchanged afterwards; the loop runs max(S) iterations, callbacks and
+        intermediates fire once per iteration, and a finished sample's pred_x0 holds its last value.  The guidance batch is
+        used if any scale differs from 1; a sample whose scale is exactly 1.0 then goes through the combine
+        eu + 1 * (ec - eu) and is not promised bit-equal to an unguided run.  eta, temperature and noise_dropout stay
+        scalars.  Refused: an S list whose values DIFFER with mask / x0, timesteps= or ddim_use_original_steps (a list that
+        repeats one value is one grid and passes); any sequence with score_corrector or quantize_x0 (they leave the fused
+        launch)."""
+        per = per_request(S, unconditional_guidance_scale, guidance_rescale, batch_size)
+        if per is None:
+            guidance_rescale = check_guidance_rescale(guidance_rescale)
         if conditioning is not None:
             cbs = _first_tensor(conditioning).shape[0]
             if cbs != batch_size:
                 print(f"Warning: Got {cbs} conditionings but batch-size is {batch_size}")
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        grids = None
+        if per is not None and len(set(per[0])) > 1:
+            if mask is not None or x0 is not None or kwargs.get("timesteps") is not None or kwargs.get("ddim_use_original_steps"):
+                raise ValueError("per-sample S with different values runs every sample's own full schedule: not with "
+                                 "mask / x0, timesteps= or ddim_use_original_steps")
+            by_steps = {}
+            for s_b in sorted(set(per[0])):                          # ends on max(S): the schedule the sampler keeps
+                self.make_schedule(ddim_num_steps=s_b, ddim_eta=eta, verbose=verbose)
+                by_steps[s_b] = self._time_grid(False, None, None)
+            grids = [by_steps[s_b] for s_b in per[0]]
+        else:
+            self.make_schedule(ddim_num_steps=S if per is None else per[0][0], ddim_eta=eta, verbose=verbose)
+        if per is not None:
+            unconditional_guidance_scale, guidance_rescale = per[1], per[2]
         C, H, W = shape
         size = (batch_size, C, H, W)
         if verbose:
@@ -186,7 +217,8 @@ class _SamplerBase:
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale, seeds=seeds)
+                                  blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale, seeds=seeds,
+                                  grids=grids)
 
     # ---- img2img: upstream LDM's DDIMSampler.stochastic_encode / decode (neither reference tree has them).
     # t_enc / t_start count the model evaluations that REMAIN (1 .. S; PLMS spends one more on its first step): the partial run
@@ -280,18 +312,57 @@ class _SamplerBase:
         if not 0. <= float(noise_dropout) < 1.:
             raise ValueError("noise_dropout must be in [0, 1)")
 
+    def _step_table(self, grids, scales, rescales, guided):
+        """(StepTable, model-input timesteps [n_calls, B], loop iterations) of a per-request run: grids[b] is sample b's own
+        _time_grid(), of S[b] steps.  Sample b is active on iterations 0 .. S[b] - 1, at grid index S[b] - 1 - i; the launches
+        are the scalar loop's, in its order: for PLMS the two of the pseudo improved Euler step on iteration 0 (the second
+        evaluates the model at each sample's own min(1, S[b] - 1); its timesteps are the LAST row), then AB-2 / 3 / 4."""
+        n = [int(g[0].shape[0]) for g in grids]
+        total = max(n)
+        table = StepTable(scales, rescales, guided)
+
+        def rows(i, coef, i_model=None):
+            out = []
+            for (time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas), n_b in zip(grids, n):
+                if i >= n_b:
+                    out.append(None)
+                    continue
+                tm = int(time_range[i if i_model is None else min(i_model, n_b - 1)])
+                out.append(((self.sqrt_alphas_cumprod[tm], self.sqrt_one_minus_alphas_cumprod[tm]), coef,
+                            ddim_step_scalars(alphas, alphas_prev, sqrt_one_minus_alphas, sigmas, n_b - i - 1)))
+            return out
+
+        t_rows = [[g[0][min(i, n_b - 1)] for g, n_b in zip(grids, n)] for i in range(total)]    # ended: its last timestep
+        for i in range(total):
+            if self.multistep and i == 0:
+                table.append(rows(0, PLMS_FIRST))
+                table.append(rows(0, PLMS_SECOND, 1))
+            else:
+                table.append(rows(i, PLMS_AB[min(i, 3)] if self.multistep else PLMS_AB[0]))
+        if self.multistep:
+            t_rows.append([g[0][min(1, n_b - 1)] for g, n_b in zip(grids, n)])
+        return table, np.array(t_rows, dtype=np.float32), total
+
     # ---- plms.py:124-179 + 182-247
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None):
+                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None, grids=None):
         """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
         t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
         mask / x0 blend of every step is one ops.q_sample launch, in place.
+        unconditional_guidance_scale / guidance_rescale: a scalar, or one value per sample -- then every step is one
+        ops.sampler_step_table launch on the rows of a StepTable built and uploaded before the loop (sample()).
+        grids (sample() passes it, nothing else does): one _time_grid() per sample, each sample its own step count.
         In order: validate, normalise the conditioning and draw the start latent, select the time grid, build the guided model
         call, loop."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        per = per_request(None, unconditional_guidance_scale, guidance_rescale, shape[0])
+        if per is None:
+            guidance_rescale = check_guidance_rescale(guidance_rescale)
+        elif score_corrector is not None or quantize_denoised:
+            raise ValueError("per-sample guidance scale / rescale / steps run inside the fused step launch: not with "
+                             "score_corrector or quantize_x0")
         check_seed_sources(seeds, self.generator, step_noises=step_noises, blend_noises=blend_noises, dropout_masks=dropout_masks)
         self._check_options(mask, x0, score_corrector, quantize_denoised, noise_dropout)
         corrector_kwargs = corrector_kwargs or {}
@@ -305,7 +376,7 @@ class _SamplerBase:
         total_steps = int(time_range.shape[0])
         if verbose:
             print(f"Running {type(self).__name__} Sampling with {total_steps} timesteps")
-        scale = float(unconditional_guidance_scale)
+        scale = float(unconditional_guidance_scale) if per is None else per[1]
         if mask is not None:
             mask = torch.as_tensor(mask).to(device=dev, dtype=torch.float32)
             x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32)
@@ -314,7 +385,16 @@ class _SamplerBase:
                 if mask.dim() != 4 or mask.shape[1] not in (1, shape[1]):
                     raise MdxError(f"mask must be [B, 1, H, W] or [B, C, H, W], got {tuple(mask.shape)}")
                 mask = mask.expand((b, mask.shape[1]) + tuple(shape[2:])).contiguous()
-        guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, time_range)
+        table, table_calls = None, itertools.count()
+        if per is not None:
+            # every scalar of every launch, from each sample's own grid, and the model-input timesteps [n_calls, B]
+            table, t_rows, total_steps = self._step_table(grids or [(time_range, alphas, alphas_prev, sqrt_one_minus_alphas,
+                                                                     sigmas)] * b, per[1], per[2],
+                                                          not (uc is None and uc_cat is None))
+            guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
+            table.upload(dev)
+        else:
+            guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, time_range)
         draws = _Draws(seeds, self.generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout)
 
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
@@ -334,9 +414,15 @@ class _SamplerBase:
         def step(x, eps_u, eps_c, index, coef, olds, e_out, x_out, p_out, xm=None, tm=None):
             """One get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] * olds[k-1], e_t = the
             CFG-combined model output (optionally written to e_out).  xm / tm: the image and timestep the model output
-            was evaluated at (what a score corrector is handed, plms.py:201, and where a v output is converted to eps)."""
-            a_t, a_prev = np.float32(alphas[index]), np.float32(alphas_prev[index])
-            sigma_t = np.float32(sigmas[index])
+            was evaluated at (what a score corrector is handed, plms.py:201, and where a v output is converted to eps).
+            Per request all of these scalars are the StepTable's: the launches take its slices in the order they were built."""
+            if table is not None:
+                k = next(table_calls)
+                table.launch(k, x, eps_u, eps_c, pred_type, olds, draws.step() if table.any_sigma[k] else None, e_out,
+                             x_out, p_out, xm)
+                return
+            s_at, s_1mat, s_aprev, dir_coef, sigma_t = ddim_step_scalars(alphas, alphas_prev, sqrt_one_minus_alphas, sigmas,
+                                                                          index)
             if score_corrector is not None:
                 # e_t leaves the fused kernel (pass 1: CFG combine only -- the rescale belongs to the combine that produces
                 # e_t, so to this pass), goes through the caller's modify_score, and re-enters as a single NHWC fp16 model
@@ -355,17 +441,18 @@ class _SamplerBase:
             noise = draws.step() if float(sigma_t) != 0.0 else None
             if quantize_denoised and p_out is None:
                 p_out = hook_p
-            update = (np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
-                      np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t, noise, e_out, x_out, p_out)
+            update = (s_at, s_1mat, s_aprev, dir_coef, sigma_t, noise, e_out, x_out, p_out)
             ops.sampler_update(x, eps_u, eps_c, scale, pred_type, olds, coef, update, guidance_rescale, xm,
                                self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)])
             if quantize_denoised:
                 # pred_x0, _, *_ = first_stage_model.quantize(pred_x0) (plms.py:218-219); x_prev is linear in pred_x0
                 q = self.model.first_stage_model.quantize(p_out)[0]
                 q = torch.as_tensor(q).to(device=dev, dtype=torch.float32)
-                x_out.add_((q - p_out) * float(np.sqrt(a_prev)))
+                x_out.add_((q - p_out) * float(s_aprev))
                 p_out.copy_(q)
 
+        # (per request with step counts that differ, time_range is the longest grid -- sample() made that schedule last -- and
+        # index / step_t of a sample are its own: the table's, and t_rows')
         for i, step_t in enumerate(time_range):
             index = total_steps - i - 1
             if mask is not None:
@@ -379,25 +466,22 @@ class _SamplerBase:
                     img = img_orig * mask + (1. - mask) * img
             eps_u, eps_c = guided(img, i)
             if not self.multistep:
-                step(img, eps_u, eps_c, index, (1., 0., 0., 0.), [], None, x_next, pred_x0, tm=step_t)
+                step(img, eps_u, eps_c, index, PLMS_AB[0], [], None, x_next, pred_x0, tm=step_t)
             else:
                 e_buf = pool.pop()
                 n_old = len(hist)
                 if n_old == 0:
                     # Pseudo Improved Euler (2nd order), plms.py:231-235: S+1 UNet calls in total
-                    step(img, eps_u, eps_c, index, (1., 0., 0., 0.), [], e_buf, x_next, None, tm=step_t)
+                    step(img, eps_u, eps_c, index, PLMS_FIRST, [], e_buf, x_next, None, tm=step_t)
                     i_next = min(i + 1, total_steps - 1)
-                    eps_u2, eps_c2 = guided(x_next, i_next)
-                    step(img, eps_u2, eps_c2, index, (.5, .5, 0., 0.), [e_buf], None, x_next, pred_x0,
+                    # which row of the guided model's timesteps the second evaluation reads: step i_next's -- per request the
+                    # row _step_table appended after the loop's, each sample's own min(1, S[b] - 1)
+                    second_row = i_next if table is None else total_steps
+                    eps_u2, eps_c2 = guided(x_next, second_row)
+                    step(img, eps_u2, eps_c2, index, PLMS_SECOND, [e_buf], None, x_next, pred_x0,
                          xm=x_next, tm=time_range[i_next])
-                elif n_old == 1:  # Adams-Bashforth 2, plms.py:236-238
-                    step(img, eps_u, eps_c, index, (3. / 2, -1. / 2, 0., 0.), hist[:1], e_buf, x_next, pred_x0, tm=step_t)
-                elif n_old == 2:  # AB-3, plms.py:239-241
-                    step(img, eps_u, eps_c, index, (23. / 12, -16. / 12, 5. / 12, 0.), hist[:2], e_buf, x_next,
-                         pred_x0, tm=step_t)
-                else:             # AB-4, plms.py:242-244
-                    step(img, eps_u, eps_c, index, (55. / 24, -59. / 24, 37. / 24, -9. / 24), hist[:3], e_buf,
-                         x_next, pred_x0, tm=step_t)
+                else:             # Adams-Bashforth 2 / 3 / 4, plms.py:236-244
+                    step(img, eps_u, eps_c, index, PLMS_AB[n_old], hist[:n_old], e_buf, x_next, pred_x0, tm=step_t)
                 hist.insert(0, e_buf)
                 if len(hist) > 3:
                     pool.append(hist.pop())

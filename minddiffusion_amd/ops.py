@@ -807,6 +807,32 @@ def sampler_update(x, out_u, out_c, cfg_scale, pred_type, olds, coef, update, gu
         sampler_step(x, out_u, out_c, out_c.shape[-1], cfg_scale, olds, coef, *update)
 
 
+STEP_ROW = 16               # MDX_STEP_* of include/mdx.h: the floats of one sample's row, and where each scalar sits in it
+(STEP_ACTIVE, STEP_CFG_SCALE, STEP_RESCALE, STEP_SQRT_AT_MODEL, STEP_SQRT_ONE_MINUS_AT_MODEL, STEP_C0) = range(6)
+(STEP_SQRT_AT, STEP_SQRT_ONE_MINUS_AT, STEP_SQRT_A_PREV, STEP_DIR_COEF, STEP_SIGMA) = range(9, 14)
+
+
+def sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0, table, any_rescale,
+                       factor_out=None):
+    """The fused step with every per-sample scalar read from row b of `table` ([B, STEP_ROW] fp32 on the device, a slice of
+    a larger tensor is fine): samples of one batch with their own guidance scale, guidance rescale and schedule point, an
+    inactive row just carried over to x_prev (see include/mdx.h).  any_rescale: whether some active row has a non-zero
+    guidance rescale.  The table's values are the builder's to check (StepTable); nothing here syncs."""
+    B, C, H, W = x.shape
+    _chk(table, f32, "table")
+    if tuple(table.shape) != (B, STEP_ROW):
+        raise _lib.MdxError(f"table: expected [{B}, {STEP_ROW}], got {tuple(table.shape)}")
+    o = list(olds) + [None] * (3 - len(olds))
+    if factor_out is not None:
+        _chk(factor_out, f32, "factor_out")
+        if factor_out.numel() < B:
+            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    _lib.check(_lib.load().mdx_sampler_step_table_f32(
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), _ptr(o[0]), _ptr(o[1]),
+        _ptr(o[2]), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(table), int(bool(any_rescale)),
+        _ptr(factor_out), B, C, H, W, _stream()), "mdx_sampler_step_table_f32")
+
+
 def probe_mfma(a, b):
     c = torch.empty((64, 16), dtype=f32, device=a.device)
     _lib.check(_lib.load().mdx_probe_mfma_32x32x16_f16(_ptr(a), _ptr(b), _ptr(c), _stream()), "mdx_probe_mfma")

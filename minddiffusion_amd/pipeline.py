@@ -18,6 +18,7 @@ from . import distributed as D
 from . import ops
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
+from .ldm.models.diffusion.guided import as_sequence, per_request
 from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
 from .ldm.modules.encoders import WINDOW, pad_conditioning
 
@@ -122,6 +123,27 @@ class DiffusionPipeline:
         return kw
 
     @staticmethod
+    def check_request_lists(what, batch, steps, scale, guidance_rescale, steps_list=True):
+        """`steps`, `scale` and `guidance_rescale` of a call, each one value or one per sample of the batch (the samplers'
+        per-request form, guided.per_request): the checked guidance_rescale.  batch None: the lengths are the sampler's to
+        check.  steps_list False: a partial run -- `strength` fixes one grid for the whole batch -- takes one step count.
+        Any list needs a single rank."""
+        seq = {k: as_sequence(v) is not None for k, v in (("steps", steps), ("scale", scale),
+                                                            ("guidance_rescale", guidance_rescale))}
+        if not any(seq.values()):
+            return check_guidance_rescale(guidance_rescale)
+        if seq["steps"] and not steps_list:
+            raise ValueError(f"{what}: `strength` fixes one grid for the whole batch: steps must be one int, not one per sample")
+        if D.world()[1] > 1:
+            raise MdxError(f"{what}: per-sample steps / scale / guidance_rescale runs on a single rank (the sharded form is "
+                           f"not built)")
+        if batch is None:
+            batch = max(len(as_sequence(v)) for k, v in (("steps", steps), ("scale", scale),
+                                                          ("guidance_rescale", guidance_rescale)) if seq[k])
+        per_request(steps, scale, guidance_rescale, batch)
+        return guidance_rescale
+
+    @staticmethod
     def _check_strength(what, strength, steps):
         """t_enc = int(strength * steps), the steps of the `steps`-step schedule that remain to run."""
         if not 0.0 < float(strength) <= 1.0:
@@ -165,8 +187,11 @@ class DiffusionPipeline:
         seeds: one int per sample of the global batch, every rank the same list: sample b's x_T and step noise then depend on
         seeds[b] alone -- not on the batch it is served in, its row or its rank (ops.randn_seeded).  None: `seed`, one
         RandomState draw for the whole batch.
-        guidance_rescale in [0, 1]: the samplers' keyword (CFG rescale for v-prediction checkpoints), every rank the same."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        guidance_rescale in [0, 1]: the samplers' keyword (CFG rescale for v-prediction checkpoints), every rank the same.
+        steps, scale and guidance_rescale each take one value or one per sample (a list): independent requests -- "30 steps,
+        scale 7.5" and "50 steps, scale 5, rescale 0.7" -- then share one UNet batch, every sample on its own schedule
+        (the samplers' per-request form).  Single rank only."""
+        guidance_rescale = self.check_request_lists("DiffusionPipeline", None, steps, scale, guidance_rescale)
         rank, n = D.world()
         shape = [4, H // 8, W // 8]                                   # txt2img.py:253
         if rank == 0:
@@ -193,6 +218,7 @@ class DiffusionPipeline:
                 per_sample_uc=per_sample_uc)
         else:
             B = int(c.shape[0])
+            self.check_request_lists("DiffusionPipeline", B, steps, scale, guidance_rescale)
             seeds = self.check_seeds(seeds, B)
             x_T = self._draw(x_T, seeds, ops.RNG_X_T, [B] + shape, seed)
             c, uc = self._on_device(c, uc, B)
@@ -221,8 +247,9 @@ class DiffusionPipeline:
         start_noise().  sample_posterior False: the posterior's mode.  mask [B, 1, h, w] at latent resolution, 1 = keep the
         init image there (PLMS / DDIM only).  Conditioning, decode and guidance_rescale as in __call__.  Single rank only.
         seeds: one int per sample; the forward noise (ops.RNG_ENCODE), the posterior noise (ops.RNG_POSTERIOR) and the step and
-        blend draws of sample b then depend on seeds[b] alone.  A passed noise / post_noise still wins."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        blend draws of sample b then depend on seeds[b] alone.  A passed noise / post_noise still wins.
+        scale and guidance_rescale each take one value or one per sample; steps is one int (`strength` fixes one grid)."""
+        guidance_rescale = self.check_request_lists("img2img", None, steps, scale, guidance_rescale, steps_list=False)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
         t_enc = self._check_strength("img2img", strength, steps)
@@ -232,6 +259,7 @@ class DiffusionPipeline:
             raise NotImplementedError("img2img: mask blending is implemented by PLMSSampler / DDIMSampler")
         c, uc = self._encoded(prompts, c, uc)
         B = int(c.shape[0])
+        self.check_request_lists("img2img", B, steps, scale, guidance_rescale, steps_list=False)
         seeds = self.check_seeds(seeds, B)
         c, uc = self._on_device(c, uc, B)
         start, a, b = self._partial_start(steps, t_enc, eta)
@@ -328,8 +356,9 @@ class DiffusionPipeline:
         is kept outside the mask, alpha * decoded + (1 - alpha) * image with alpha = the binarised mask, or with mask_blur
         (a Gaussian sigma in pixels, > 0) alpha = max(m, G * m) -- the mask widened outward, exactly 1 on the hole; composite
         False returns the decoder's picture as the reference does.  output "float": [B, 3, H, W] in [0, 1]; "uint8":
-        [B, H, W, 3], (uint8)(255 v) as inpaint.py:112-115."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        [B, H, W, 3], (uint8)(255 v) as inpaint.py:112-115.
+        scale and guidance_rescale each take one value or one per sample; steps is one int, as in img2img."""
+        guidance_rescale = self.check_request_lists("inpaint", None, steps, scale, guidance_rescale, steps_list=False)
         if output not in ("float", "uint8"):
             raise ValueError(f"inpaint: output must be 'float' or 'uint8', got {output!r}")
         t_enc = self._check_strength("inpaint", strength, steps)
@@ -342,6 +371,7 @@ class DiffusionPipeline:
             raise MdxError("inpaint runs on a single rank (the sharded form is not built)")
         c, uc = self._encoded(prompts, c, uc)
         B = int(c.shape[0])
+        self.check_request_lists("inpaint", B, steps, scale, guidance_rescale, steps_list=False)
         seeds = self.check_seeds(seeds, B)
         try:
             self._check_inpaint_inputs(image, mask, B)

@@ -14,6 +14,9 @@ median over rounds of (replay time / launches), and rescale - pred, which is wha
   torch_t / torch_td    the torch sequence of the samplers without seeds: randn, * temperature (t), and with noise_dropout
                         rand, >=, cast, * keep, / (1 - p) on top (td): 2 and 7 launches
   seeded_t / seeded_td  the one mdx_randn_f32 launch of ops.randn_seeded(scale=temperature[, dropout=p])
+--table measures the table-driven entry beside the scalar entries it stands in for, the same way and in the same process:
+  table / table_rescale  mdx_sampler_step_table_f32 with any_rescale 0 / 1 on rows that repeat the scalar calls' arguments
+                         (any_rescale 1: every row rescales, as in the scalar rescale launch)
 Prints one JSON line (and writes --out)."""
 import argparse
 import json
@@ -44,6 +47,36 @@ def bench_shape(shape, launches, rounds, warmup):
     entries = {"pred": lambda: ops.sampler_step_pred(*args), "rescale": lambda: ops.sampler_step_rescale(*args, 0.7)}
     res = time_entries(shape, entries, launches, rounds, warmup)
     res["extra_us"] = round(res["rescale_us"] - res["pred_us"], 3)
+    return res
+
+
+def bench_table(shape, launches, rounds, warmup):
+    import numpy as np
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    B, C, H, W = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    r32 = lambda: torch.randn(shape, device=dev, generator=g)
+    x, olds = r32(), [r32(), r32(), r32()]
+    out = torch.randn((2 * B, H * W, 8), device=dev, generator=g).half()
+    out_u, out_c = out[:B], out[B:]
+    e_out, x_prev, p_out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    coef = (55 / 24, -59 / 24, 37 / 24, -9 / 24)
+    args = (x, None, out_u, out_c, 8, 7.5, ops.PRED_V, 0.8, 0.6, olds, coef, 0.55, 0.83, 0.6, 0.8, 0.0, None, e_out, x_prev,
+            p_out)
+    row = np.zeros(ops.STEP_ROW, np.float32)
+    row[:ops.STEP_SIGMA + 1] = (1.0, 7.5, 0.0, 0.8, 0.6) + coef + (0.55, 0.83, 0.6, 0.8, 0.0)
+    plain = torch.tensor(np.tile(row, (B, 1)), device=dev)
+    row[ops.STEP_RESCALE] = 0.7
+    rescaled = torch.tensor(np.tile(row, (B, 1)), device=dev)
+    table = lambda t, any_rescale: ops.sampler_step_table(x, None, out_u, out_c, ops.PRED_V, olds, None, e_out, x_prev, p_out,
+                                                          t, any_rescale)
+    entries = {"pred": lambda: ops.sampler_step_pred(*args), "table": lambda: table(plain, 0),
+               "rescale": lambda: ops.sampler_step_rescale(*args, 0.7), "table_rescale": lambda: table(rescaled, 1)}
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    res["table_minus_pred_us"] = round(res["table_us"] - res["pred_us"], 3)
+    res["table_rescale_minus_rescale_us"] = round(res["table_rescale_us"] - res["rescale_us"], 3)
     return res
 
 
@@ -111,13 +144,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--noise", action="store_true", help="measure the stochastic step's noise preparation instead")
+    ap.add_argument("--table", action="store_true", help="measure the table-driven entry beside the scalar entries instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("step_bench: needs a GPU")
-    res = {"launches": a.launches, "rounds": a.rounds,
-           "shapes": [(bench_noise if a.noise else bench_shape)(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
+    bench = bench_noise if a.noise else bench_table if a.table else bench_shape
+    res = {"launches": a.launches, "rounds": a.rounds, "shapes": [bench(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
     if a.noise:
         res["what"] = "noise preparation of a stochastic step, us per step"
     line = json.dumps(res)
