@@ -565,6 +565,33 @@ int mdx_sampler_step_table_f32(const float* x, const float* x_model, const void*
                                const float* noise, float* e_t_out, float* x_prev, float* pred_x0, const float* table,
                                int any_rescale, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
 
+/* ---- Sampling sessions: the B samples of a batch are SLOTS that requests enter and leave while the batch keeps running
+ * (continuous batching; neither reference tree has it).  Slot b owns, all on the device and written only when a request is
+ * admitted into it:
+ *   sched[b][cap][MDX_STEP_ROW] fp32   the rows of its request, one per model evaluation, as mdx_sampler_step_table_f32 reads them
+ *   slot_start[b], slot_len[b]  int32  the session tick of the request's first model evaluation, and its step count
+ * At session tick `tick` (a host argument of every entry below) the slot stands at pos = tick - slot_start[b] and is ACTIVE iff
+ * 0 <= pos < min(slot_len[b], cap).  Nothing on the device changes between admissions: no cursor, no advance launch.
+ *
+ * mdx_sampler_step_slots_f32: mdx_sampler_step_table_f32 with row b = sched[b][pos_b].  An active slot computes, bit for bit,
+ * what the table entry computes on that row (the kernels run the same device bodies); a slot that is not active, or whose row has
+ * [MDX_STEP_ACTIVE] == 0, is an INACTIVE row of the table entry: x_prev[b] = x[b] (nothing to do where they alias), pred_x0[b],
+ * e_t_out[b] and factor_out[b] not written.  any_rescale, the two launch forms and the aliasing contract are the table entry's;
+ * nothing aliases sched / slot_start / slot_len.  Refused before any launch: what the table entry refuses, a NULL sched /
+ * slot_start / slot_len, cap <= 0, tick < 0. */
+int mdx_sampler_step_slots_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                               int pred_type, const float* old1, const float* old2, const float* old3,
+                               const float* noise, float* e_t_out, float* x_prev, float* pred_x0, const float* sched,
+                               const int* slot_start, const int* slot_len, int cap, int tick, int any_rescale,
+                               float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
+/* dst[r * B + b][0 .. n) = src[b][pos_b][0 .. n) for r < reps and every ACTIVE slot b (src [B][cap][n], dst [reps * B][n], fp32,
+ * contiguous, not overlapping); the dst rows of a slot that is not active are not written.  One launch; 16-byte loads and
+ * stores where n % 4 == 0 and both bases are 16-byte aligned, single floats otherwise.  With reps = 2 this puts the
+ * time-embedding rows of a tick into the [uncond; cond] layout of the guidance batch.  MDX_E_INVALID (nothing launched): a NULL
+ * pointer, B <= 0 or > 65535, n <= 0, reps <= 0, cap <= 0, tick < 0. */
+int mdx_slot_gather_f32(const float* src, const int* slot_start, const int* slot_len, int cap, int tick, float* dst, int B, long n,
+                        int reps, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);
@@ -714,6 +741,12 @@ int mdx_inpaint_composite_f32(const float* decoded, const float* image, const fl
 int mdx_philox_u32(const unsigned long long* seeds, unsigned stream, unsigned draw, unsigned* out, int B, long n, mdx_stream_t s);
 int mdx_randn_f32(const unsigned long long* seeds, unsigned stream, unsigned draw, float scale, float dropout_p, float* out, int B,
                   long n, mdx_stream_t s);
+/* mdx_randn_f32 with the draw counter per session slot (above): sample b of an ACTIVE slot gets draw = draw0 + pos_b (mod 2^32)
+ * -- the same stream, scale and dropout semantics and the same bits per element as mdx_randn_f32 called with that draw on that
+ * sample alone; the [n] span of a slot that is not active (0 <= tick - slot_start[b] < slot_len[b] fails) is not written.  Both
+ * store widths as mdx_randn_f32.  MDX_E_INVALID (nothing launched): what mdx_randn_f32 refuses, a NULL slot pointer, tick < 0. */
+int mdx_randn_slots_f32(const unsigned long long* seeds, unsigned stream, unsigned draw0, float scale, float dropout_p, float* out,
+                        const int* slot_start, const int* slot_len, int tick, int B, long n, mdx_stream_t s);
 
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):

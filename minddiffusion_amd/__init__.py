@@ -6,8 +6,17 @@ denoising hot path.  The package mirrors the reference's module layout for that 
     minddiffusion_amd.ldm.models.diffusion.ddpm.LatentDiffusion  (reference: ldm/models/diffusion/ddpm.py)
     minddiffusion_amd.ldm.modules.diffusionmodules.openaimodel.UNetModel
     minddiffusion_amd.pipeline.DiffusionPipeline                 (reference: txt2img.py main loop)
+    minddiffusion_amd.SamplingSession                            (new: requests join and leave a running UNet batch;
+                                                                  ldm/models/diffusion/session.py, DiffusionPipeline.session)
 
 All arithmetic runs in hand-written HIP kernels (minddiffusion_amd/csrc -> libmdx.so, C-ABI in
 include/mdx.h).  There is no CPU fallback anywhere in the package.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):      # on first use: importing the package stays free of torch
+    if name == "SamplingSession":
+        from .ldm.models.diffusion.session import SamplingSession
+        return SamplingSession
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

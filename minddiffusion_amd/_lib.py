@@ -145,6 +145,10 @@ SIGNATURES = {
     "mdx_sampler_step_table_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                            c_int, c_int, c_int, c_int, c_void_p]),
+    "mdx_sampler_step_slots_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mdx_slot_gather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_long, c_int, c_void_p]),
     "mdx_avgpool2x2_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_upsample_nearest2x_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_glide_text_embed_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -169,6 +173,8 @@ SIGNATURES = {
                                           c_int, c_void_p]),
     "mdx_philox_u32": (c_int, [c_void_p, c_uint, c_uint, c_void_p, c_int, c_long, c_void_p]),
     "mdx_randn_f32": (c_int, [c_void_p, c_uint, c_uint, c_float, c_float, c_void_p, c_int, c_long, c_void_p]),
+    "mdx_randn_slots_f32": (c_int, [c_void_p, c_uint, c_uint, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_long, c_void_p]),
     "mdx_softmax_rows_f16": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_void_p]),
     "mdx_probe_mfma_32x32x16_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mdx_probe_mfma_16x16x32_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -124,6 +124,16 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Sampling sessions (include/mdx.h, "slots"): where slot b of a session stands at session tick `tick`.  pos = tick -
+// slot_start[b] counts the model evaluations its request has had; the slot is active iff 0 <= pos < min(slot_len[b], cap) and
+// the result is then pos, else -1.  cap bounds every [cap]-sized per-slot table the caller indexes with the result, whatever
+// slot_len holds.  b is the workgroup's (or the wave's) sample, so both loads are the same address in every lane.
+__device__ __forceinline__ int mdx_slot_pos(const int* slot_start, const int* slot_len, int b, int cap, int tick) {
+    const long long pos = (long long)tick - slot_start[b];
+    const int len = slot_len[b] < cap ? slot_len[b] : cap;
+    return pos >= 0 && pos < len ? (int)pos : -1;
+}
+
 // 16-byte direct-to-LDS DMA through a buffer descriptor: per-lane source byte offset `voff`
 // (offsets >= num_records return zeros: this is how conv zero padding and tile tails are done),
 // destination = wave-uniform `lds` + lane*16.

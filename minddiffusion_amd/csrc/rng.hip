@@ -67,6 +67,10 @@ struct RngParams {
     float scale, dropout_p, inv_keep;
     unsigned long long n;   // elements of one sample
     unsigned long long items;   // B * n / V
+    // SLOTS only (mdx_randn_slots_f32): sample b draws with counter draw + pos_b, and only while its slot is active
+    const int* slot_start;
+    const int* slot_len;
+    int tick;
 };
 
 enum { MODE_U32 = 0, MODE_NORMAL = 1, MODE_NORMAL_DROPOUT = 2 };
@@ -74,9 +78,10 @@ enum { MODE_U32 = 0, MODE_NORMAL = 1, MODE_NORMAL_DROPOUT = 2 };
 // The four elements 4 blk .. 4 blk + 3 of the sample with this seed; both launch forms go through here, so an element's bits do
 // not depend on the form that wrote it.
 template <int MODE>
-__device__ __forceinline__ void quad_values(const RngParams& p, unsigned long long seed, unsigned blk, unsigned (&bits)[4]) {
+__device__ __forceinline__ void quad_values(const RngParams& p, unsigned long long seed, unsigned draw, unsigned blk,
+                                            unsigned (&bits)[4]) {
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    const Quad q = philox4x32_10(blk, p.draw, p.stream, k0, k1);
+    const Quad q = philox4x32_10(blk, draw, p.stream, k0, k1);
     if constexpr (MODE == MODE_U32) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) bits[e] = q.w[e];
@@ -87,7 +92,7 @@ __device__ __forceinline__ void quad_values(const RngParams& p, unsigned long lo
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = p.scale * z[e];
         if constexpr (MODE == MODE_NORMAL_DROPOUT) {
-            const Quad d = philox4x32_10(blk, p.draw, p.stream | DROPOUT_STREAM_BIT, k0, k1);
+            const Quad d = philox4x32_10(blk, draw, p.stream | DROPOUT_STREAM_BIT, k0, k1);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = uniform_open(d.w[e]) >= p.dropout_p ? v[e] * p.inv_keep : 0.0f;
         }
@@ -98,22 +103,30 @@ __device__ __forceinline__ void quad_values(const RngParams& p, unsigned long lo
 
 // V == 4: item j is quad j % (n / 4) of sample j / (n / 4) (n % 4 == 0, out 16-byte aligned: the host decides);
 // V == 1: item j is element j % n of sample j / n, lane (element & 3) of its quad.
-template <int MODE, int V>
+// SLOTS: the draw counter is per sample, p.draw + pos of the sample's session slot (mdx_common.h: mdx_slot_pos), and the items
+// of an inactive slot are skipped -- nothing of its span is written.  The values still come from quad_values alone.
+template <int MODE, int V, bool SLOTS = false>
 __global__ __launch_bounds__(RNG_THREADS) void rng_kernel(const RngParams p) {
     const unsigned long long per = p.n / V;
     unsigned* out = reinterpret_cast<unsigned*>(p.out);     // fp32 results travel as their bit patterns
     for (unsigned long long j = (unsigned long long)blockIdx.x * RNG_THREADS + threadIdx.x; j < p.items;
          j += (unsigned long long)gridDim.x * RNG_THREADS) {
         const unsigned long long b = j / per, i = j - b * per;
+        unsigned draw = p.draw;
+        if constexpr (SLOTS) {
+            const int pos = mdx_slot_pos(p.slot_start, p.slot_len, (int)b, 0x7fffffff, p.tick);
+            if (pos < 0) continue;
+            draw += (unsigned)pos;
+        }
         const unsigned long long seed = p.seeds[b];
         unsigned v[4];
         if constexpr (V == 4) {
-            quad_values<MODE>(p, seed, (unsigned)i, v);
+            quad_values<MODE>(p, seed, draw, (unsigned)i, v);
             u32x4 t;
             t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
             *reinterpret_cast<u32x4*>(out + j * 4) = t;
         } else {
-            quad_values<MODE>(p, seed, (unsigned)(i >> 2), v);
+            quad_values<MODE>(p, seed, draw, (unsigned)(i >> 2), v);
             const int lane = (int)(i & 3);
             out[j] = lane == 0 ? v[0] : lane == 1 ? v[1] : lane == 2 ? v[2] : v[3];
         }
@@ -127,14 +140,14 @@ inline int rng_blocks(unsigned long long items) {
     return (int)(blocks < (unsigned long long)RNG_MAX_BLOCKS ? blocks : (unsigned long long)RNG_MAX_BLOCKS);
 }
 
-template <int MODE>
+template <int MODE, bool SLOTS = false>
 void rng_launch(RngParams p, int B, hipStream_t s) {
     if (p.n % 4 == 0 && aligned16(p.out)) {
         p.items = (unsigned long long)B * (p.n / 4);
-        hipLaunchKernelGGL((rng_kernel<MODE, 4>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
+        hipLaunchKernelGGL((rng_kernel<MODE, 4, SLOTS>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
     } else {
         p.items = (unsigned long long)B * p.n;
-        hipLaunchKernelGGL((rng_kernel<MODE, 1>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
+        hipLaunchKernelGGL((rng_kernel<MODE, 1, SLOTS>), dim3(rng_blocks(p.items)), dim3(RNG_THREADS), 0, s, p);
     }
 }
 
@@ -151,6 +164,7 @@ extern "C" int mdx_philox_u32(const unsigned long long* seeds, unsigned stream, 
     p.stream = stream; p.draw = draw;
     p.scale = 1.0f; p.dropout_p = 0.0f; p.inv_keep = 1.0f;
     p.n = (unsigned long long)n; p.items = 0;
+    p.slot_start = p.slot_len = nullptr; p.tick = 0;
     rng_launch<MODE_U32>(p, B, (hipStream_t)s);
     MDX_LAUNCH_CHECK("mdx_philox_u32");
     return MDX_OK;
@@ -167,10 +181,34 @@ extern "C" int mdx_randn_f32(const unsigned long long* seeds, unsigned stream, u
     p.stream = stream; p.draw = draw;
     p.scale = scale; p.dropout_p = dropout_p; p.inv_keep = 1.0f / (1.0f - dropout_p);
     p.n = (unsigned long long)n; p.items = 0;
+    p.slot_start = p.slot_len = nullptr; p.tick = 0;
     if (dropout_p > 0.0f)
         rng_launch<MODE_NORMAL_DROPOUT>(p, B, (hipStream_t)s);
     else
         rng_launch<MODE_NORMAL>(p, B, (hipStream_t)s);
     MDX_LAUNCH_CHECK("mdx_randn_f32");
+    return MDX_OK;
+}
+
+extern "C" int mdx_randn_slots_f32(const unsigned long long* seeds, unsigned stream, unsigned draw0, float scale, float dropout_p,
+                                   float* out, const int* slot_start, const int* slot_len, int tick, int B, long n,
+                                   mdx_stream_t s) {
+    MDX_REQUIRE(seeds && out && slot_start && slot_len, "mdx_randn_slots_f32: null pointer");
+    MDX_REQUIRE(B > 0 && n > 0 && n <= RNG_MAX_N, "mdx_randn_slots_f32: bad extents (B=%d n=%ld; 0 < n <= 2^34)", B, n);
+    MDX_REQUIRE(tick >= 0, "mdx_randn_slots_f32: tick must be >= 0, got %d", tick);
+    MDX_REQUIRE(dropout_p >= 0.0f && dropout_p < 1.0f, "mdx_randn_slots_f32: dropout_p must be in [0, 1), got %g",
+                (double)dropout_p);
+    MDX_REQUIRE(isfinite(scale), "mdx_randn_slots_f32: scale must be finite");
+    RngParams p;
+    p.seeds = seeds; p.out = out;
+    p.stream = stream; p.draw = draw0;
+    p.scale = scale; p.dropout_p = dropout_p; p.inv_keep = 1.0f / (1.0f - dropout_p);
+    p.n = (unsigned long long)n; p.items = 0;
+    p.slot_start = slot_start; p.slot_len = slot_len; p.tick = tick;
+    if (dropout_p > 0.0f)
+        rng_launch<MODE_NORMAL_DROPOUT, true>(p, B, (hipStream_t)s);
+    else
+        rng_launch<MODE_NORMAL, true>(p, B, (hipStream_t)s);
+    MDX_LAUNCH_CHECK("mdx_randn_slots_f32");
     return MDX_OK;
 }

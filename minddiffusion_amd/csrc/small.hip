@@ -352,9 +352,9 @@ struct TableParams {
     float* factor_out;
 };
 
-__device__ __forceinline__ bool table_row(StepParams& p, const float* table, int b, float& phi) {
-    const float* row = table + (size_t)b * MDX_STEP_ROW;
-    if (row[MDX_STEP_ACTIVE] == 0.f) return false;
+// row: the MDX_STEP_ROW floats of the sample, or nullptr for a sample that has none (a session slot outside its request)
+__device__ __forceinline__ bool table_row(StepParams& p, const float* row, float& phi) {
+    if (!row || row[MDX_STEP_ACTIVE] == 0.f) return false;
     p.cfg_scale = row[MDX_STEP_CFG_SCALE];
     phi = row[MDX_STEP_RESCALE];
     p.am = row[MDX_STEP_SQRT_AT_MODEL];
@@ -383,20 +383,20 @@ __device__ __forceinline__ void table_copy_row(const StepParams& p, int b, unsig
     for (unsigned j = first + threadIdx.x; j < N; j += stride) p.x_prev[base + j] = p.x[base + j];
 }
 
+// The two launch forms as functions of (parameters, the sample's row): the table kernels hand them row b of one table, the
+// slot kernels the row their slot stands on.
 // No row rescales: gridDim.x workgroups share sample blockIdx.y, sampler_step_kernel's statements per element.
 template <int PRED>
-__global__ __launch_bounds__(256) void sampler_step_table_kernel(const TableParams tp) {
-    mdx_kernarg_touch<sizeof(TableParams)>();
-    StepParams p = tp.s;
+__device__ __forceinline__ void step_row_spread(StepParams& p, const float* row, float* factor_out) {
     const int b = blockIdx.y;
     const unsigned N = (unsigned)p.C * (unsigned)p.HW, HW = p.HW;      // the host refuses what does not fit 31 bits
     const unsigned first = blockIdx.x * 256u, stride = gridDim.x * 256u;
     float phi;
-    if (!table_row(p, tp.table, b, phi)) {
+    if (!table_row(p, row, phi)) {
         table_copy_row(p, b, first, stride);
         return;
     }
-    if (tp.factor_out && blockIdx.x == 0 && threadIdx.x == 0) tp.factor_out[b] = 1.f;
+    if (factor_out && blockIdx.x == 0 && threadIdx.x == 0) factor_out[b] = 1.f;
     const size_t base = (size_t)b * N;
     for (unsigned j = first + threadIdx.x; j < N; j += stride) {
         const unsigned c = j / HW;
@@ -411,20 +411,91 @@ __global__ __launch_bounds__(256) void sampler_step_table_kernel(const TablePara
 // launch against the plain entry) and test_constant_outputs_give_factor_one hold it on hardware; if a toolchain update makes
 // them fail, respell rescale_apply -- do not loosen the tests.
 template <int PRED>
-__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_table_rescale_kernel(const TableParams tp) {
-    mdx_kernarg_touch<sizeof(TableParams)>();
-    StepParams p = tp.s;
-    __shared__ float part[RESCALE_THREADS / 64][4];
+__device__ __forceinline__ void step_row_owned(StepParams& p, const float* row, float* factor_out, float (*part)[4]) {
     const int b = blockIdx.x;
     float phi;
-    if (!table_row(p, tp.table, b, phi)) {
+    if (!table_row(p, row, phi)) {
         table_copy_row(p, b, 0u, (unsigned)RESCALE_THREADS);
         return;
     }
     float f = 1.f;
     if (phi != 0.f) f = rescale_factor(p, phi, b, part);      // the row is the workgroup's: every thread takes the same side
-    if (tp.factor_out && threadIdx.x == 0) tp.factor_out[b] = f;
+    if (factor_out && threadIdx.x == 0) factor_out[b] = f;
     rescale_apply<PRED>(p, f, b);
+}
+
+template <int PRED>
+__global__ __launch_bounds__(256) void sampler_step_table_kernel(const TableParams tp) {
+    mdx_kernarg_touch<sizeof(TableParams)>();
+    StepParams p = tp.s;
+    step_row_spread<PRED>(p, tp.table + (size_t)blockIdx.y * MDX_STEP_ROW, tp.factor_out);
+}
+
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_table_rescale_kernel(const TableParams tp) {
+    mdx_kernarg_touch<sizeof(TableParams)>();
+    StepParams p = tp.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    step_row_owned<PRED>(p, tp.table + (size_t)blockIdx.x * MDX_STEP_ROW, tp.factor_out, part);
+}
+
+// ------------------------------------------------------------------ fused sampler update, rows looked up per session slot
+// A sampling session (mdx_sampler_step_slots_f32): slot b keeps the rows of the request in it, sched[b][0 .. cap), and stands
+// on row pos = tick - slot_start[b] of them.  The tick is a kernel argument and nothing on the device moves between
+// admissions.  A slot outside its request has no row: the inactive row of the table entry.
+struct SlotParams {
+    StepParams s;
+    const float* sched;       // [B][cap][MDX_STEP_ROW]
+    const int* slot_start;    // [B]
+    const int* slot_len;      // [B]
+    int cap, tick;
+    float* factor_out;
+};
+
+__device__ __forceinline__ const float* slot_row(const SlotParams& sp, int b) {
+    const int pos = mdx_slot_pos(sp.slot_start, sp.slot_len, b, sp.cap, sp.tick);
+    return pos < 0 ? nullptr : sp.sched + ((size_t)b * sp.cap + pos) * MDX_STEP_ROW;
+}
+
+template <int PRED>
+__global__ __launch_bounds__(256) void sampler_step_slots_kernel(const SlotParams sp) {
+    mdx_kernarg_touch<sizeof(SlotParams)>();
+    StepParams p = sp.s;
+    step_row_spread<PRED>(p, slot_row(sp, blockIdx.y), sp.factor_out);
+}
+
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_slots_rescale_kernel(const SlotParams sp) {
+    mdx_kernarg_touch<sizeof(SlotParams)>();
+    StepParams p = sp.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    step_row_owned<PRED>(p, slot_row(sp, blockIdx.x), sp.factor_out, part);
+}
+
+// ------------------------------------------------------------------ per-slot row gather (mdx_slot_gather_f32)
+// dst[r * B + b][:] = src[b][pos_b][:] for the active slots: gridDim.x workgroups share slot blockIdx.y.  V == 4 moves 16 bytes
+// per lane (n % 4 == 0 and both bases 16-byte aligned: the host decides), V == 1 one float.
+constexpr int SLOT_GATHER_THREADS = 256;
+
+template <int V>
+__global__ __launch_bounds__(SLOT_GATHER_THREADS) void slot_gather_kernel(const float* __restrict__ src,
+                                                                           const int* __restrict__ slot_start,
+                                                                           const int* __restrict__ slot_len, int cap, int tick,
+                                                                           float* __restrict__ dst, int B, size_t n, int reps) {
+    const int b = blockIdx.y;
+    const int pos = mdx_slot_pos(slot_start, slot_len, b, cap, tick);
+    if (pos < 0) return;
+    const float* row = src + ((size_t)b * cap + pos) * n;
+    const size_t items = n / V, stride = (size_t)gridDim.x * SLOT_GATHER_THREADS;
+    for (size_t j = (size_t)blockIdx.x * SLOT_GATHER_THREADS + threadIdx.x; j < items; j += stride) {
+        if constexpr (V == 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(row + j * 4);
+            for (int r = 0; r < reps; ++r) *reinterpret_cast<f32x4*>(dst + ((size_t)r * B + b) * n + j * 4) = v;
+        } else {
+            const float v = row[j];
+            for (int r = 0; r < reps; ++r) dst[((size_t)r * B + b) * n + j] = v;
+        }
+    }
 }
 
 // ------------------------------------------------------------------ MFMA layout probe
@@ -629,6 +700,33 @@ extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model
     return MDX_OK;
 }
 
+// What the table entry and the slot entry refuse and fill alike: the pointer and extent checks of the scalar entries on
+// coefficients that need none (they live on the device), the limits of the two launch forms, and the history / noise
+// pointers as given -- table_row keeps or drops them by the row's coefficient.
+static int step_rows_params(StepParams& p, const char* fn, const float* x, const float* x_model, const void* out_u,
+                            const void* out_c, int out_ld, int pred_type, const float* old1, const float* old2,
+                            const float* old3, const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
+                            int any_rescale, int B, int C, int H, int W) {
+    const float no_history[4] = {1.f, 0.f, 0.f, 0.f};
+    const int rc = sampler_step_params(p, fn, x, x_model, out_u, out_c, out_ld, 1.f, pred_type, 1.f, 0.f, old1, old2, old3,
+                                       no_history, 1.f, 0.f, 1.f, 0.f, 0.f, noise, e_t_out, x_prev, pred_x0, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(!any_rescale || out_u, "%s: any_rescale needs the unconditional output out_u", fn);
+    MDX_REQUIRE(!any_rescale || (size_t)C * H * W >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
+    MDX_REQUIRE((size_t)C * H * W <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
+    MDX_REQUIRE(any_rescale || B <= 65535, "%s: bad extents (B exceeds 65535 samples)", fn);
+    p.old1 = old1;
+    p.old2 = old2;
+    p.old3 = old3;
+    p.noise = noise;
+    return MDX_OK;
+}
+
+// the workgroups of sampler_step_kernel's grid for the same batch, dealt to the samples
+static dim3 step_rows_spread_grid(int B, int C, int H, int W) {
+    return dim3((grid_for((size_t)B * C * H * W) + B - 1) / B, B);
+}
+
 extern "C" int mdx_sampler_step_table_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
                                           int out_ld, int pred_type, const float* old1, const float* old2,
                                           const float* old3, const float* noise, float* e_t_out, float* x_prev,
@@ -636,20 +734,10 @@ extern "C" int mdx_sampler_step_table_f32(const float* x, const float* x_model, 
                                           int C, int H, int W, mdx_stream_t s) {
     const char* fn = "mdx_sampler_step_table_f32";
     TableParams tp;
-    // the coefficients live on the device: the pointer and extent checks of the scalar entries, on coefficients that need none
-    const float no_history[4] = {1.f, 0.f, 0.f, 0.f};
-    const int rc = sampler_step_params(tp.s, fn, x, x_model, out_u, out_c, out_ld, 1.f, pred_type, 1.f, 0.f, old1, old2, old3,
-                                       no_history, 1.f, 0.f, 1.f, 0.f, 0.f, noise, e_t_out, x_prev, pred_x0, B, C, H, W);
+    const int rc = step_rows_params(tp.s, fn, x, x_model, out_u, out_c, out_ld, pred_type, old1, old2, old3, noise, e_t_out,
+                                    x_prev, pred_x0, any_rescale, B, C, H, W);
     if (rc != MDX_OK) return rc;
     MDX_REQUIRE(table, "%s: null table", fn);
-    MDX_REQUIRE(!any_rescale || out_u, "%s: any_rescale needs the unconditional output out_u", fn);
-    MDX_REQUIRE(!any_rescale || (size_t)C * H * W >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
-    MDX_REQUIRE((size_t)C * H * W <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
-    MDX_REQUIRE(any_rescale || B <= 65535, "%s: bad extents (B exceeds 65535 samples)", fn);
-    tp.s.old1 = old1;      // table_row keeps or drops them by the row's coefficient
-    tp.s.old2 = old2;
-    tp.s.old3 = old3;
-    tp.s.noise = noise;
     tp.table = table;
     tp.factor_out = factor_out;
     const hipStream_t st = (hipStream_t)s;
@@ -659,14 +747,69 @@ extern "C" int mdx_sampler_step_table_f32(const float* x, const float* x_model, 
         else
             hipLaunchKernelGGL(sampler_step_table_rescale_kernel<MDX_PRED_EPS>, dim3(B), dim3(RESCALE_THREADS), 0, st, tp);
     } else {
-        // the workgroups of sampler_step_kernel's grid for the same batch, dealt to the samples
-        const int per_sample = (grid_for((size_t)B * C * H * W) + B - 1) / B;
-        const dim3 grid(per_sample, B);
+        const dim3 grid = step_rows_spread_grid(B, C, H, W);
         if (pred_type == MDX_PRED_V)
             hipLaunchKernelGGL(sampler_step_table_kernel<MDX_PRED_V>, grid, dim3(256), 0, st, tp);
         else
             hipLaunchKernelGGL(sampler_step_table_kernel<MDX_PRED_EPS>, grid, dim3(256), 0, st, tp);
     }
+    MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
+}
+
+extern "C" int mdx_sampler_step_slots_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
+                                          int out_ld, int pred_type, const float* old1, const float* old2,
+                                          const float* old3, const float* noise, float* e_t_out, float* x_prev,
+                                          float* pred_x0, const float* sched, const int* slot_start, const int* slot_len,
+                                          int cap, int tick, int any_rescale, float* factor_out, int B, int C, int H, int W,
+                                          mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_slots_f32";
+    SlotParams sp;
+    const int rc = step_rows_params(sp.s, fn, x, x_model, out_u, out_c, out_ld, pred_type, old1, old2, old3, noise, e_t_out,
+                                    x_prev, pred_x0, any_rescale, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(sched && slot_start && slot_len, "%s: null slot pointer", fn);
+    MDX_REQUIRE(cap > 0 && tick >= 0, "%s: bad slot extents (cap=%d tick=%d; cap > 0, tick >= 0)", fn, cap, tick);
+    sp.sched = sched;
+    sp.slot_start = slot_start;
+    sp.slot_len = slot_len;
+    sp.cap = cap;
+    sp.tick = tick;
+    sp.factor_out = factor_out;
+    const hipStream_t st = (hipStream_t)s;
+    if (any_rescale) {
+        if (pred_type == MDX_PRED_V)
+            hipLaunchKernelGGL(sampler_step_slots_rescale_kernel<MDX_PRED_V>, dim3(B), dim3(RESCALE_THREADS), 0, st, sp);
+        else
+            hipLaunchKernelGGL(sampler_step_slots_rescale_kernel<MDX_PRED_EPS>, dim3(B), dim3(RESCALE_THREADS), 0, st, sp);
+    } else {
+        const dim3 grid = step_rows_spread_grid(B, C, H, W);
+        if (pred_type == MDX_PRED_V)
+            hipLaunchKernelGGL(sampler_step_slots_kernel<MDX_PRED_V>, grid, dim3(256), 0, st, sp);
+        else
+            hipLaunchKernelGGL(sampler_step_slots_kernel<MDX_PRED_EPS>, grid, dim3(256), 0, st, sp);
+    }
+    MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
+}
+
+extern "C" int mdx_slot_gather_f32(const float* src, const int* slot_start, const int* slot_len, int cap, int tick, float* dst,
+                                   int B, long n, int reps, mdx_stream_t s) {
+    const char* fn = "mdx_slot_gather_f32";
+    MDX_REQUIRE(src && slot_start && slot_len && dst, "%s: null pointer", fn);
+    MDX_REQUIRE(B > 0 && B <= 65535 && n > 0 && reps > 0, "%s: bad extents (B=%d n=%ld reps=%d)", fn, B, n, reps);
+    MDX_REQUIRE(cap > 0 && tick >= 0, "%s: bad slot extents (cap=%d tick=%d; cap > 0, tick >= 0)", fn, cap, tick);
+    const bool vec = n % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+    const size_t items = vec ? (size_t)n / 4 : (size_t)n;
+    size_t per_slot = (items + SLOT_GATHER_THREADS - 1) / SLOT_GATHER_THREADS;
+    if (per_slot > 64) per_slot = 64;       // a row is a few tens of KB: further trips of the grid-stride loop beyond that
+    const dim3 grid((unsigned)per_slot, B);
+    if (vec)
+        hipLaunchKernelGGL(slot_gather_kernel<4>, grid, dim3(SLOT_GATHER_THREADS), 0, (hipStream_t)s, src, slot_start, slot_len,
+                           cap, tick, dst, B, (size_t)n, reps);
+    else
+        hipLaunchKernelGGL(slot_gather_kernel<1>, grid, dim3(SLOT_GATHER_THREADS), 0, (hipStream_t)s, src, slot_start, slot_len,
+                           cap, tick, dst, B, (size_t)n, reps);
     MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
 }

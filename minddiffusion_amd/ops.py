@@ -833,6 +833,52 @@ def sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out
         _ptr(factor_out), B, C, H, W, _stream()), "mdx_sampler_step_table_f32")
 
 
+# ---- sampling sessions (include/mdx.h, "slots"): the samples of a batch are slots that requests enter and leave
+def _chk_slots(B, slot_start, slot_len):
+    for name, t in (("slot_start", slot_start), ("slot_len", slot_len)):
+        _chk(t, torch.int32, name)
+        if tuple(t.shape) != (B,):
+            raise _lib.MdxError(f"{name}: expected [{B}] int32, got {tuple(t.shape)}")
+
+
+def sampler_step_slots(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0, sched, slot_start, slot_len,
+                       tick, any_rescale, factor_out=None):
+    """sampler_step_table with the row of sample b looked up per slot: sched [B, cap, STEP_ROW] fp32 holds the rows of the
+    request in slot b, and at session tick `tick` the slot reads row tick - slot_start[b] if that lies in [0, slot_len[b]) and is
+    an inactive row otherwise (see include/mdx.h).  any_rescale: whether some active slot's row has a non-zero guidance
+    rescale -- the caller's host mirror knows; nothing here syncs."""
+    B, C, H, W = x.shape
+    _chk(sched, f32, "sched")
+    if sched.dim() != 3 or sched.shape[0] != B or sched.shape[2] != STEP_ROW:
+        raise _lib.MdxError(f"sched: expected [{B}, cap, {STEP_ROW}], got {tuple(sched.shape)}")
+    _chk_slots(B, slot_start, slot_len)
+    o = list(olds) + [None] * (3 - len(olds))
+    if factor_out is not None:
+        _chk(factor_out, f32, "factor_out")
+        if factor_out.numel() < B:
+            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    _lib.check(_lib.load().mdx_sampler_step_slots_f32(
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), _ptr(o[0]), _ptr(o[1]),
+        _ptr(o[2]), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(sched), _ptr(slot_start), _ptr(slot_len),
+        int(sched.shape[1]), int(tick), int(bool(any_rescale)), _ptr(factor_out), B, C, H, W, _stream()),
+        "mdx_sampler_step_slots_f32")
+
+
+def slot_gather(src, slot_start, slot_len, tick, out, reps=2):
+    """out[r * B + b] = src[b, tick - slot_start[b]] for r < reps and every active slot b; the rows of the other slots are not
+    written.  src [B, cap, n] fp32, out [reps * B, n] fp32.  One launch."""
+    _chk(src, f32, "src"); _chk(out, f32, "out")
+    if src.dim() != 3:
+        raise _lib.MdxError(f"slot_gather: src must be [B, cap, n], got {tuple(src.shape)}")
+    B, cap, n = (int(d) for d in src.shape)
+    _chk_slots(B, slot_start, slot_len)
+    if tuple(out.shape) != (int(reps) * B, n):
+        raise _lib.MdxError(f"slot_gather: out has shape {tuple(out.shape)}, expected {(int(reps) * B, n)}")
+    _lib.check(_lib.load().mdx_slot_gather_f32(_ptr(src), _ptr(slot_start), _ptr(slot_len), cap, int(tick), _ptr(out), B, n,
+                                               int(reps), _stream()), "mdx_slot_gather_f32")
+    return out
+
+
 def probe_mfma(a, b):
     c = torch.empty((64, 16), dtype=f32, device=a.device)
     _lib.check(_lib.load().mdx_probe_mfma_32x32x16_f16(_ptr(a), _ptr(b), _ptr(c), _stream()), "mdx_probe_mfma")
@@ -1138,6 +1184,20 @@ def randn_seeded(seeds, stream, draw, sample_shape, scale=1.0, dropout=0.0, out=
     out, B, n = _rng_args("randn_seeded", seeds, stream, draw, sample_shape, out, f32)
     _lib.check(_lib.load().mdx_randn_f32(_ptr(seeds), int(stream), int(draw), float(scale), float(dropout), _ptr(out), B, n,
                                          _stream()), "mdx_randn_f32")
+    return out
+
+
+def randn_slots(seeds, stream, draw0, slot_start, slot_len, tick, out, scale=1.0, dropout=0.0):
+    """randn_seeded with the draw counter per session slot: sample b of `out` [B, *sample_shape] gets draw
+    draw0 + (tick - slot_start[b]) while that position lies in [0, slot_len[b]) -- the bits randn_seeded(seeds[b:b+1], stream,
+    that draw, ...) gives -- and is not written otherwise.  One launch."""
+    if out is None:
+        raise _lib.MdxError("randn_slots: pass out (the slots that are not active keep what it holds)")
+    out, B, n = _rng_args("randn_slots", seeds, stream, draw0, tuple(out.shape[1:]), out, f32)
+    _chk_slots(B, slot_start, slot_len)
+    _lib.check(_lib.load().mdx_randn_slots_f32(_ptr(seeds), int(stream), int(draw0), float(scale), float(dropout), _ptr(out),
+                                               _ptr(slot_start), _ptr(slot_len), int(tick), B, n, _stream()),
+               "mdx_randn_slots_f32")
     return out
 
 

@@ -235,6 +235,50 @@ class DiffusionPipeline:
             samples = D.gather_latents(samples)
         return samples
 
+    # ---- continuous batching (ldm/models/diffusion/session.py): requests join and leave a running UNet batch
+    def _session_sampler(self):
+        from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        for cls, name in ((DPMSolverSampler, "dpm_solver"), (PLMSSampler, "plms"), (DDIMSampler, "ddim")):
+            if isinstance(self.sampler, cls):
+                return name
+        raise MdxError(f"DiffusionPipeline.session: pass sampler='ddim' or 'dpm_solver' (the pipeline's sampler is a "
+                       f"{type(self.sampler).__name__})")
+
+    def session(self, slots=4, H=512, W=512, sampler=None, context_len=WINDOW, max_steps=50, temperature=1.0,
+                noise_dropout=0.0, empty=None):
+        """A SamplingSession on this pipeline's model: `slots` samples of one latent shape whose requests come and go
+        (submit / step / run_until_idle).  sampler: 'ddim' or 'dpm_solver' (default: the pipeline's; PLMS is refused)."""
+        from .ldm.models.diffusion.session import SamplingSession
+        return SamplingSession(self.model, slots, H=H, W=W, sampler=sampler or self._session_sampler(),
+                               context_len=context_len, max_steps=max_steps, temperature=temperature,
+                               noise_dropout=noise_dropout, device=self.device, empty=empty)
+
+    def serve(self, requests, slots=4, H=512, W=512, output="float", sampler=None, temperature=1.0, noise_dropout=0.0,
+              empty=None):
+        """Drain a list of requests -- dicts of SamplingSession.submit's keywords -- through one session of `slots` slots;
+        the results come back in REQUEST order, whatever order they finished in.  output: 'latent' [N, 4, H/8, W/8]; 'float'
+        [N, 3, H, W] in [0, 1], what __call__(decode=True) returns; 'uint8' [N, H, W, 3], truncated as inpaint.py:112-115."""
+        if output not in ("latent", "float", "uint8"):
+            raise ValueError("output must be 'latent', 'float' or 'uint8'")
+        requests = list(requests)
+        if not requests:
+            raise MdxError("DiffusionPipeline.serve: no requests")
+        lens = [int(r[k].shape[-2]) for r in requests for k in ("c", "uc") if isinstance(r.get(k), torch.Tensor)]
+        if not lens or any(r.get("prompt") is not None for r in requests):
+            lens.append(WINDOW)
+        max_steps = max([int(r["steps"]) for r in requests if isinstance(r.get("steps"), (int, np.integer))] + [30])
+        sess = self.session(slots, H, W, sampler, max(lens), max_steps, temperature, noise_dropout, empty)
+        handles = [sess.submit(**r) for r in requests]
+        sess.run_until_idle()
+        self.last_session = sess
+        latents = torch.stack([h.latent for h in handles])
+        if output == "latent":
+            return latents
+        images = torch.cat([self._decoded(latents[i:i + slots]) for i in range(0, len(handles), slots)])
+        if output == "float":
+            return images
+        return (images * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
     def img2img(self, init_image=None, init_latent=None, strength=0.75, prompts=None, c=None, uc=None, steps=50, scale=9.0,
                 eta=0.0, seed=42, noise=None, post_noise=None, sample_posterior=True, mask=None, decode=False, callback=None,
                 img_callback=None, guidance_rescale=0.0, seeds=None):
