@@ -747,6 +747,22 @@ int mdx_randn_f32(const unsigned long long* seeds, unsigned stream, unsigned dra
  * store widths as mdx_randn_f32.  MDX_E_INVALID (nothing launched): what mdx_randn_f32 refuses, a NULL slot pointer, tick < 0. */
 int mdx_randn_slots_f32(const unsigned long long* seeds, unsigned stream, unsigned draw0, float scale, float dropout_p, float* out,
                         const int* slot_start, const int* slot_len, int tick, int B, long n, mdx_stream_t s);
+/* The mask blend of an img2img request in a session (plms.py:153-157 per slot), one launch: for every slot b that is ACTIVE at
+ * `tick` (above, with `cap`) and has blend_on[b] != 0, and every element e of its [C][HW] sample,
+ *   n   = the value mdx_randn_f32 gives sample b at (stream, draw0 + pos_b mod 2^32) with scale 1 and no dropout
+ *   q   = fma(a, x0[b][e], b * n),   (a, b) = blend_ab[b][pos_b][0 .. 2)           (the q-sample statement of mdx_q_sample_f32)
+ *   img[b][e] = fma(keep[b][e], q, (1 - keep[b][e]) * img[b][e])                    (its blend statement)
+ * x0, keep, img: NCHW fp32 [B][C][HW], contiguous; blend_ab fp32 [B][cap][2]; blend_on int32 [B].  Only the img spans of those
+ * slots are written (in place); the span of a slot that is not active or has blend_on[b] == 0 is neither read nor written, and
+ * the noise is never stored.  Bit for bit, per slot: mdx_randn_f32 on sample b alone at that draw followed by
+ * mdx_q_sample_f32(x0[b], noise, a, b, mask = keep[b] (mask_c = C), img = out = img[b]) -- the kernels run the same device
+ * bodies; where keep == 0 the element keeps its bits and where keep == 1 it is q.  16-byte accesses where HW % 4 == 0 and x0,
+ * keep and img are 16-byte aligned, single floats otherwise: the same bits per element.  img aliases nothing, and nothing
+ * aliases blend_ab / blend_on / seeds / slot_start / slot_len.  MDX_E_INVALID (nothing launched): a NULL pointer, B <= 0 or
+ * > 65535, C <= 0, HW <= 0, C * HW > 2^34 (the generator's extent limit), cap <= 0, tick < 0. */
+int mdx_slot_blend_f32(const float* x0, const float* keep, float* img, const unsigned long long* seeds, unsigned stream,
+                       unsigned draw0, const float* blend_ab, const int* blend_on, const int* slot_start, const int* slot_len,
+                       int cap, int tick, int B, int C, int HW, mdx_stream_t s);
 
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):

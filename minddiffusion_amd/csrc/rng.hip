@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "mdx_common.h"
+#include "qsample_device.h"
 
 namespace {
 
@@ -153,6 +154,56 @@ void rng_launch(RngParams p, int B, hipStream_t s) {
 
 constexpr long RNG_MAX_N = 1L << 34;    // element >> 2 is the counter's 32-bit word 0
 
+// ------------------------------------------------------------------ per-slot mask blend (mdx_slot_blend_f32)
+// The blend at the top of a decode() iteration for the slots of a session: img = keep q + (1 - keep) img with
+// q = a x0 + b noise, the noise drawn here -- quad_values<MODE_NORMAL> at (stream, draw0 + pos_b), scale 1 -- and never stored.
+// r carries the generator's arguments (r.n = C * HW, r.draw = draw0, the slot tables, the tick).
+struct SlotBlendParams {
+    RngParams r;
+    const float* x0;        // [B][C][HW]
+    const float* keep;      // [B][C][HW]
+    float* img;             // [B][C][HW]
+    const float* blend_ab;  // [B][cap][2]
+    const int* blend_on;    // [B]
+    int cap;
+};
+
+// Items as rng_kernel's: V == 4 is quad i of sample b (HW % 4 == 0, so C * HW % 4 == 0, and the three tensors 16-byte aligned:
+// the host decides), V == 1 element i, lane (i & 3) of its quad.  A slot that is not active, or does not blend, is skipped:
+// nothing of its span is read or written.
+template <int V>
+__global__ __launch_bounds__(RNG_THREADS) void slot_blend_kernel(const SlotBlendParams p) {
+    const unsigned long long per = p.r.n / V;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * RNG_THREADS + threadIdx.x; j < p.r.items;
+         j += (unsigned long long)gridDim.x * RNG_THREADS) {
+        const unsigned long long b = j / per, i = j - b * per;
+        const int pos = mdx_slot_pos(p.r.slot_start, p.r.slot_len, (int)b, p.cap, p.r.tick);
+        if (pos < 0 || p.blend_on[b] == 0) continue;
+        const float* ab = p.blend_ab + ((size_t)b * p.cap + pos) * 2;
+        const float ca = ab[0], cb = ab[1];
+        const unsigned draw = p.r.draw + (unsigned)pos;
+        const unsigned long long seed = p.r.seeds[b];
+        const size_t at = (size_t)j * V;                        // == b * n + i * V
+        unsigned bits[4];
+        float nz[V], x[V], m[V], im[V];
+        if constexpr (V == 4) {
+            quad_values<MODE_NORMAL>(p.r, seed, draw, (unsigned)i, bits);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) nz[e] = __uint_as_float(bits[e]);
+        } else {
+            quad_values<MODE_NORMAL>(p.r, seed, draw, (unsigned)(i >> 2), bits);
+            const int lane = (int)(i & 3);
+            nz[0] = __uint_as_float(lane == 0 ? bits[0] : lane == 1 ? bits[1] : lane == 2 ? bits[2] : bits[3]);
+        }
+        load_v<V>(p.x0 + at, x);
+        load_v<V>(p.keep + at, m);
+        load_v<V>(p.img + at, im);
+#pragma unroll
+        for (int e = 0; e < V; ++e) im[e] = blend_f(m[e], q_sample_f(x[e], nz[e], ca, cb), im[e]);
+        store_v<V>(p.img + at, im);
+    }
+}
+
 }  // namespace
 
 extern "C" int mdx_philox_u32(const unsigned long long* seeds, unsigned stream, unsigned draw, unsigned* out, int B, long n,
@@ -210,5 +261,34 @@ extern "C" int mdx_randn_slots_f32(const unsigned long long* seeds, unsigned str
     else
         rng_launch<MODE_NORMAL, true>(p, B, (hipStream_t)s);
     MDX_LAUNCH_CHECK("mdx_randn_slots_f32");
+    return MDX_OK;
+}
+
+extern "C" int mdx_slot_blend_f32(const float* x0, const float* keep, float* img, const unsigned long long* seeds,
+                                  unsigned stream, unsigned draw0, const float* blend_ab, const int* blend_on,
+                                  const int* slot_start, const int* slot_len, int cap, int tick, int B, int C, int HW,
+                                  mdx_stream_t s) {
+    const char* fn = "mdx_slot_blend_f32";
+    MDX_REQUIRE(x0 && keep && img && seeds && blend_ab && blend_on && slot_start && slot_len, "%s: null pointer", fn);
+    MDX_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long long)C * HW <= RNG_MAX_N,
+                "%s: bad extents (B=%d C=%d HW=%d; 0 < B <= 65535, 0 < C * HW <= 2^34)", fn, B, C, HW);
+    MDX_REQUIRE(cap > 0 && tick >= 0, "%s: bad slot extents (cap=%d tick=%d; cap > 0, tick >= 0)", fn, cap, tick);
+    SlotBlendParams p;
+    p.r.seeds = seeds; p.r.out = nullptr;
+    p.r.stream = stream; p.r.draw = draw0;
+    p.r.scale = 1.0f; p.r.dropout_p = 0.0f; p.r.inv_keep = 1.0f;
+    p.r.n = (unsigned long long)C * HW; p.r.items = 0;
+    p.r.slot_start = slot_start; p.r.slot_len = slot_len; p.r.tick = tick;
+    p.x0 = x0; p.keep = keep; p.img = img;
+    p.blend_ab = blend_ab; p.blend_on = blend_on;
+    p.cap = cap;
+    if (HW % 4 == 0 && aligned16(x0) && aligned16(keep) && aligned16(img)) {
+        p.r.items = (unsigned long long)B * (p.r.n / 4);
+        hipLaunchKernelGGL(slot_blend_kernel<4>, dim3(rng_blocks(p.r.items)), dim3(RNG_THREADS), 0, (hipStream_t)s, p);
+    } else {
+        p.r.items = (unsigned long long)B * p.r.n;
+        hipLaunchKernelGGL(slot_blend_kernel<1>, dim3(rng_blocks(p.r.items)), dim3(RNG_THREADS), 0, (hipStream_t)s, p);
+    }
+    MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
 }

@@ -8,8 +8,9 @@ Three layers:
   * SlotScheduler       which request sits in which slot on which tick: a FIFO into the lowest free slot.  It mirrors every
                         slot's position by counting and never reads the device.
   * SamplingSession     the device state (written only when a request is admitted) and the launches of one tick:
-                        ops.slot_gather, the two x copies into the guidance batch, the UNet, ops.randn_slots where some active
-                        slot draws noise, ops.sampler_step_slots in place.
+                        ops.slot_blend where some active slot blends (an img2img request with a keep_mask), ops.slot_gather,
+                        the two x copies into the guidance batch, the UNet, ops.randn_slots where some active slot draws
+                        noise, ops.sampler_step_slots in place.
 """
 import collections
 
@@ -26,28 +27,62 @@ SAMPLERS = ("ddim", "dpm_solver")
 _REFUSED_KEYWORDS = ("mask", "x0", "score_corrector", "quantize_x0")
 
 
-def request_rows(model, sampler, steps, scale, guidance_rescale=0.0, eta=0.0):
-    """(rows [steps, ops.STEP_ROW] float32, t_input [steps] float32) of one request: the rows a StepTable holds for it served
+def _dpm_start(sampler_obj, steps, t_enc):
+    """The continuous time the last t_enc of `steps` DPM-Solver steps begin at (DiffusionPipeline._partial_start)."""
+    t_0 = 1.0 / sampler_obj.alphas_cumprod.shape[0]
+    return t_0 + (1.0 - t_0) * t_enc / steps
+
+
+def request_rows(model, sampler, steps, scale, guidance_rescale=0.0, eta=0.0, t_enc=None):
+    """(rows [n, ops.STEP_ROW] float32, t_input [n] float32) of one request: the rows a StepTable holds for it served
     as a batch of one -- built by the samplers' own _step_table, so by ddim_step_scalars / PLMS_AB[0] or dpm_step_scalars /
     dpm_model_point, and validated by StepTable.host() (finite, phi in [0, 1], sqrt_at != 0) -- and the model-input timestep of
-    every evaluation.  `model` needs what a sampler reads before it touches the device (the schedule arrays)."""
+    every evaluation.  `model` needs what a sampler reads before it touches the device (the schedule arrays).
+    t_enc None: the full run, n = steps.  Otherwise the partial run of an img2img request, n = t_enc: the last t_enc steps of
+    the `steps`-step schedule, as decode(t_start=t_enc) (DDIM) or sample(S=t_enc, t_start=) (DPM-Solver) walk them."""
+    n = steps if t_enc is None else int(t_enc)
+    if not 1 <= n <= steps:
+        raise ValueError(f"t_enc must be an integer in [1, {steps}] (the model evaluations that remain), got {t_enc!r}")
     if sampler == "ddim":
         from .ddim import DDIMSampler
         s = DDIMSampler(model)
         s.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)      # IndexError: no grid for this step count
-        table, t_rows, total = s._step_table([s._time_grid(False, None, None)], [scale], [guidance_rescale], True)
+        table, t_rows, total = s._step_table([s._time_grid(False, None, t_enc)], [scale], [guidance_rescale], True)
     elif sampler == "dpm_solver":
         from .dpm_solver import DPMSolverSampler
         from .dpm_solver.dpm_solver import NoiseScheduleVP
         if eta != 0.0:
             raise ValueError("eta: DPM-Solver draws no step noise, eta must be 0")
-        ns = NoiseScheduleVP("discrete", alphas_cumprod=DPMSolverSampler(model).alphas_cumprod)
-        table, t_rows, total = DPMSolverSampler._step_table(ns, [steps], [scale], [guidance_rescale], True)
+        d = DPMSolverSampler(model)
+        ns = NoiseScheduleVP("discrete", alphas_cumprod=d.alphas_cumprod)
+        table, t_rows, total = DPMSolverSampler._step_table(ns, [n], [scale], [guidance_rescale], True,
+                                                            t_start=None if t_enc is None else _dpm_start(d, steps, n))
     else:
         raise ValueError(f"sampler must be one of {SAMPLERS} in a session, got {sampler!r}")
     rows = table.host()[:, 0]
-    assert rows.shape == (steps, ops.STEP_ROW) and total == steps
+    assert rows.shape == (n, ops.STEP_ROW) and total == n
     return np.ascontiguousarray(rows), np.ascontiguousarray(t_rows[:, 0], dtype=np.float32)
+
+
+def start_coefficients(model, sampler, steps, t_enc, eta=0.0):
+    """(a, b) of x = a z0 + b noise at the level an img2img request starts from: the sampler's own q_coefficients at the start
+    DiffusionPipeline._partial_start selects (grid index t_enc of the `steps`-step schedule; for DPM-Solver the continuous time)."""
+    if sampler == "ddim":
+        from .ddim import DDIMSampler
+        s = DDIMSampler(model)
+        s.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
+        return s.q_coefficients(t_enc)
+    from .dpm_solver import DPMSolverSampler
+    d = DPMSolverSampler(model)
+    return d.q_coefficients(_dpm_start(d, steps, t_enc))
+
+
+def blend_coefficients(model, t_input):
+    """[n, 2] float32: (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) at the integer model-input timestep of every
+    position -- the sampler's make_schedule arrays, so the values decode() hands ops.q_sample at the top of its iterations."""
+    ac = np.asarray(model.alphas_cumprod, dtype=np.float32)
+    t = np.asarray(t_input).astype(np.int64)
+    return np.ascontiguousarray(np.stack([np.sqrt(ac)[t], np.sqrt(1. - ac)[t]], axis=1), dtype=np.float32)
 
 
 def check_request(sampler, max_steps, steps, scale, guidance_rescale, eta, seed, **refused):
@@ -59,7 +94,8 @@ def check_request(sampler, max_steps, steps, scale, guidance_rescale, eta, seed,
             raise TypeError(f"submit() got an unexpected keyword argument {k!r}")
         if v is not None and v is not False:
             raise ValueError(f"submit: {k} is not available in a session: "
-                             + ("a request starts at its own first step, there is no blend against an init latent"
+                             + ("an img2img request takes init_latent= / init_image= (with strength=) and, for the blend, "
+                                "keep_mask="
                                 if k in ("mask", "x0") else "it leaves the fused step launch"))
     per_request([steps], [scale], [guidance_rescale], 1)                # an int >= 1, a finite scale, phi in [0, 1]
     steps, scale, guidance_rescale, eta = int(steps), float(scale), float(guidance_rescale), float(eta)
@@ -75,9 +111,52 @@ def check_request(sampler, max_steps, steps, scale, guidance_rescale, eta, seed,
     return steps, scale, guidance_rescale, eta, seed
 
 
+def _one_sample(name, t, dims, what):
+    """A tensor [*dims] or [1, *dims] (None in a dims entry: any extent) -> its [*dims] view."""
+    if not isinstance(t, torch.Tensor) or t.dim() not in (len(dims), len(dims) + 1) or (t.dim() > len(dims) and t.shape[0] != 1):
+        raise MdxError(f"submit: {name} must be a tensor {what}, got "
+                       f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    t = t.reshape(tuple(t.shape[-len(dims):]))
+    if any(d is not None and int(s) not in (d if isinstance(d, tuple) else (d,)) for s, d in zip(t.shape, dims)):
+        raise MdxError(f"submit: {name} has shape {tuple(t.shape)}, expected {what}")
+    return t
+
+
+def check_init(sampler, steps, shape, vae=None, init_latent=None, init_image=None, strength=None, keep_mask=None):
+    """The img2img keywords of SamplingSession.submit, checked: (t_enc, init_latent [C, h, w], init_image [3, H, W], keep_mask
+    [1 | C, h, w]), all None for a request that starts from noise.  steps: checked by check_request; shape: the session's latent
+    shape; vae: model.first_stage_model.  Validates and reshapes only: nothing is copied or moved."""
+    if init_latent is not None and init_image is not None:
+        raise ValueError("submit: pass at most one of init_latent and init_image")
+    if init_latent is None and init_image is None:
+        for k, v in (("strength", strength), ("keep_mask", keep_mask)):
+            if v is not None:
+                raise ValueError(f"submit: {k} needs an init (init_latent= or init_image=)")
+        return None, None, None, None
+    from ....pipeline import DiffusionPipeline
+    t_enc = DiffusionPipeline._check_strength("submit", 0.75 if strength is None else strength, steps)
+    C, h, w = shape
+    if keep_mask is not None:
+        if sampler == "dpm_solver":
+            raise NotImplementedError("submit: keep_mask: mask blending is implemented by PLMSSampler / DDIMSampler (a 'ddim' "
+                                      "session)")
+        keep_mask = _one_sample("keep_mask", keep_mask, ((1, C), h, w), f"[1 | {C}, {h}, {w}] (the latent resolution)")
+    if init_latent is not None:
+        init_latent = _one_sample("init_latent", init_latent, (C, h, w), f"[{C}, {h}, {w}] (the session's latent shape)")
+    else:
+        if vae is None or not hasattr(vae, "encode_noised"):
+            raise MdxError("submit: init_image= needs a VAE with an encoder attached (model.first_stage_model); pass init_latent=")
+        init_image = _one_sample("init_image", init_image, (3, None, None), "[3, H, W] in [-1, 1]")
+        got = tuple(vae.latent_shape((1,) + tuple(init_image.shape)))[1:]
+        if got != (C, h, w):
+            raise MdxError(f"submit: init_image {tuple(init_image.shape)} encodes to a latent {got}, the session's is {(C, h, w)}")
+    return t_enc, init_latent, init_image, keep_mask
+
+
 class Request:
     """One submitted request and, once it runs, where: `slot` and `start` (the session tick of its first model evaluation).
-    `latent` is the finished [C, H, W] latent (a device tensor) from the tick it ended on."""
+    `latent` is the finished [C, H, W] latent (a device tensor) from the tick it ended on.  `steps` is the number of ticks it
+    runs: its step count, or t_enc of an img2img request."""
 
     def __init__(self, index, steps, rows, t_input, payload=None):
         self.index, self.steps, self.rows, self.t_input, self.payload = index, int(steps), rows, t_input, payload
@@ -164,10 +243,15 @@ class SamplingSession:
     The guidance batch is always used: a scale of exactly 1.0 goes through the combine eu + 1 * (ec - eu).
     temperature / noise_dropout: of the eta > 0 step noise (DDIM), session-wide.
     empty: the [1, 77, D] encoding of the empty window, for contexts shorter than context_len (default: the attached text
-    encoder's)."""
+    encoder's).
+    img2img requests (submit(init_latent= | init_image=, strength=)) start at position 0 of the PARTIAL run: they hold their slot
+    for t_enc = int(strength * steps) ticks, from x[b] = a z0 + b noise.  With keep_mask= ('ddim' only) the slot also owns
+    x0[b], keep[b], blend_ab[b] and blend_on[b] -- made on the first such admission, written only on admissions -- and every tick
+    on which some active slot blends starts with one ops.slot_blend launch (the blend at the top of decode()'s iterations).
+    sample_posterior: whether init_image= requests sample the VAE posterior or take its mode."""
 
     def __init__(self, model, slots, H=512, W=512, sampler="ddim", context_len=WINDOW, max_steps=50, temperature=1.0,
-                 noise_dropout=0.0, device=None, empty=None):
+                 noise_dropout=0.0, device=None, empty=None, sample_posterior=True):
         if sampler == "plms":
             raise MdxError("SamplingSession: PLMS evaluates the model twice on a request's first step (plms.py:231-235), which "
                            "one shared evaluation per tick cannot give a newcomer alone: use 'ddim' or 'dpm_solver'")
@@ -215,14 +299,17 @@ class SamplingSession:
         # the noise term of the step: the seeded draw (DDIM, eta > 0), or the previous data prediction (DPM-Solver)
         self.noise = z(B, *self.shape) if sampler == "ddim" else None
         self.x0_bufs = [z(B, *self.shape), z(B, *self.shape)] if sampler == "dpm_solver" else None
+        self.sample_posterior = bool(sample_posterior)
+        self.x0 = self.keep = self.blend_ab = self.blend_on = None      # the blend state: made by the first keep_mask admission
         self.unet_evals = 0
         self.admissions = 0
+        self.blend_launches = 0
 
     # ---- host: submit never touches the device
-    def _rows(self, steps, scale, guidance_rescale, eta):
-        key = (steps, scale, guidance_rescale, eta)
+    def _rows(self, steps, scale, guidance_rescale, eta, t_enc=None):
+        key = (steps, scale, guidance_rescale, eta, t_enc)
         if key not in self._rows_cache:
-            self._rows_cache[key] = request_rows(self.model, self.sampler, steps, scale, guidance_rescale, eta)
+            self._rows_cache[key] = request_rows(self.model, self.sampler, steps, scale, guidance_rescale, eta, t_enc)
         return self._rows_cache[key]
 
     def _check_context(self, name, t):
@@ -244,11 +331,23 @@ class SamplingSession:
                            f"to pad it with: pass empty= to the session or attach a text encoder")
         return t
 
-    def submit(self, prompt=None, c=None, uc=None, steps=30, scale=7.5, guidance_rescale=0.0, eta=0.0, seed=0, **refused):
+    def submit(self, prompt=None, c=None, uc=None, steps=30, scale=7.5, guidance_rescale=0.0, eta=0.0, seed=0, init_latent=None,
+               init_image=None, strength=None, keep_mask=None, **refused):
         """Queue one request; returns its handle (Request).  prompt (with a text encoder attached; encoded when the request is
-        admitted) or c / uc tensors [T, D].  Never blocks and never touches the device."""
+        admitted) or c / uc tensors [T, D].  Never blocks and never touches the device.
+        img2img: init_latent [C, h, w] (already scaled by scale_factor) or init_image [3, H, W] in [-1, 1] (needs
+        model.first_stage_model), exactly one; strength in (0, 1], default 0.75: the request runs the last
+        t_enc = int(strength * steps) steps of its `steps`-step schedule and holds its slot for t_enc ticks.  keep_mask
+        [1 | C, h, w], 1 = keep the init latent there (img2img(mask=)'s meaning; 'ddim' sessions only).  Its draws -- the forward
+        noise (ops.RNG_ENCODE), the posterior noise of init_image (ops.RNG_POSTERIOR), the step and blend draws, both counted
+        from 0 at its first tick -- depend on `seed` alone.  An init_image is encoded at batch 1 when the request is ADMITTED:
+        the encoder runs between two ticks and stalls that tick for every slot.  (The first init_image of a size builds the
+        encoder's plan here, to learn its latent shape.)"""
         steps, scale, guidance_rescale, eta, seed = check_request(self.sampler, self.cap, steps, scale, guidance_rescale, eta,
                                                                   seed, **refused)
+        t_enc, init_latent, init_image, keep_mask = check_init(
+            self.sampler, steps, self.shape, getattr(self.model, "first_stage_model", None), init_latent, init_image, strength,
+            keep_mask)
         if (prompt is None) == (c is None):
             raise MdxError("submit: pass either prompt= or c= (and uc=)")
         if prompt is not None:
@@ -260,8 +359,17 @@ class SamplingSession:
             c, uc = self._check_context("c", c), self._check_context("uc", uc)
             if uc is None:
                 raise MdxError("submit: the guidance batch is always used in a session: pass uc= with c=")
-        rows, t_input = self._rows(steps, scale, guidance_rescale, eta)
-        return self.scheduler.submit(steps, rows, t_input, {"prompt": prompt, "c": c, "uc": uc, "seed": seed})
+        rows, t_input = self._rows(steps, scale, guidance_rescale, eta, t_enc)
+        payload = {"prompt": prompt, "c": c, "uc": uc, "seed": seed, "t_enc": t_enc, "z0": init_latent, "image": init_image,
+                   "keep": keep_mask}
+        if t_enc is not None:
+            key = ("start", steps, t_enc, eta)
+            if key not in self._rows_cache:
+                self._rows_cache[key] = tuple(float(v) for v in start_coefficients(self.model, self.sampler, steps, t_enc, eta))
+            payload["ab"] = self._rows_cache[key]
+        if keep_mask is not None:
+            payload["blend_ab"] = blend_coefficients(self.model, t_input)
+        return self.scheduler.submit(len(rows), rows, t_input, payload)
 
     def step(self):
         """One tick.  Returns [(handle, latent [C, H, W])] of the requests that ended on it."""
@@ -304,14 +412,52 @@ class SamplingSession:
         self.context[b].copy_(uc[0], non_blocking=True)         # in place: the UNet's context cache sees the version change
         self.context[B + b].copy_(c[0], non_blocking=True)
         self.seeds[b:b + 1].copy_(torch.tensor([p["seed"]], dtype=torch.int64), non_blocking=True)
-        ops.randn_seeded(self.seeds[b:b + 1], ops.RNG_X_T, 0, self.shape, out=self.x[b:b + 1])
+        if p.get("t_enc") is None:
+            ops.randn_seeded(self.seeds[b:b + 1], ops.RNG_X_T, 0, self.shape, out=self.x[b:b + 1])
+        else:
+            self._admit_init(b, req)
+        if self.blend_on is not None:
+            self.blend_on[b:b + 1].copy_(torch.tensor([int(p.get("keep") is not None)], dtype=torch.int32), non_blocking=True)
         self.sched[b, :req.steps].copy_(torch.from_numpy(req.rows), non_blocking=True)
         self.temb[b, :req.steps].copy_(self.model.time_embedding_table(torch.from_numpy(req.t_input).to(dev)))
         self.slot_meta[:, b].copy_(torch.tensor([tick, req.steps], dtype=torch.int32), non_blocking=True)
         self.admissions += 1
 
+    def _admit_init(self, b, req):
+        """The start latent of an img2img request, x[b] = a z0 + b randn(seed, RNG_ENCODE, 0) -- noised_latent's two launches on
+        the one-row view, or for an image the encoder at batch 1 and its fused launch -- and, with a keep_mask, the slot's blend
+        state."""
+        p, dev = req.payload, self.device
+        a, bb = p["ab"]
+        row = self.x[b:b + 1]
+        noise = ops.randn_seeded(self.seeds[b:b + 1], ops.RNG_ENCODE, 0, self.shape)
+        if p["image"] is not None:
+            post = ops.randn_seeded(self.seeds[b:b + 1], ops.RNG_POSTERIOR, 0, self.shape) if self.sample_posterior else None
+            image = p["image"].to(device=dev, dtype=torch.float32)[None].contiguous()
+            z0, x_enc = self.model.first_stage_model.encode_noised(image, self.model.scale_factor, a, bb, noise, post_noise=post,
+                                                                   sample=self.sample_posterior)
+            row.copy_(x_enc)
+        else:
+            z0 = p["z0"].to(device=dev, dtype=torch.float32)[None].contiguous()
+            ops.q_sample(z0, noise, a, bb, out=row)
+        if p["keep"] is None:
+            return
+        if self.blend_on is None:
+            z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+            self.x0, self.keep = z(self.B, *self.shape), z(self.B, *self.shape)
+            self.blend_ab, self.blend_on = z(self.B, self.cap, 2), z(self.B, dtype=torch.int32)
+        self.x0[b].copy_(z0[0])
+        self.keep[b].copy_(p["keep"].to(device=dev, dtype=torch.float32).expand(self.shape))
+        self.blend_ab[b, :req.steps].copy_(torch.from_numpy(p["blend_ab"]), non_blocking=True)
+
     def tick(self, tick, any_noise, any_rescale):
         B = self.B
+        # whether some active slot blends: from the requests held, by counting, as the scheduler finds any_noise
+        if any(r is not None and r.payload.get("keep") is not None and 0 <= tick - r.start < r.steps
+               for r in self.scheduler.slots):
+            ops.slot_blend(self.x0, self.keep, self.x, self.seeds, ops.RNG_BLEND, 0, self.blend_ab, self.blend_on,
+                           self.slot_start, self.slot_len, tick)
+            self.blend_launches += 1
         ops.slot_gather(self.temb, self.slot_start, self.slot_len, tick, self.emb, reps=2)
         self.x_in[:B].copy_(self.x)
         self.x_in[B:].copy_(self.x)

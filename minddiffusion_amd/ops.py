@@ -1201,6 +1201,31 @@ def randn_slots(seeds, stream, draw0, slot_start, slot_len, tick, out, scale=1.0
     return out
 
 
+def slot_blend(x0, keep, img, seeds, stream, draw0, blend_ab, blend_on, slot_start, slot_len, tick):
+    """The mask blend of decode()'s iterations per session slot, in place and in one launch: for every slot b that is active at
+    `tick` and has blend_on[b] != 0, img[b] = keep[b] * q + (1 - keep[b]) * img[b] with q = a * x0[b] + b * noise, (a, b) =
+    blend_ab[b, pos_b] and the noise drawn inside the kernel -- the bits of randn_seeded(seeds[b:b+1], stream, draw0 + pos_b)
+    followed by q_sample(x0[b], noise, a, b, out=img[b], mask=keep[b], img=img[b]).  The other slots' rows of img are not
+    touched.  x0, keep, img [B, C, H, W] fp32; blend_ab [B, cap, 2] fp32; blend_on [B] int32."""
+    _chk(x0, f32, "x0"); _chk(keep, f32, "keep"); _chk(img, f32, "img"); _chk(blend_ab, f32, "blend_ab")
+    _chk(seeds, torch.int64, "seeds"); _chk(blend_on, torch.int32, "blend_on")
+    if img.dim() != 4:
+        raise _lib.MdxError(f"slot_blend: img must be [B, C, H, W], got {tuple(img.shape)}")
+    B, C, H, W = (int(d) for d in img.shape)
+    _same_shape(img, "x0", x0); _same_shape(img, "keep", keep)
+    if blend_ab.dim() != 3 or blend_ab.shape[0] != B or blend_ab.shape[2] != 2:
+        raise _lib.MdxError(f"slot_blend: blend_ab must be [{B}, cap, 2], got {tuple(blend_ab.shape)}")
+    if tuple(seeds.shape) != (B,) or tuple(blend_on.shape) != (B,):
+        raise _lib.MdxError(f"slot_blend: seeds and blend_on must be [{B}], got {tuple(seeds.shape)}, {tuple(blend_on.shape)}")
+    _chk_slots(B, slot_start, slot_len)
+    if not (0 <= int(stream) < (1 << 31) and 0 <= int(draw0) < (1 << 32)):
+        raise _lib.MdxError(f"slot_blend: stream must be in [0, 2^31) and draw0 in [0, 2^32), got {stream!r}, {draw0!r}")
+    _lib.check(_lib.load().mdx_slot_blend_f32(_ptr(x0), _ptr(keep), _ptr(img), _ptr(seeds), int(stream), int(draw0),
+                                              _ptr(blend_ab), _ptr(blend_on), _ptr(slot_start), _ptr(slot_len),
+                                              int(blend_ab.shape[1]), int(tick), B, C, H * W, _stream()), "mdx_slot_blend_f32")
+    return img
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Row-local fused SpatialTransformer tail (include/mdx.h: mdx_st_tail_f16, csrc/stchain.hip)
 def pack_frag_weight(w2d):

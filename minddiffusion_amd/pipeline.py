@@ -245,17 +245,19 @@ class DiffusionPipeline:
                        f"{type(self.sampler).__name__})")
 
     def session(self, slots=4, H=512, W=512, sampler=None, context_len=WINDOW, max_steps=50, temperature=1.0,
-                noise_dropout=0.0, empty=None):
+                noise_dropout=0.0, empty=None, sample_posterior=True):
         """A SamplingSession on this pipeline's model: `slots` samples of one latent shape whose requests come and go
-        (submit / step / run_until_idle).  sampler: 'ddim' or 'dpm_solver' (default: the pipeline's; PLMS is refused)."""
+        (submit / step / run_until_idle).  sampler: 'ddim' or 'dpm_solver' (default: the pipeline's; PLMS is refused).
+        sample_posterior: whether submit(init_image=) requests sample the VAE posterior or take its mode."""
         from .ldm.models.diffusion.session import SamplingSession
         return SamplingSession(self.model, slots, H=H, W=W, sampler=sampler or self._session_sampler(),
                                context_len=context_len, max_steps=max_steps, temperature=temperature,
-                               noise_dropout=noise_dropout, device=self.device, empty=empty)
+                               noise_dropout=noise_dropout, device=self.device, empty=empty, sample_posterior=sample_posterior)
 
     def serve(self, requests, slots=4, H=512, W=512, output="float", sampler=None, temperature=1.0, noise_dropout=0.0,
               empty=None):
-        """Drain a list of requests -- dicts of SamplingSession.submit's keywords -- through one session of `slots` slots;
+        """Drain a list of requests -- dicts of SamplingSession.submit's keywords, the img2img ones (init_latent / init_image,
+        strength, keep_mask) included -- through one session of `slots` slots;
         the results come back in REQUEST order, whatever order they finished in.  output: 'latent' [N, 4, H/8, W/8]; 'float'
         [N, 3, H, W] in [0, 1], what __call__(decode=True) returns; 'uint8' [N, H, W, 3], truncated as inpaint.py:112-115."""
         if output not in ("latent", "float", "uint8"):
