@@ -764,6 +764,38 @@ int mdx_slot_blend_f32(const float* x0, const float* keep, float* img, const uns
                        unsigned draw0, const float* blend_ab, const int* blend_on, const int* slot_start, const int* slot_len,
                        int cap, int tick, int B, int C, int HW, mdx_stream_t s);
 
+/* ---- Windowed UNet evaluation (not in the reference; MultiDiffusion, Bar-Tal et al. 2023; csrc/window.hip): a latent canvas
+ * larger than the resolution the UNet was trained at is evaluated as a batch of overlapping windows of that resolution, and the
+ * outputs are averaged where windows overlap.
+ * The window grid: per axis of canvas length L, window w and stride s the offsets are 0, s, 2s, ... while o + w < L, then a last
+ * offset L - w (clamped, not padded); L == w has the single offset 0.  Window k = iy * nx + ix sits at (oy[iy], ox[ix]).  The
+ * offsets are one int32 table [ny + nx], rows then columns, passed twice: `offsets` on the device (the kernels read it) and
+ * `offsets_host`, the same values in host memory (checked before any launch; the kernels clamp what they read into the canvas).
+ * Both entries refuse, before any launch (MDX_E_INVALID): null pointers, non-positive extents, h > Hc or w > Wc, an offset that
+ * leaves the canvas (o < 0 or o + w > L), an axis whose offsets do not ascend from 0 to L - w or leave pixels uncovered (a step
+ * larger than the window), an output that overlaps the input.
+ *
+ * gather: windows k0 .. k0 + n - 1 of canvas NCHW fp32 [NB][C][Hc][Wc] (C counts every input channel, c_concat included) into out
+ * NCHW fp32 [NB * n][C][h][w]; window kk of canvas row j is output row j * n + kk, so a [uncond ; cond] canvas batch gives a
+ * [uncond ; cond] window batch.  A copy: 16 bytes per lane when w, Wc and every x-offset of the range are multiples of 4 and both
+ * bases are 16-byte aligned, single floats otherwise -- the same bits.  Also refused: a range outside [0, ny * nx).  Only the
+ * NB * n output rows are written. */
+int mdx_window_gather_f32(const float* canvas, float* out, const int* offsets, const int* offsets_host, int ny, int nx, int k0,
+                          int n, int NB, int C, int Hc, int Wc, int h, int w, mdx_stream_t s);
+/* average: windows NHWC fp16 [NB * N][h * w][ld], N = ny * nx, row j * N + k (the gather's order with n = N) onto out NHWC fp16
+ * [NB][Hc * Wc][ld].  One lane owns 8 halves (one 16-byte access; ld == 8: one canvas pixel) and visits the windows that cover
+ * its pixel in ascending k; every output element has one writer, no atomics.  Per channel c < C, with e_k the window's fp16 value:
+ *   weights == NULL:  acc = (float)e_k0;  acc += (float)e_k for each further window (plain fp32 adds);
+ *                     out = fp16_rne(acc / (float)count)                                   (IEEE fp32 division)
+ *   weights [h * w] fp32, all > 0 (n_weights == h * w), indexed by the pixel's place inside the window:
+ *                     acc = w_k0 * e_k0;  acc = fmaf(w_k, e_k, acc);  wsum = w_k0 + w_k + ... (plain adds);
+ *                     out = fp16_rne(acc / wsum)
+ * A pixel covered by ONE window takes that window's halves unchanged, in both forms.  Channels [C, ld) of out are written 0.
+ * Also refused: ld < C or ld % 8 != 0, windows / out not 16-byte aligned, weights with n_weights <= 0 or != h * w. */
+int mdx_window_average_f16(const void* windows, void* out, const float* weights, int n_weights, const int* offsets,
+                           const int* offsets_host, int ny, int nx, int NB, int C, int ld, int Hc, int Wc, int h, int w,
+                           mdx_stream_t s);
+
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
  *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)

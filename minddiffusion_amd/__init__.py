@@ -8,6 +8,8 @@ denoising hot path.  The package mirrors the reference's module layout for that 
     minddiffusion_amd.pipeline.DiffusionPipeline                 (reference: txt2img.py main loop)
     minddiffusion_amd.SamplingSession                            (new: requests join and leave a running UNet batch;
                                                                   ldm/models/diffusion/session.py, DiffusionPipeline.session)
+    minddiffusion_amd.WindowedDiffusion                          (new: overlapping-window UNet evaluation on large canvases;
+                                                                  ldm/models/diffusion/windowed.py, DiffusionPipeline.windowed)
 
 All arithmetic runs in hand-written HIP kernels (minddiffusion_amd/csrc -> libmdx.so, C-ABI in
 include/mdx.h).  There is no CPU fallback anywhere in the package.
@@ -19,4 +21,7 @@ def __getattr__(name):      # on first use: importing the package stays free of 
     if name == "SamplingSession":
         from .ldm.models.diffusion.session import SamplingSession
         return SamplingSession
+    if name == "WindowedDiffusion":
+        from .ldm.models.diffusion.windowed import WindowedDiffusion
+        return WindowedDiffusion
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

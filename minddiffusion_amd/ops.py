@@ -1124,6 +1124,101 @@ def inpaint_composite(decoded, image=None, alpha=None, output="float", out_f32=N
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Windowed UNet evaluation (include/mdx.h: mdx_window_gather_f32 / mdx_window_average_f16, csrc/window.hip).
+def window_offsets(length, window, stride):
+    """The offsets of one axis: 0, s, 2s, ... while o + w < L, then a last window at L - w (clamped, not padded);
+    L == w: [0]."""
+    length, window, stride = int(length), int(window), int(stride)
+    if not 0 < window <= length:
+        raise _lib.MdxError(f"window_offsets: a window of {window} on an axis of {length}")
+    if not 0 < stride <= window:
+        raise _lib.MdxError(f"window_offsets: stride {stride} must be in [1, window = {window}] (a larger one leaves pixels "
+                            f"uncovered)")
+    offs = []
+    o = 0
+    while o + window < length:
+        offs.append(o)
+        o += stride
+    return offs + [length - window]
+
+
+class WindowGrid:
+    """The windows of one canvas: oy / ox (window_offsets per axis), window k = iy * nx + ix at (oy[iy], ox[ix]), and the
+    int32 table [ny + nx] both kernels read -- on the host from construction, on a device from the first on(device), once."""
+
+    def __init__(self, canvas_hw, window_hw, stride_hw):
+        (self.Hc, self.Wc), (self.h, self.w) = (int(v) for v in canvas_hw), (int(v) for v in window_hw)
+        self.oy = window_offsets(self.Hc, self.h, stride_hw[0])
+        self.ox = window_offsets(self.Wc, self.w, stride_hw[1])
+        self.ny, self.nx = len(self.oy), len(self.ox)
+        self.N = self.ny * self.nx
+        self.host = np.ascontiguousarray(np.asarray(self.oy + self.ox, dtype=np.int32))
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.host).to(device)
+        return self._dev[device]
+
+    def origin(self, k):
+        return self.oy[k // self.nx], self.ox[k % self.nx]
+
+    def coverage(self):
+        """[Hc, Wc] int64: how many windows cover each canvas pixel."""
+        cy, cx = np.zeros(self.Hc, np.int64), np.zeros(self.Wc, np.int64)
+        for o in self.oy:
+            cy[o:o + self.h] += 1
+        for o in self.ox:
+            cx[o:o + self.w] += 1
+        return cy[:, None] * cx[None, :]
+
+    def _host_ptr(self):
+        return ctypes.c_void_p(self.host.ctypes.data)
+
+
+def window_gather(canvas, grid, k0=0, n=None, out=None):
+    """Windows k0 .. k0 + n - 1 of canvas [NB, C, Hc, Wc] fp32 as [NB * n, C, h, w], window kk of canvas row j in output row
+    j * n + kk.  One launch."""
+    _chk(canvas, f32, "canvas"); _chk(out, f32, "out")
+    if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
+        raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
+    NB, C = int(canvas.shape[0]), int(canvas.shape[1])
+    k0 = int(k0)
+    n = grid.N - k0 if n is None else int(n)
+    if k0 < 0 or n < 1 or k0 + n > grid.N:
+        raise _lib.MdxError(f"window_gather: windows [{k0}, {k0} + {n}) are not inside the grid of {grid.ny} x {grid.nx}")
+    if out is None:
+        out = torch.empty((NB * n, C, grid.h, grid.w), dtype=f32, device=canvas.device)
+    elif tuple(out.shape) != (NB * n, C, grid.h, grid.w):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB * n, C, grid.h, grid.w)}")
+    _lib.check(_lib.load().mdx_window_gather_f32(_ptr(canvas), _ptr(out), _ptr(grid.on(canvas.device)), grid._host_ptr(), grid.ny,
+                                                 grid.nx, k0, n, NB, C, grid.Hc, grid.Wc, grid.h, grid.w, _stream()),
+               "mdx_window_gather_f32")
+    return out
+
+
+def window_average(windows, grid, C, out=None, weights=None):
+    """The outputs of ALL windows, NHWC fp16 [NB * N, h * w, ld] in window_gather's row order, averaged onto the canvas
+    [NB, Hc * Wc, ld] (include/mdx.h: the arithmetic is part of the contract).  weights: [h, w] fp32 > 0 on the device, None:
+    uniform.  Channels [C, ld) of the result are 0.  One launch."""
+    _chk(windows, f16, "windows"); _chk(out, f16, "out"); _chk(weights, f32, "weights")
+    if windows.dim() != 3 or windows.shape[0] % grid.N or windows.shape[1] != grid.h * grid.w:
+        raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {grid.N}, {grid.h * grid.w}, ld]")
+    NB, ld = int(windows.shape[0]) // grid.N, int(windows.shape[2])
+    if weights is not None and tuple(weights.shape) != (grid.h, grid.w):
+        raise _lib.MdxError(f"weights: shape {tuple(weights.shape)}, expected {(grid.h, grid.w)}")
+    if out is None:
+        out = torch.empty((NB, grid.Hc * grid.Wc, ld), dtype=f16, device=windows.device)
+    elif tuple(out.shape) != (NB, grid.Hc * grid.Wc, ld):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB, grid.Hc * grid.Wc, ld)}")
+    _lib.check(_lib.load().mdx_window_average_f16(_ptr(windows), _ptr(out), _ptr(weights), 0 if weights is None else weights.numel(),
+                                                  _ptr(grid.on(windows.device)), grid._host_ptr(), grid.ny, grid.nx, NB, int(C), ld,
+                                                  grid.Hc, grid.Wc, grid.h, grid.w, _stream()), "mdx_window_average_f16")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Per-sample seeded noise (include/mdx.h: mdx_philox_u32 / mdx_randn_f32, csrc/rng.hip).  `stream` says what a draw is for,
 # `draw` which one it is; these are the streams the samplers and the pipeline use (a stream is < 2^31: the top bit selects
 # the dropout decisions of the same stream).

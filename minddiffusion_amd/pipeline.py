@@ -235,6 +235,30 @@ class DiffusionPipeline:
             samples = D.gather_latents(samples)
         return samples
 
+    # ---- large canvases (ldm/models/diffusion/windowed.py): the UNet evaluated in overlapping windows of the trained size
+    def windowed(self, window=512, stride=None, weights=None, max_unet_batch=16):
+        """A new DiffusionPipeline on WindowedDiffusion(self.model, ...): the same sampler kind and device, all weights
+        shared.  On it __call__(..., H=512, W=2048), img2img, inpaint, session(H=, W=) and serve run as they do here, the UNet
+        evaluated per step on overlapping windows of the canvas and averaged where they overlap.  window / stride: IMAGE
+        pixels, ints or (H, W) pairs, multiples of 8 (stride None: half the window); weights: None or [window / 8] positive
+        latent-pixel weights (windowed.gaussian_weights); max_unet_batch: the largest UNet batch one chunk of windows makes."""
+        from .ldm.models.diffusion.windowed import WindowedDiffusion, _pair
+
+        def latent(v, name):
+            if v is None:
+                return None
+            a, b = _pair(v, name)
+            if a < 8 or b < 8 or a % 8 or b % 8:
+                raise MdxError(f"DiffusionPipeline.windowed: {name} is in image pixels, positive multiples of 8, got {v!r}")
+            return a // 8, b // 8
+        try:
+            kind = self._session_sampler()
+        except MdxError:
+            raise MdxError(f"DiffusionPipeline.windowed: the new pipeline gets a sampler of this one's kind, 'ddim', 'plms' or "
+                           f"'dpm_solver'; this one's is a {type(self.sampler).__name__}") from None
+        model = WindowedDiffusion(self.model, latent(window, "window"), latent(stride, "stride"), weights, max_unet_batch)
+        return DiffusionPipeline(model, kind, self.device)
+
     # ---- continuous batching (ldm/models/diffusion/session.py): requests join and leave a running UNet batch
     def _session_sampler(self):
         from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
