@@ -796,6 +796,47 @@ int mdx_window_average_f16(const void* windows, void* out, const float* weights,
                            const int* offsets_host, int ny, int nx, int NB, int C, int ld, int Hc, int Wc, int h, int w,
                            mdx_stream_t s);
 
+/* ---- Regions and wrap-around windows on the same canvas (csrc/window.hip; MultiDiffusion section 4.2 without bootstrapping).  The
+ * two entries above keep their behaviour; these two add a table of window numbers, masks per region, and `wrap_x`.
+ * wrap_x (0 | 1): with 1 a window at x-offset o covers canvas columns (o + i) mod Wc, i < w (w <= Wc), so the right and the left
+ * edge of the canvas lie inside one window.  The wrapped x offsets are 0, s, 2s, ... while o < Wc (nx = ceil(Wc / s)); rows never
+ * wrap.  Refused for a wrapped x axis: offsets that do not start at 0, do not ascend, step by more than w, a last offset >= Wc
+ * or with Wc - last > w.  Everything the two entries above refuse is refused here too, the x axis by the wrapped rule when
+ * wrap_x is 1; wrap_x other than 0 | 1 is refused.
+ *
+ * gather_rows: mdx_window_gather_f32 with the windows named by a table: rows[n] on the device, rows_host the same values on the
+ * host (checked: every entry in [0, ny * nx)).  Window numbers may repeat and come in any order; output row j * n + i is window
+ * rows[i] of canvas row j.  A copy: 16 bytes per lane when w, Wc and every x offset the rows use are multiples of 4 and both bases
+ * are 16-byte aligned (a float4 then never straddles the seam), single floats otherwise -- the same bits.  Only the NB * n output
+ * rows are written. */
+int mdx_window_gather_rows_f32(const float* canvas, float* out, const int* offsets, const int* offsets_host, int ny, int nx,
+                               const int* rows, const int* rows_host, int n, int wrap_x, int NB, int C, int Hc, int Wc, int h,
+                               int w, mdx_stream_t s);
+/* average_regions: the outputs of P (window, region) pairs, NHWC fp16 [NB * P][h * w][ld], row j * P + p, onto out NHWC fp16
+ * [NB][Hc * Wc][ld].  The pairs are sorted by window k, then region r: pair_window_host[P] (host only), pair_region[P] and the
+ * CSR index pair_first[N + 1] (the pairs of window k are [pair_first[k], pair_first[k + 1])), the last two on the device and
+ * on the host.  masks: device fp32 [R][Hc][Wc], finite, >= 0, their sum > 0 at every pixel, and region r active (paired) in every
+ * window that covers a pixel where M_r > 0 -- the caller's to guarantee (ops.RegionPlan does).  R == 0: no regions; masks and
+ * the pair tables are NULL, P == ny * nx, pair p is window p and M == 1.
+ *   out(p) = sum_r sum_{k covers p} q * e_{r,k}(p) / sum q,   q = M_r(p) * wt(p - origin_k),   wt == 1 without `weights`.
+ * One lane owns 8 halves of one canvas pixel; one writer per element, no atomics; the covering windows are visited in ascending
+ * k and the pairs of a window in ascending r.  The arithmetic, per channel c < C, is part of the contract:
+ *   a term with M_r(p) == 0 is skipped BEFORE its window row is read: whatever that row holds, NaN included, cannot reach p;
+ *   q = m without weights; with weights q = m * wt, one fp32 multiply;
+ *   first term: acc = q * e (fp32 multiply), qsum = q;  later terms: acc = fmaf(q, e, acc), qsum = qsum + q (plain fp32 add);
+ *   out = fp16_rne(acc / qsum), an IEEE fp32 division;  a pixel with exactly ONE term takes that term's halves unchanged.
+ * Channels [C, ld) are written 0.  With R == 0 and wrap_x == 0, or R == 1 and an all-ones mask, this is the arithmetic of
+ * mdx_window_average_f16 (1 * e and fmaf(1, e, acc) are its adds, qsum its count or weight sum) and the results are bit-equal.
+ * Also refused: ld < C or ld % 8 != 0, windows / out not 16-byte aligned or overlapping, weights with n_weights != h * w,
+ * P <= 0, R < 0; R == 0 with masks or P != ny * nx; R > 0 with a NULL mask or pair table, pair_first not running from 0 to P
+ * without descending, a pair whose window differs from its CSR slot, a region outside [0, R), regions of one window that do not
+ * ascend. */
+int mdx_window_average_regions_f16(const void* windows, void* out, const float* weights, int n_weights, const int* offsets,
+                                   const int* offsets_host, int ny, int nx, int wrap_x, const int* pair_window_host,
+                                   const int* pair_region, const int* pair_region_host, const int* pair_first,
+                                   const int* pair_first_host, int P, const float* masks, int R, int NB, int C, int ld, int Hc,
+                                   int Wc, int h, int w, mdx_stream_t s);
+
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
  *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)

@@ -210,6 +210,13 @@ class StepTable:
                                self.device_table[k], self.any_rescale[k] and out_u is not None)
 
 
+def use_cfg(uc, uc_cat, scale):
+    """Whether a run evaluates the guidance batch [uncond ; cond]: not without an unconditional context and an unconditional
+    c_concat, and not when the scale -- every scale of a per-request list -- is exactly 1.  GuidedModel's rule; whoever lays
+    out a context the way GuidedModel will (the pipeline's region contexts) asks this function."""
+    return not ((uc is None and uc_cat is None) or bool(np.all(np.asarray(scale) == 1.)))
+
+
 class GuidedModel:
     """The model call of step i on the guidance batch [uncond; cond] (plms.py:192-195): ``guided(x, i) -> (out_u, out_c)``,
     NHWC fp16 halves of one UNet output (out_u None without guidance).  Everything that does not change over the run is made
@@ -226,7 +233,7 @@ class GuidedModel:
 
     def __init__(self, model, b, shape, cond, uc, c_cat, uc_cat, scale, dev, t_steps):
         self.model, self.b, self.cx = model, b, shape[0]
-        self.use_cfg = not ((uc is None and uc_cat is None) or bool(np.all(np.asarray(scale) == 1.)))
+        self.use_cfg = use_cfg(uc, uc_cat, scale)
         nb = self.nb = 2 * b if self.use_cfg else b
         if cond is None:
             self.c_in = None

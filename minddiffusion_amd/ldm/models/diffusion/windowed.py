@@ -8,7 +8,15 @@ is a model wrapper: samplers, sessions and the pipeline reach the network throug
 DPM-Solver, v-prediction, guidance rescale, per-request lists and seeds, img2img and the mask blend, hybrid inpainting (its
 c_concat channels ride inside ``x`` and are windowed with it), LoRA and sampling sessions run on a large canvas unchanged.
 Two HIP launches per call surround the UNet (csrc/window.hip): ops.window_gather and ops.window_average.
+
+wrap_x: the windows wrap around the canvas' right edge into its left one (a 360-degree panorama: both edges lie inside one
+window).  ``with wm.regions(masks, contexts):`` gives every region of the canvas its own text context (MultiDiffusion section
+4.2 without bootstrapping): the UNet runs once per ACTIVE (window, region) pair and the outputs are averaged with the region
+masks as weights.  Both go through ops.window_gather_rows and ops.window_average_regions, one launch each, and change
+nothing in the UNet, the step kernels or the samplers.  Known cost: under guidance the unconditional half is evaluated once
+per pair, so the R regions of one window repeat the same unconditional evaluation.
 """
+import contextlib
 import weakref
 
 import numpy as np
@@ -57,11 +65,12 @@ def chunk_list(n_windows, canvas_batch, max_unet_batch):
 class WindowedDiffusion:
     """A LatentDiffusion evaluated in overlapping windows.  window / stride: latent pixels, ints or (h, w) pairs; stride None:
     half the window.  weights: None (the plain mean) or [h, w] positive weights (gaussian_weights) for feathered seams.
-    max_unet_batch (even): the largest UNet batch one chunk of windows may make.  Everything else -- the schedule arrays,
+    max_unet_batch (even): the largest UNet batch one chunk of windows may make.  wrap_x: windows wrap around the x axis (on a
+    canvas wider than the window; a narrower or equal one has nothing to wrap).  Everything else -- the schedule arrays,
     parameterization, unet, model.conditioning_key, time_embedding_table, the first and cond stage models, the LoRA calls --
     is the inner model's."""
 
-    def __init__(self, model, window=(64, 64), stride=None, weights=None, max_unet_batch=16):
+    def __init__(self, model, window=(64, 64), stride=None, weights=None, max_unet_batch=16, wrap_x=False):
         if isinstance(model, WindowedDiffusion):
             raise MdxError("WindowedDiffusion: the model is already windowed")
         key = getattr(getattr(model, "model", None), "conditioning_key", "crossattn")
@@ -95,12 +104,16 @@ class WindowedDiffusion:
         self.window, self.stride = (h, w), (sh, sw)
         self.weights = weights
         self.max_unet_batch = int(max_unet_batch)
-        self.chunks = []            # [(k0, n), ...] of the last windowed call
+        self.wrap_x = bool(wrap_x)
+        self.chunks = []            # [(k0, n), ...] of the last windowed call: ranges of windows, or of pairs (wrap_x / regions)
+        self.pairs = []             # [(k, r), ...] the UNet rows of the last wrapped or region call; r None without regions
         self.grid = None            # ops.WindowGrid of the last windowed call
         self.evals = 0              # windowed calls (a single-window call forwards and does not count)
         self.context_refreshes = 0  # in-place refreshes of a per-window context repeat
         self._grids, self._bufs, self._ctx = {}, {}, {}
         self._weights_dev = None
+        self._regions = None        # inside `with regions(...)`: {"plan", "contexts", "rows"}
+        self._rows, self._rctx = {}, {}
 
     def __getattr__(self, name):    # (only reached for what the wrapper does not define)
         if name == "inner":
@@ -113,8 +126,44 @@ class WindowedDiffusion:
         key = (int(Hc), int(Wc))
         if key not in self._grids:
             h, w = min(self.window[0], key[0]), min(self.window[1], key[1])
-            self._grids[key] = ops.WindowGrid(key, (h, w), (min(self.stride[0], h), min(self.stride[1], w)))
+            self._grids[key] = ops.WindowGrid(key, (h, w), (min(self.stride[0], h), min(self.stride[1], w)),
+                                              wrap_x=self.wrap_x and key[1] > w)
         return self._grids[key]
+
+    # ---- regions: a mask over the canvas and a text context each
+    @contextlib.contextmanager
+    def regions(self, masks, contexts):
+        """Inside the block every model call evaluates R regions: masks [R, Hc, Wc] (fp32, finite, >= 0, their sum > 0 at every
+        pixel) for the canvas shape that will be called, contexts a list of R tensors in the model call's OWN row layout
+        [NB, T, D] -- what the sampler hands over as `cond`; under guidance cat([uc, c_r]) -- so the wrapper never guesses
+        which rows are unconditional.  A call whose cond differs from them in rows, T, D, dtype or device, or whose canvas
+        has another shape, is an MdxError.  Outside the block the wrapper is what it is without it."""
+        if self._regions is not None:
+            raise MdxError("WindowedDiffusion.regions: already inside a regions block")
+        masks = torch.as_tensor(masks)
+        if masks.dim() != 3:
+            raise MdxError(f"WindowedDiffusion.regions: masks have shape {tuple(masks.shape)}, expected [R, Hc, Wc]")
+        contexts = list(contexts)
+        if len(contexts) != int(masks.shape[0]) or not contexts:
+            raise MdxError(f"WindowedDiffusion.regions: {len(contexts)} contexts for {int(masks.shape[0])} masks")
+        first = contexts[0]
+        for r, c in enumerate(contexts):
+            if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dim() == 3):
+                raise MdxError(f"WindowedDiffusion.regions: context {r} must be a CUDA(HIP) tensor [NB, T, D]")
+            if tuple(c.shape) != tuple(first.shape) or c.dtype != first.dtype or c.device != first.device:
+                raise MdxError(f"WindowedDiffusion.regions: context {r} is {tuple(c.shape)} {c.dtype} on {c.device}, context 0 "
+                               f"{tuple(first.shape)} {first.dtype} on {first.device} (bring them to one length with "
+                               f"encoders.pad_conditioning)")
+        Hc, Wc = int(masks.shape[1]), int(masks.shape[2])
+        g = self.grid_for(Hc, Wc)
+        if self.weights is not None and (g.h, g.w) != self.window:
+            raise MdxError(f"WindowedDiffusion: the weights are for {self.window} windows, a {Hc}x{Wc} canvas clips them to "
+                           f"{(g.h, g.w)}")
+        self._regions = {"plan": ops.RegionPlan(g, masks), "contexts": contexts}
+        try:
+            yield self
+        finally:
+            self._regions = None
 
     def _in_bufs(self, x, n):
         """The UNet input batch and timestep rows of a chunk of n windows."""
@@ -153,6 +202,100 @@ class WindowedDiffusion:
         self.context_refreshes += 1
         return ent["buf"]
 
+    def _chunk_rows(self, g, plan, p0, n):
+        """The ops.WindowRows of pairs p0 .. p0 + n - 1 (their window numbers), made once per plan and range."""
+        key = (id(g) if plan is None else id(plan), p0, n)
+        ent = self._rows.get(key)
+        if ent is None or ent[0] is not (g if plan is None else plan):      # (the owner is kept: ids are reused)
+            windows = range(p0, p0 + n) if plan is None else plan.pair_window.host[p0:p0 + n]
+            if len(self._rows) > 64:
+                self._rows.clear()
+            ent = self._rows[key] = (g if plan is None else plan, ops.WindowRows(windows))
+        return ent[1]
+
+    def _region_context(self, cond, p0, n):
+        """The context buffer [NB * n, T, D] of pairs p0 .. p0 + n - 1, row j * n + i = contexts[pair_region[p0 + i]][j]: one
+        persistent buffer per chunk, refreshed in place only when one of the chunk's region tensors (the object or its version
+        counter) changes -- the rule of _context, over all the regions of the chunk."""
+        reg = self._regions
+        ctxs, first = reg["contexts"], reg["contexts"][0]
+        if not (isinstance(cond, torch.Tensor) and tuple(cond.shape) == tuple(first.shape) and cond.dtype == first.dtype
+                and cond.device == first.device):
+            what = (f"{tuple(cond.shape)} {cond.dtype} on {cond.device}" if isinstance(cond, torch.Tensor) else repr(cond))
+            raise MdxError(f"WindowedDiffusion.regions: the call's cond is {what}, the region contexts are "
+                           f"{tuple(first.shape)} {first.dtype} on {first.device} (rows, T, D, dtype and device must agree)")
+        ids = tuple(int(r) for r in reg["plan"].pair_region.host[p0:p0 + n])
+        used = sorted(set(ids))
+        key = (ids,) + tuple((ctxs[r].data_ptr(), ctxs[r]._version) for r in used)
+        ent = self._rctx.get((p0, n))
+        if ent is not None and ent["key"] == key and all(ref() is ctxs[r] for ref, r in zip(ent["refs"], used)):
+            return ent["buf"]
+        NB = int(first.shape[0])
+        shape = (NB * n,) + tuple(first.shape[1:])
+        if ent is None or tuple(ent["buf"].shape) != shape or ent["buf"].dtype != first.dtype or ent["buf"].device != first.device:
+            ent = self._rctx[(p0, n)] = {"buf": torch.empty(shape, dtype=first.dtype, device=first.device)}
+        view = ent["buf"].view((NB, n) + tuple(first.shape[1:]))
+        for i, r in enumerate(ids):
+            view[:, i].copy_(ctxs[r])
+        ent["key"], ent["refs"] = key, [weakref.ref(ctxs[r]) for r in used]
+        self.context_refreshes += 1
+        return ent["buf"]
+
+    def _chunk_kw(self, buf, temb, NB, n, device):
+        """The temb keyword of a chunk of n rows per canvas row: per-sample rows repeated, one row handed on as it is."""
+        if temb is None:
+            return {}
+        if temb.dim() != 2:
+            return {"temb": temb}             # one row: it broadcasts over any batch
+        if "temb" not in buf or buf["temb"].shape[1] != temb.shape[1]:
+            buf["temb"] = torch.empty((NB * n, temb.shape[1]), dtype=temb.dtype, device=device)
+        buf["temb"].view(NB, n, -1).copy_(temb[:, None, :].expand(NB, n, temb.shape[1]))
+        return {"temb": buf["temb"]}
+
+    def _apply_pairs(self, x, t, cond, temb, cfg_dup, g):
+        """The wrapped and the region form of the call: the UNet rows are pairs -- (window, region), or the windows of a
+        wrapped grid -- cut into chunks of at most max_unet_batch // NB pairs; per chunk ops.window_gather_rows, the chunk's
+        context buffer and the inner model with the caller's cfg_dup (row order j * n + i keeps the [uncond ; cond] halves
+        identical inputs); then ONE ops.window_average_regions launch over all pairs."""
+        NB = int(x.shape[0])
+        reg = self._regions
+        plan = None if reg is None else reg["plan"]
+        if plan is not None and plan.grid is not g:
+            raise MdxError(f"WindowedDiffusion.regions: the masks are for a {plan.grid.Hc}x{plan.grid.Wc} canvas, the call is on "
+                           f"{g.Hc}x{g.Wc}")
+        P = g.N if plan is None else plan.P
+        self.grid = g
+        self.pairs = [(k, None) for k in range(g.N)] if plan is None else list(plan.pairs)
+        self.chunks = chunk_list(P, NB, self.max_unet_batch)
+        stage = None
+        for p0, n in self.chunks:
+            buf = self._in_bufs(x, n)
+            ops.window_gather_rows(x, g, self._chunk_rows(g, plan, p0, n), out=buf["x"])
+            buf["t"].view(NB, n).copy_(t.reshape(NB, 1).expand(NB, n))
+            ctx = self._context(cond, n) if plan is None else self._region_context(cond, p0, n)
+            e = self.inner.apply_model_nhwc(buf["x"], buf["t"], ctx, cfg_dup=cfg_dup,
+                                            **self._chunk_kw(buf, temb, NB, n, x.device))
+            ld = int(e.shape[2])
+            if len(self.chunks) == 1:
+                stage = e
+            else:
+                key = ("pairs", NB, P, g.h, g.w, ld, x.device)
+                if key not in self._bufs:
+                    self._bufs[key] = torch.zeros((NB * P, g.h * g.w, ld), dtype=torch.float16, device=x.device)
+                stage = self._bufs[key]
+                stage.view(NB, P, g.h * g.w, ld)[:, p0:p0 + n].copy_(e.view(NB, n, g.h * g.w, ld))
+        out = self._out_buf(x, ld, "out")
+        ops.window_average_regions(stage, g, self._out_channels(), plan=plan, out=out, weights=self._weights_on(x.device))
+        self.evals += 1
+        return out
+
+    def _weights_on(self, device):
+        if self.weights is None:
+            return None
+        if self._weights_dev is None or self._weights_dev.device != device:
+            self._weights_dev = self.weights.to(device)
+        return self._weights_dev
+
     # ---- the model call
     def apply_model_nhwc(self, x, t, cond, temb=None, cfg_dup=False):
         """LatentDiffusion.apply_model_nhwc on the canvas x [NB, C, Hc, Wc]: NHWC fp16 [NB, Hc * Wc, ld], a buffer of the
@@ -162,32 +305,26 @@ class WindowedDiffusion:
             raise MdxError("WindowedDiffusion: x must be a CUDA(HIP) tensor [NB, C, H, W] (no CPU fallback)")
         NB, C, Hc, Wc = (int(v) for v in x.shape)
         g = self.grid_for(Hc, Wc)
-        if g.N == 1:
+        if g.N == 1 and self._regions is None:
             return self.inner.apply_model_nhwc(x, t, cond, temb=temb, cfg_dup=cfg_dup)
         if self.weights is not None and (g.h, g.w) != self.window:
             raise MdxError(f"WindowedDiffusion: the weights are for {self.window} windows, a {Hc}x{Wc} canvas clips them to "
                            f"{(g.h, g.w)}")
-        self.grid = g
-        self.chunks = chunk_list(g.N, NB, self.max_unet_batch)
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.to(torch.float32).contiguous()
         t = torch.as_tensor(t, device=x.device).to(torch.float32).reshape(-1)
         if t.numel() == 1:
             t = t.expand(NB)
+        if g.wrap_x or self._regions is not None:
+            return self._apply_pairs(x, t, cond, temb, cfg_dup, g)
+        self.grid = g
+        self.chunks = chunk_list(g.N, NB, self.max_unet_batch)
         stage = None
         for k0, n in self.chunks:
             buf = self._in_bufs(x, n)
             ops.window_gather(x, g, k0, n, out=buf["x"])
             buf["t"].view(NB, n).copy_(t.reshape(NB, 1).expand(NB, n))
-            kw = {}
-            if temb is not None:
-                if temb.dim() == 2:
-                    if "temb" not in buf or buf["temb"].shape[1] != temb.shape[1]:
-                        buf["temb"] = torch.empty((NB * n, temb.shape[1]), dtype=temb.dtype, device=x.device)
-                    buf["temb"].view(NB, n, -1).copy_(temb[:, None, :].expand(NB, n, temb.shape[1]))
-                    kw["temb"] = buf["temb"]
-                else:
-                    kw["temb"] = temb         # one row: it broadcasts over any batch
+            kw = self._chunk_kw(buf, temb, NB, n, x.device)
             e = self.inner.apply_model_nhwc(buf["x"], buf["t"], self._context(cond, n), cfg_dup=cfg_dup, **kw)
             ld = int(e.shape[2])
             if len(self.chunks) == 1:
@@ -196,12 +333,7 @@ class WindowedDiffusion:
                 stage = self._out_buf(x, ld, "stage")
                 stage.view(NB, g.N, g.h * g.w, ld)[:, k0:k0 + n].copy_(e.view(NB, n, g.h * g.w, ld))
         out = self._out_buf(x, ld, "out")
-        wts = None
-        if self.weights is not None:
-            if self._weights_dev is None or self._weights_dev.device != x.device:
-                self._weights_dev = self.weights.to(x.device)
-            wts = self._weights_dev
-        ops.window_average(stage, g, self._out_channels(), out=out, weights=wts)
+        ops.window_average(stage, g, self._out_channels(), out=out, weights=self._weights_on(x.device))
         self.evals += 1
         return out
 

@@ -1124,7 +1124,8 @@ def inpaint_composite(decoded, image=None, alpha=None, output="float", out_f32=N
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Windowed UNet evaluation (include/mdx.h: mdx_window_gather_f32 / mdx_window_average_f16, csrc/window.hip).
+# Windowed UNet evaluation (include/mdx.h: mdx_window_gather_f32 / mdx_window_average_f16 and, for regions and wrap-around
+# windows, mdx_window_gather_rows_f32 / mdx_window_average_regions_f16; csrc/window.hip).
 def window_offsets(length, window, stride):
     """The offsets of one axis: 0, s, 2s, ... while o + w < L, then a last window at L - w (clamped, not padded);
     L == w: [0]."""
@@ -1144,12 +1145,20 @@ def window_offsets(length, window, stride):
 
 class WindowGrid:
     """The windows of one canvas: oy / ox (window_offsets per axis), window k = iy * nx + ix at (oy[iy], ox[ix]), and the
-    int32 table [ny + nx] both kernels read -- on the host from construction, on a device from the first on(device), once."""
+    int32 table [ny + nx] the kernels read -- on the host from construction, on a device from the first on(device), once.
+    wrap_x: the x offsets are 0, s, 2s, ... while o < Wc (nx = ceil(Wc / s)) and a window at o covers the canvas columns
+    (o + i) mod Wc, i < w: the left and the right edge of the canvas lie inside one window (a 360-degree panorama).  Rows never
+    wrap.  A wrapped grid is read by window_gather_rows / window_average_regions only."""
 
-    def __init__(self, canvas_hw, window_hw, stride_hw):
+    def __init__(self, canvas_hw, window_hw, stride_hw, wrap_x=False):
         (self.Hc, self.Wc), (self.h, self.w) = (int(v) for v in canvas_hw), (int(v) for v in window_hw)
+        self.wrap_x = bool(wrap_x)
         self.oy = window_offsets(self.Hc, self.h, stride_hw[0])
-        self.ox = window_offsets(self.Wc, self.w, stride_hw[1])
+        if self.wrap_x:
+            window_offsets(self.Wc, self.w, stride_hw[1])            # (the same refusals: 0 < s <= w <= Wc)
+            self.ox = list(range(0, self.Wc, int(stride_hw[1])))
+        else:
+            self.ox = window_offsets(self.Wc, self.w, stride_hw[1])
         self.ny, self.nx = len(self.oy), len(self.ox)
         self.N = self.ny * self.nx
         self.host = np.ascontiguousarray(np.asarray(self.oy + self.ox, dtype=np.int32))
@@ -1164,23 +1173,97 @@ class WindowGrid:
     def origin(self, k):
         return self.oy[k // self.nx], self.ox[k % self.nx]
 
+    def columns(self, k):
+        """The canvas columns of window k, in the window's own order (modulo Wc on a wrapped grid)."""
+        return (self.ox[k % self.nx] + np.arange(self.w)) % self.Wc
+
     def coverage(self):
-        """[Hc, Wc] int64: how many windows cover each canvas pixel."""
+        """[Hc, Wc] int64: how many windows cover each canvas pixel (columns counted modulo Wc on a wrapped grid)."""
         cy, cx = np.zeros(self.Hc, np.int64), np.zeros(self.Wc, np.int64)
         for o in self.oy:
             cy[o:o + self.h] += 1
         for o in self.ox:
-            cx[o:o + self.w] += 1
+            cx[(o + np.arange(self.w)) % self.Wc] += 1
         return cy[:, None] * cx[None, :]
 
     def _host_ptr(self):
         return ctypes.c_void_p(self.host.ctypes.data)
 
 
+class _IntTable:
+    """An int32 table the kernels read on the device and the C entries validate on the host: both copies, made once."""
+
+    def __init__(self, values):
+        self.host = np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+        self.lo, self.hi = (int(self.host.min()), int(self.host.max())) if self.host.size else (0, -1)      # at construction
+        self._dev = {}
+
+    def __len__(self):
+        return int(self.host.shape[0])
+
+    def on(self, device):
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.host).to(device)
+        return self._dev[device]
+
+    def _host_ptr(self):
+        return ctypes.c_void_p(self.host.ctypes.data)
+
+
+class WindowRows(_IntTable):
+    """A table of window numbers for window_gather_rows: any order, repeats allowed."""
+
+
+class RegionPlan:
+    """R regions on the canvas of `grid`: masks [R, Hc, Wc] fp32, finite, >= 0, their sum > 0 at every pixel, and the list of
+    ACTIVE (window, region) pairs sorted by window then region -- (k, r) is active iff M_r is non-zero somewhere inside window
+    k (wrap included) -- so a small region costs only the windows it touches, and a pixel with M_r > 0 has every covering
+    window active for r (the denominator of the region mean is positive everywhere).  pair_window [P], pair_region [P] and the
+    CSR index pair_first [N + 1] are held on the host (what the C entry validates) and, from on(device), on the device."""
+
+    def __init__(self, grid, masks):
+        m = torch.as_tensor(masks).detach().to("cpu", torch.float32)
+        if m.dim() != 3 or tuple(m.shape[1:]) != (grid.Hc, grid.Wc) or m.shape[0] < 1:
+            raise _lib.MdxError(f"RegionPlan: masks have shape {tuple(m.shape)}, expected [R >= 1, {grid.Hc}, {grid.Wc}]")
+        a = np.ascontiguousarray(m.numpy())
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise _lib.MdxError("RegionPlan: masks must be finite and >= 0")
+        if not (a.sum(0, dtype=np.float64) > 0).all():
+            raise _lib.MdxError("RegionPlan: the masks must sum to > 0 at every canvas pixel (a pixel no region claims has no "
+                                "output)")
+        self.grid, self.R, self.masks_host = grid, int(a.shape[0]), a
+        pw, pr, first = [], [], [0]
+        for k in range(grid.N):
+            oy = grid.oy[k // grid.nx]
+            inside = a[:, oy:oy + grid.h][:, :, grid.columns(k)]
+            for r in range(self.R):
+                if inside[r].any():
+                    pw.append(k)
+                    pr.append(r)
+            first.append(len(pw))
+        self.pairs = list(zip(pw, pr))
+        self.P = len(pw)
+        self.pair_window, self.pair_region, self.pair_first = _IntTable(pw), _IntTable(pr), _IntTable(first)
+        self._masks_dev = {}
+
+    def masks_on(self, device):
+        device = torch.device(device)
+        if device not in self._masks_dev:
+            self._masks_dev[device] = torch.from_numpy(self.masks_host).to(device)
+        return self._masks_dev[device]
+
+
+def _clamped(grid, what):
+    if grid.wrap_x:
+        raise _lib.MdxError(f"{what}: a wrapped grid (wrap_x) is read by window_gather_rows / window_average_regions")
+
+
 def window_gather(canvas, grid, k0=0, n=None, out=None):
     """Windows k0 .. k0 + n - 1 of canvas [NB, C, Hc, Wc] fp32 as [NB * n, C, h, w], window kk of canvas row j in output row
     j * n + kk.  One launch."""
     _chk(canvas, f32, "canvas"); _chk(out, f32, "out")
+    _clamped(grid, "window_gather")
     if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
         raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
     NB, C = int(canvas.shape[0]), int(canvas.shape[1])
@@ -1203,6 +1286,7 @@ def window_average(windows, grid, C, out=None, weights=None):
     [NB, Hc * Wc, ld] (include/mdx.h: the arithmetic is part of the contract).  weights: [h, w] fp32 > 0 on the device, None:
     uniform.  Channels [C, ld) of the result are 0.  One launch."""
     _chk(windows, f16, "windows"); _chk(out, f16, "out"); _chk(weights, f32, "weights")
+    _clamped(grid, "window_average")
     if windows.dim() != 3 or windows.shape[0] % grid.N or windows.shape[1] != grid.h * grid.w:
         raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {grid.N}, {grid.h * grid.w}, ld]")
     NB, ld = int(windows.shape[0]) // grid.N, int(windows.shape[2])
@@ -1215,6 +1299,61 @@ def window_average(windows, grid, C, out=None, weights=None):
     _lib.check(_lib.load().mdx_window_average_f16(_ptr(windows), _ptr(out), _ptr(weights), 0 if weights is None else weights.numel(),
                                                   _ptr(grid.on(windows.device)), grid._host_ptr(), grid.ny, grid.nx, NB, int(C), ld,
                                                   grid.Hc, grid.Wc, grid.h, grid.w, _stream()), "mdx_window_average_f16")
+    return out
+
+
+def window_gather_rows(canvas, grid, rows, out=None):
+    """The windows rows[0 .. n) -- a WindowRows, or a sequence of window numbers; any order, repeats allowed -- of canvas
+    [NB, C, Hc, Wc] fp32 as [NB * n, C, h, w], window rows[i] of canvas row j in output row j * n + i.  Reads a wrapped grid
+    (grid.wrap_x) as well as a clamped one.  One launch."""
+    _chk(canvas, f32, "canvas"); _chk(out, f32, "out")
+    if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
+        raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
+    if not isinstance(rows, WindowRows):
+        rows = WindowRows(rows)
+    NB, C, n = int(canvas.shape[0]), int(canvas.shape[1]), len(rows)
+    if n < 1 or rows.lo < 0 or rows.hi >= grid.N:              # (the C entry checks the host table itself, entry by entry)
+        raise _lib.MdxError(f"window_gather_rows: rows {rows.host.tolist()} are not inside the grid of {grid.ny} x {grid.nx}")
+    if out is None:
+        out = torch.empty((NB * n, C, grid.h, grid.w), dtype=f32, device=canvas.device)
+    elif tuple(out.shape) != (NB * n, C, grid.h, grid.w):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB * n, C, grid.h, grid.w)}")
+    _lib.check(_lib.load().mdx_window_gather_rows_f32(_ptr(canvas), _ptr(out), _ptr(grid.on(canvas.device)), grid._host_ptr(),
+                                                      grid.ny, grid.nx, _ptr(rows.on(canvas.device)), rows._host_ptr(), n,
+                                                      int(grid.wrap_x), NB, C, grid.Hc, grid.Wc, grid.h, grid.w, _stream()),
+               "mdx_window_gather_rows_f32")
+    return out
+
+
+def window_average_regions(windows, grid, C, plan=None, out=None, weights=None):
+    """The outputs of all P active pairs of `plan` (a RegionPlan on `grid`), NHWC fp16 [NB * P, h * w, ld], row j * P + p,
+    averaged onto the canvas [NB, Hc * Wc, ld] with every term weighed by its region's mask at the pixel (times `weights`
+    inside the window); include/mdx.h states the arithmetic.  plan None: no regions -- the pairs are the N windows -- which is
+    window_average on a grid that may wrap.  One launch."""
+    _chk(windows, f16, "windows"); _chk(out, f16, "out"); _chk(weights, f32, "weights")
+    if plan is not None and plan.grid is not grid:
+        raise _lib.MdxError("window_average_regions: the plan was made for another grid")
+    P = grid.N if plan is None else plan.P
+    if windows.dim() != 3 or windows.shape[0] % P or windows.shape[1] != grid.h * grid.w:
+        raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {P}, {grid.h * grid.w}, ld]")
+    NB, ld = int(windows.shape[0]) // P, int(windows.shape[2])
+    if weights is not None and tuple(weights.shape) != (grid.h, grid.w):
+        raise _lib.MdxError(f"weights: shape {tuple(weights.shape)}, expected {(grid.h, grid.w)}")
+    if out is None:
+        out = torch.empty((NB, grid.Hc * grid.Wc, ld), dtype=f16, device=windows.device)
+    elif tuple(out.shape) != (NB, grid.Hc * grid.Wc, ld):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB, grid.Hc * grid.Wc, ld)}")
+    dev = windows.device
+    if plan is None:
+        tables, masks, R = (None,) * 5, None, 0
+    else:
+        tables = (plan.pair_window._host_ptr(), _ptr(plan.pair_region.on(dev)), plan.pair_region._host_ptr(),
+                  _ptr(plan.pair_first.on(dev)), plan.pair_first._host_ptr())
+        masks, R = plan.masks_on(dev), plan.R
+    _lib.check(_lib.load().mdx_window_average_regions_f16(
+        _ptr(windows), _ptr(out), _ptr(weights), 0 if weights is None else weights.numel(), _ptr(grid.on(dev)), grid._host_ptr(),
+        grid.ny, grid.nx, int(grid.wrap_x), *tables, P, _ptr(masks), R, NB, int(C), ld, grid.Hc, grid.Wc, grid.h, grid.w,
+        _stream()), "mdx_window_average_regions_f16")
     return out
 
 

@@ -11,6 +11,8 @@ Text encoding and VAE decode are outside the hot path
 conditioning tensors (c, uc), or attach ``model.cond_stage_model`` / ``model.first_stage_model``.
 With torch.distributed initialised the global batch is sharded across ranks (distributed.py).
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -18,7 +20,7 @@ from . import distributed as D
 from . import ops
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
-from .ldm.models.diffusion.guided import as_sequence, per_request
+from .ldm.models.diffusion.guided import as_sequence, per_request, use_cfg
 from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
 from .ldm.modules.encoders import WINDOW, pad_conditioning
 
@@ -36,6 +38,7 @@ class DiffusionPipeline:
             else:
                 sampler = (DDIMSampler if sampler == "ddim" else PLMSSampler)(model)
         self.sampler = sampler
+        self.seam_cols = 0            # latent columns of circular padding per side around the decoder (windowed(wrap_x=True))
 
     def start_noise(self, batch, shape, seed):
         """numpy RandomState(seed).randn -- the reference's own practice for reproducible x_T
@@ -175,13 +178,92 @@ class DiffusionPipeline:
         blend_kw = {} if mask is None else {"mask": mask, "x0": x0}
         return self.sampler.decode(x_enc, cond, t_enc, **blend_kw, **common)[0]
 
+    def _decode_latent(self, samples):
+        """model.decode_first_stage; on a wrap_x pipeline with seam_pad > 0 the latent is padded circularly by seam_cols columns
+        per side first and the padded image columns are cropped, so the decoder's 3 x 3 convs see the other edge of the panorama
+        where they would see zeros.  (GroupNorm and the mid attention are global: this is not exact periodicity.)"""
+        pad = min(int(self.seam_cols), int(samples.shape[-1]))
+        if pad <= 0:
+            return self.model.decode_first_stage(samples)             # txt2img.py:265-266
+        padded = torch.cat([samples[..., -pad:], samples, samples[..., :pad]], -1).contiguous()
+        x = self.model.decode_first_stage(padded)
+        cut = pad * (int(x.shape[-1]) // int(padded.shape[-1]))        # (the VAE's own factor: 8 for SD)
+        return x[..., cut:int(x.shape[-1]) - cut].contiguous()
+
     def _decoded(self, samples):
-        x = self.model.decode_first_stage(samples)                    # txt2img.py:265-266
+        x = self._decode_latent(samples)
         return torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
+
+    # ---- regional prompts (ldm/models/diffusion/windowed.py): a mask over the canvas and a prompt each
+    @staticmethod
+    def background_mask(masks):
+        """[R, h, w] region masks in [0, 1] -> [1 + R, h, w] with the call's own prompt as region 0 on 1 - max_r m_r: the
+        masks then sum to >= 1 at every pixel."""
+        return torch.cat([(1.0 - masks.max(0).values)[None], masks], 0)
+
+    def _check_regions_allowed(self, what, regions):
+        """regions= is refused, before any work, on a pipeline that is not windowed and on several ranks."""
+        from .ldm.models.diffusion.windowed import WindowedDiffusion
+        if regions is None:
+            return
+        if not isinstance(self.model, WindowedDiffusion):
+            raise MdxError(f"{what}: regions= needs a windowed pipeline (DiffusionPipeline.windowed)")
+        if D.world()[1] > 1:
+            raise MdxError(f"{what}: regions= runs on a single rank (the sharded form is not built)")
+
+    def _region_scope(self, what, regions, c, uc, scale, latent_hw, image_hw):
+        """The `with` block of a call's `regions=[{"prompt": ... | "c": ..., "mask": m}, ...]` (None: no block).  c / uc: the
+        call's conditioning as the sampler gets it, on the device.  m: [h, w] at the latent grid, or [H, W] at the image's,
+        reduced with ops.inpaint_resize_mask; values in [0, 1]; shared by the batch.  The contexts are laid out as GuidedModel
+        will lay out its own, by guided.use_cfg: cat([uc, c_r]) under guidance, c_r without."""
+        if regions is None:
+            return contextlib.nullcontext()
+        self._check_regions_allowed(what, regions)
+        regions = list(regions)
+        if not regions:
+            raise MdxError(f"{what}: regions= is empty")
+        B, (h, w) = int(c.shape[0]), (int(v) for v in latent_hw)
+        masks, ctxs = [], [c]
+        for i, reg in enumerate(regions):
+            if not isinstance(reg, dict) or "mask" not in reg or ("prompt" in reg) == ("c" in reg):
+                raise MdxError(f"{what}: region {i} must be a dict with 'mask' and exactly one of 'prompt' and 'c'")
+            m = torch.as_tensor(reg["mask"]).to(torch.float32)
+            if m.dim() != 2 or tuple(m.shape) not in ((h, w), tuple(int(v) for v in image_hw)):
+                raise MdxError(f"{what}: region {i}: the mask is {tuple(m.shape)}, expected {(h, w)} (the latent grid) or "
+                               f"{tuple(int(v) for v in image_hw)} (the image)")
+            if not bool(torch.isfinite(m).all()) or float(m.min()) < 0.0 or float(m.max()) > 1.0:
+                raise MdxError(f"{what}: region {i}: mask values must be finite and in [0, 1]")
+            m = m.to(self.device)
+            if tuple(m.shape) != (h, w):
+                m = ops.inpaint_resize_mask(m[None, None].contiguous(), (h, w))[0, 0]
+            masks.append(m)
+            if "prompt" in reg:
+                cr = self.model.get_learned_conditioning(B * [reg["prompt"]])
+            else:
+                cr = reg["c"]
+                if not (isinstance(cr, torch.Tensor) and cr.dim() == 3 and int(cr.shape[0]) in (1, B)):
+                    raise MdxError(f"{what}: region {i}: c must be a tensor [{B} | 1, T, D]")
+            cr = cr.to(self.device, c.dtype)
+            ctxs.append(cr.expand(B, -1, -1) if cr.shape[0] != B else cr)
+        T = max(int(x.shape[1]) for x in ctxs + ([uc] if uc is not None else []))
+        if any(int(x.shape[1]) != T for x in ctxs) or (uc is not None and int(uc.shape[1]) != T):
+            if getattr(self.model, "cond_stage_model", None) is None:
+                raise MdxError(f"{what}: the region contexts and the call's c / uc differ in length and no text encoder is "
+                               f"attached to encode the empty window: bring them to one length with encoders.pad_conditioning")
+            if uc is not None and int(uc.shape[1]) != T:
+                raise MdxError(f"{what}: a region's context is longer than the call's own c / uc ({T} tokens): give the call "
+                               f"a prompt of as many windows, or pad c and uc with encoders.pad_conditioning")
+            empty = self.model.get_learned_conditioning([""])[:, :WINDOW]
+            longest = next(x for x in ctxs if int(x.shape[1]) == T)
+            ctxs = [pad_conditioning(x, longest, empty)[0] for x in ctxs]
+        self.fit_context(ctxs[0])
+        guided = use_cfg(uc, None, scale)
+        ctxs = [(torch.cat([uc.to(x.dtype), x], 0) if guided else x).contiguous() for x in ctxs]
+        return self.model.regions(self.background_mask(torch.stack(masks)), ctxs)
 
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
                  decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
-                 guidance_rescale=0.0, seeds=None):
+                 guidance_rescale=0.0, seeds=None, regions=None):
         """Multi-rank runs: every rank calls with the same `prompts` list (or the same `batch_size` when rank 0 passes
         precomputed (c, uc) tensors); only rank 0's c / uc / x_T are used, the other ranks may pass None.
         seeds: one int per sample of the global batch, every rank the same list: sample b's x_T and step noise then depend on
@@ -190,9 +272,12 @@ class DiffusionPipeline:
         guidance_rescale in [0, 1]: the samplers' keyword (CFG rescale for v-prediction checkpoints), every rank the same.
         steps, scale and guidance_rescale each take one value or one per sample (a list): independent requests -- "30 steps,
         scale 7.5" and "50 steps, scale 5, rescale 0.7" -- then share one UNet batch, every sample on its own schedule
-        (the samplers' per-request form).  Single rank only."""
+        (the samplers' per-request form).  Single rank only.
+        regions (a windowed pipeline, single rank): [{"prompt": ... | "c": [B | 1, T, D], "mask": m}, ...] -- regional prompts;
+        m [H/8, W/8] or [H, W] in [0, 1], shared by the batch.  The call's own prompt is region 0, on 1 - max_r m_r."""
         guidance_rescale = self.check_request_lists("DiffusionPipeline", None, steps, scale, guidance_rescale)
         rank, n = D.world()
+        self._check_regions_allowed("DiffusionPipeline", regions)
         shape = [4, H // 8, W // 8]                                   # txt2img.py:253
         if rank == 0:
             c, uc = self._encoded(prompts, c, uc, required=n == 1)
@@ -225,10 +310,11 @@ class DiffusionPipeline:
             x_T = x_T.to(self.device)
         # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W;
         # the seeds are this rank's samples': the eta > 0 step draws
-        samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=int(c.shape[0]), shape=shape, verbose=False,
-                                             unconditional_guidance_scale=scale, unconditional_conditioning=uc,
-                                             eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
-                                             **self._sampler_kw(guidance_rescale, seeds))
+        with self._region_scope("DiffusionPipeline", regions, c, uc, scale, shape[1:], (H, W)):
+            samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=int(c.shape[0]), shape=shape, verbose=False,
+                                                 unconditional_guidance_scale=scale, unconditional_conditioning=uc,
+                                                 eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
+                                                 **self._sampler_kw(guidance_rescale, seeds))
         if decode:
             samples = self._decoded(samples)
         if gather and n > 1:
@@ -236,12 +322,15 @@ class DiffusionPipeline:
         return samples
 
     # ---- large canvases (ldm/models/diffusion/windowed.py): the UNet evaluated in overlapping windows of the trained size
-    def windowed(self, window=512, stride=None, weights=None, max_unet_batch=16):
+    def windowed(self, window=512, stride=None, weights=None, max_unet_batch=16, wrap_x=False, seam_pad=64):
         """A new DiffusionPipeline on WindowedDiffusion(self.model, ...): the same sampler kind and device, all weights
         shared.  On it __call__(..., H=512, W=2048), img2img, inpaint, session(H=, W=) and serve run as they do here, the UNet
         evaluated per step on overlapping windows of the canvas and averaged where they overlap.  window / stride: IMAGE
         pixels, ints or (H, W) pairs, multiples of 8 (stride None: half the window); weights: None or [window / 8] positive
-        latent-pixel weights (windowed.gaussian_weights); max_unet_batch: the largest UNet batch one chunk of windows makes."""
+        latent-pixel weights (windowed.gaussian_weights); max_unet_batch: the largest UNet batch one chunk of windows makes.
+        wrap_x: the windows wrap around the right edge of the canvas into the left one (a 360-degree panorama); decoding then
+        pads the latent circularly by seam_pad IMAGE pixels (a multiple of 8; 0: the plain decode) per side and crops them.
+        The new pipeline's __call__, img2img and inpaint take regions= (regional prompts)."""
         from .ldm.models.diffusion.windowed import WindowedDiffusion, _pair
 
         def latent(v, name):
@@ -256,8 +345,13 @@ class DiffusionPipeline:
         except MdxError:
             raise MdxError(f"DiffusionPipeline.windowed: the new pipeline gets a sampler of this one's kind, 'ddim', 'plms' or "
                            f"'dpm_solver'; this one's is a {type(self.sampler).__name__}") from None
-        model = WindowedDiffusion(self.model, latent(window, "window"), latent(stride, "stride"), weights, max_unet_batch)
-        return DiffusionPipeline(model, kind, self.device)
+        if isinstance(seam_pad, bool) or not isinstance(seam_pad, (int, np.integer)) or seam_pad < 0 or seam_pad % 8:
+            raise MdxError(f"DiffusionPipeline.windowed: seam_pad is in image pixels, a multiple of 8 >= 0, got {seam_pad!r}")
+        model = WindowedDiffusion(self.model, latent(window, "window"), latent(stride, "stride"), weights, max_unet_batch,
+                                  wrap_x=wrap_x)
+        pipe = DiffusionPipeline(model, kind, self.device)
+        pipe.seam_cols = int(seam_pad) // 8 if wrap_x else 0
+        return pipe
 
     # ---- continuous batching (ldm/models/diffusion/session.py): requests join and leave a running UNet batch
     def _session_sampler(self):
@@ -307,7 +401,7 @@ class DiffusionPipeline:
 
     def img2img(self, init_image=None, init_latent=None, strength=0.75, prompts=None, c=None, uc=None, steps=50, scale=9.0,
                 eta=0.0, seed=42, noise=None, post_noise=None, sample_posterior=True, mask=None, decode=False, callback=None,
-                img_callback=None, guidance_rescale=0.0, seeds=None):
+                img_callback=None, guidance_rescale=0.0, seeds=None, regions=None):
         """Start from an image instead of pure noise: encode it, noise the latent to the level `strength` selects, and run only
         the remaining t_enc = int(strength * steps) of the `steps`-step schedule (strength 1: all of them).
 
@@ -318,8 +412,10 @@ class DiffusionPipeline:
         init image there (PLMS / DDIM only).  Conditioning, decode and guidance_rescale as in __call__.  Single rank only.
         seeds: one int per sample; the forward noise (ops.RNG_ENCODE), the posterior noise (ops.RNG_POSTERIOR) and the step and
         blend draws of sample b then depend on seeds[b] alone.  A passed noise / post_noise still wins.
-        scale and guidance_rescale each take one value or one per sample; steps is one int (`strength` fixes one grid)."""
+        scale and guidance_rescale each take one value or one per sample; steps is one int (`strength` fixes one grid).
+        regions: regional prompts on a windowed pipeline, as in __call__ (masks at the latent's or the init image's size)."""
         guidance_rescale = self.check_request_lists("img2img", None, steps, scale, guidance_rescale, steps_list=False)
+        self._check_regions_allowed("img2img", regions)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
         t_enc = self._check_strength("img2img", strength, steps)
@@ -352,8 +448,10 @@ class DiffusionPipeline:
             x_enc = self.sampler.stochastic_encode(z0, start, noise=self._draw(noise, seeds, ops.RNG_ENCODE, z0.shape, seed))
         if z0.shape[0] != B:
             raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
-        samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, callback, img_callback,
-                                    self._sampler_kw(guidance_rescale, seeds), mask=mask, x0=z0)
+        image_hw = tuple(init_image.shape[2:]) if init_image is not None else tuple(8 * int(v) for v in z0.shape[2:])
+        with self._region_scope("img2img", regions, c, uc, scale, z0.shape[2:], image_hw):
+            samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, callback, img_callback,
+                                        self._sampler_kw(guidance_rescale, seeds), mask=mask, x0=z0)
         return self._decoded(samples) if decode else samples
 
     # ---- inpainting: wukong-huahua/inpaint.py, image and mask in, composited image out
@@ -412,7 +510,7 @@ class DiffusionPipeline:
 
     def inpaint(self, image, mask, prompts=None, c=None, uc=None, steps=30, scale=7.5, eta=0.0, strength=1.0, seed=42,
                 seeds=None, x_T=None, noise=None, post_noise=None, sample_posterior=True, mask_blur=0.0, composite=True,
-                decode=True, output="float", guidance_rescale=0.0, callback=None, img_callback=None):
+                decode=True, output="float", guidance_rescale=0.0, callback=None, img_callback=None, regions=None):
         """Repaint the masked region of an image (wukong-huahua/inpaint.py:65-117; its CLI defaults: PLMS, 30 steps, scale 7.5).
 
         image [B | 1, 3, H, W] in [-1, 1]; mask [B | 1, 1, H, W], >= 0.5 = repaint; batch-1 inputs are repeated to the
@@ -427,8 +525,10 @@ class DiffusionPipeline:
         (a Gaussian sigma in pixels, > 0) alpha = max(m, G * m) -- the mask widened outward, exactly 1 on the hole; composite
         False returns the decoder's picture as the reference does.  output "float": [B, 3, H, W] in [0, 1]; "uint8":
         [B, H, W, 3], (uint8)(255 v) as inpaint.py:112-115.
-        scale and guidance_rescale each take one value or one per sample; steps is one int, as in img2img."""
+        scale and guidance_rescale each take one value or one per sample; steps is one int, as in img2img.
+        regions: regional prompts on a windowed pipeline, as in __call__ (masks at the latent's or the image's size)."""
         guidance_rescale = self.check_request_lists("inpaint", None, steps, scale, guidance_rescale, steps_list=False)
+        self._check_regions_allowed("inpaint", regions)
         if output not in ("float", "uint8"):
             raise ValueError(f"inpaint: output must be 'float' or 'uint8', got {output!r}")
         t_enc = self._check_strength("inpaint", strength, steps)
@@ -458,7 +558,8 @@ class DiffusionPipeline:
             keep = 1.0 - ops.inpaint_resize_mask(mask, vae.latent_shape(image.shape)[2:])
             samples = self.img2img(init_image=image, strength=strength, c=c, uc=uc, steps=steps, scale=scale, eta=eta, seed=seed,
                                    noise=noise, post_noise=post_noise, sample_posterior=sample_posterior, mask=keep,
-                                   callback=callback, img_callback=img_callback, guidance_rescale=guidance_rescale, seeds=seeds)
+                                   callback=callback, img_callback=img_callback, guidance_rescale=guidance_rescale, seeds=seeds,
+                                   regions=regions)
         else:
             c, uc = self._on_device(c, uc, B)
             lat = vae.latent_shape(image.shape)
@@ -466,24 +567,27 @@ class DiffusionPipeline:
             cond = {"c_concat": c_cat, "c_crossattn": c}                  # inpaint.py:88
             uc_full = None if uc is None else {"c_concat": c_cat, "c_crossattn": uc}      # inpaint.py:91-92
             kw = self._sampler_kw(guidance_rescale, seeds)
+            scope = self._region_scope("inpaint", regions, c, uc, scale, lat[2:], image.shape[2:])
             if t_enc == steps:
                 # the reference's run (strength 1): pure noise, every step; neither mask nor x0 goes to the sampler (inpaint.py's
                 # x0= without a mask is inert)
                 x_T = self._draw(x_T, seeds, ops.RNG_X_T, lat, seed)
-                samples = self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=list(lat[1:]), verbose=False,
-                                              eta=eta, x_T=x_T.to(self.device), unconditional_guidance_scale=scale,
-                                              unconditional_conditioning=uc_full, callback=callback, img_callback=img_callback,
-                                              **kw)[0]
+                with scope:
+                    samples = self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=list(lat[1:]), verbose=False,
+                                                  eta=eta, x_T=x_T.to(self.device), unconditional_guidance_scale=scale,
+                                                  unconditional_conditioning=uc_full, callback=callback,
+                                                  img_callback=img_callback, **kw)[0]
             else:
                 # strength < 1: start from the (unmasked) image's own latent, noised to where the last t_enc steps begin -- img2img
                 start, a, b = self._partial_start(steps, t_enc, eta)
                 _, x_enc = vae.encode_noised(image, self.model.scale_factor, a, b,
                                              self._draw(noise, seeds, ops.RNG_ENCODE, lat, seed), post_noise=post,
                                              sample=sample_posterior)
-                samples = self._run_partial(x_enc, cond, uc_full, start, t_enc, scale, callback, img_callback, kw)
+                with scope:
+                    samples = self._run_partial(x_enc, cond, uc_full, start, t_enc, scale, callback, img_callback, kw)
         if not decode:
             return samples
-        x = self.model.decode_first_stage(samples).to(torch.float32).contiguous()
+        x = self._decode_latent(samples).to(torch.float32).contiguous()
         alpha = None
         if composite:
             alpha = ops.mask_feather(mask, mask_blur) if mask_blur > 0.0 else mask
