@@ -17,6 +17,7 @@ nothing in the UNet, the step kernels or the samplers.  Known cost: under guidan
 per pair, so the R regions of one window repeat the same unconditional evaluation.
 """
 import contextlib
+import functools
 import weakref
 
 import numpy as np
@@ -105,8 +106,9 @@ class WindowedDiffusion:
         self.weights = weights
         self.max_unet_batch = int(max_unet_batch)
         self.wrap_x = bool(wrap_x)
-        self.chunks = []            # [(k0, n), ...] of the last windowed call: ranges of windows, or of pairs (wrap_x / regions)
-        self.pairs = []             # [(k, r), ...] the UNet rows of the last wrapped or region call; r None without regions
+        self.chunks = []            # [(p0, n), ...] of the last windowed call: ranges of its UNet rows (self.pairs)
+        self.pairs = []             # [(k, r), ...] the UNet rows of the last windowed call, plain, wrapped or with regions: window
+                                    # k for region r; without regions r is None and the rows are the windows, (k, None), k < N
         self.grid = None            # ops.WindowGrid of the last windowed call
         self.evals = 0              # windowed calls (a single-window call forwards and does not count)
         self.context_refreshes = 0  # in-place refreshes of a per-window context repeat
@@ -174,12 +176,13 @@ class WindowedDiffusion:
             self._bufs[key] = {"x": z(NB * n, C, self.grid.h, self.grid.w), "t": z(NB * n)}
         return self._bufs[key]
 
-    def _out_buf(self, x, ld, name):
-        """"out": the canvas result [NB, Hc * Wc, ld]; "stage": the outputs of all windows (several chunks only)."""
+    def _out_buf(self, x, ld, rows=None):
+        """The canvas result [NB, Hc * Wc, ld]; with rows, the staged outputs [NB * rows, h * w, ld] of all the UNet rows of a
+        call (several chunks only)."""
         g, NB = self.grid, int(x.shape[0])
-        key = (name, NB, g.Hc, g.Wc, g.h, g.w, ld, x.device)
+        key = (rows, NB, g.Hc, g.Wc, g.h, g.w, ld, x.device)
         if key not in self._bufs:
-            shape = (NB, g.Hc * g.Wc, ld) if name == "out" else (NB * g.N, g.h * g.w, ld)
+            shape = (NB, g.Hc * g.Wc, ld) if rows is None else (NB * rows, g.h * g.w, ld)
             self._bufs[key] = torch.zeros(shape, dtype=torch.float16, device=x.device)
         return self._bufs[key]
 
@@ -204,13 +207,14 @@ class WindowedDiffusion:
 
     def _chunk_rows(self, g, plan, p0, n):
         """The ops.WindowRows of pairs p0 .. p0 + n - 1 (their window numbers), made once per plan and range."""
-        key = (id(g) if plan is None else id(plan), p0, n)
+        owner = g if plan is None else plan
+        key = (id(owner), p0, n)
         ent = self._rows.get(key)
-        if ent is None or ent[0] is not (g if plan is None else plan):      # (the owner is kept: ids are reused)
+        if ent is None or ent[0] is not owner:                              # (the owner is kept: ids are reused)
             windows = range(p0, p0 + n) if plan is None else plan.pair_window.host[p0:p0 + n]
             if len(self._rows) > 64:
                 self._rows.clear()
-            ent = self._rows[key] = (g if plan is None else plan, ops.WindowRows(windows))
+            ent = self._rows[key] = (owner, ops.WindowRows(windows))
         return ent[1]
 
     def _region_context(self, cond, p0, n):
@@ -252,43 +256,6 @@ class WindowedDiffusion:
         buf["temb"].view(NB, n, -1).copy_(temb[:, None, :].expand(NB, n, temb.shape[1]))
         return {"temb": buf["temb"]}
 
-    def _apply_pairs(self, x, t, cond, temb, cfg_dup, g):
-        """The wrapped and the region form of the call: the UNet rows are pairs -- (window, region), or the windows of a
-        wrapped grid -- cut into chunks of at most max_unet_batch // NB pairs; per chunk ops.window_gather_rows, the chunk's
-        context buffer and the inner model with the caller's cfg_dup (row order j * n + i keeps the [uncond ; cond] halves
-        identical inputs); then ONE ops.window_average_regions launch over all pairs."""
-        NB = int(x.shape[0])
-        reg = self._regions
-        plan = None if reg is None else reg["plan"]
-        if plan is not None and plan.grid is not g:
-            raise MdxError(f"WindowedDiffusion.regions: the masks are for a {plan.grid.Hc}x{plan.grid.Wc} canvas, the call is on "
-                           f"{g.Hc}x{g.Wc}")
-        P = g.N if plan is None else plan.P
-        self.grid = g
-        self.pairs = [(k, None) for k in range(g.N)] if plan is None else list(plan.pairs)
-        self.chunks = chunk_list(P, NB, self.max_unet_batch)
-        stage = None
-        for p0, n in self.chunks:
-            buf = self._in_bufs(x, n)
-            ops.window_gather_rows(x, g, self._chunk_rows(g, plan, p0, n), out=buf["x"])
-            buf["t"].view(NB, n).copy_(t.reshape(NB, 1).expand(NB, n))
-            ctx = self._context(cond, n) if plan is None else self._region_context(cond, p0, n)
-            e = self.inner.apply_model_nhwc(buf["x"], buf["t"], ctx, cfg_dup=cfg_dup,
-                                            **self._chunk_kw(buf, temb, NB, n, x.device))
-            ld = int(e.shape[2])
-            if len(self.chunks) == 1:
-                stage = e
-            else:
-                key = ("pairs", NB, P, g.h, g.w, ld, x.device)
-                if key not in self._bufs:
-                    self._bufs[key] = torch.zeros((NB * P, g.h * g.w, ld), dtype=torch.float16, device=x.device)
-                stage = self._bufs[key]
-                stage.view(NB, P, g.h * g.w, ld)[:, p0:p0 + n].copy_(e.view(NB, n, g.h * g.w, ld))
-        out = self._out_buf(x, ld, "out")
-        ops.window_average_regions(stage, g, self._out_channels(), plan=plan, out=out, weights=self._weights_on(x.device))
-        self.evals += 1
-        return out
-
     def _weights_on(self, device):
         if self.weights is None:
             return None
@@ -315,25 +282,39 @@ class WindowedDiffusion:
         t = torch.as_tensor(t, device=x.device).to(torch.float32).reshape(-1)
         if t.numel() == 1:
             t = t.expand(NB)
-        if g.wrap_x or self._regions is not None:
-            return self._apply_pairs(x, t, cond, temb, cfg_dup, g)
+        plan = None if self._regions is None else self._regions["plan"]
+        if plan is not None and plan.grid is not g:
+            raise MdxError(f"WindowedDiffusion.regions: the masks are for a {plan.grid.Hc}x{plan.grid.Wc} canvas, the call is on "
+                           f"{g.Hc}x{g.Wc}")
+        # The UNet rows are pairs -- (window, region), or without regions the windows -- cut into chunks of at most
+        # max_unet_batch // NB rows (row order j * n + i keeps the [uncond ; cond] halves identical inputs).  The one choice of
+        # the launches: a range of windows of a clamped grid, or a table of window numbers, region masks and wrap-around.
+        if plan is None and not g.wrap_x:
+            gather = lambda p0, n, out: ops.window_gather(x, g, p0, n, out=out)
+            average = ops.window_average
+        else:
+            gather = lambda p0, n, out: ops.window_gather_rows(x, g, self._chunk_rows(g, plan, p0, n), out=out)
+            average = functools.partial(ops.window_average_regions, plan=plan)
+        P = g.N if plan is None else plan.P
         self.grid = g
-        self.chunks = chunk_list(g.N, NB, self.max_unet_batch)
+        self.pairs = [(k, None) for k in range(g.N)] if plan is None else list(plan.pairs)
+        self.chunks = chunk_list(P, NB, self.max_unet_batch)
         stage = None
-        for k0, n in self.chunks:
+        for p0, n in self.chunks:
             buf = self._in_bufs(x, n)
-            ops.window_gather(x, g, k0, n, out=buf["x"])
+            gather(p0, n, buf["x"])
             buf["t"].view(NB, n).copy_(t.reshape(NB, 1).expand(NB, n))
-            kw = self._chunk_kw(buf, temb, NB, n, x.device)
-            e = self.inner.apply_model_nhwc(buf["x"], buf["t"], self._context(cond, n), cfg_dup=cfg_dup, **kw)
+            ctx = self._context(cond, n) if plan is None else self._region_context(cond, p0, n)
+            e = self.inner.apply_model_nhwc(buf["x"], buf["t"], ctx, cfg_dup=cfg_dup,
+                                            **self._chunk_kw(buf, temb, NB, n, x.device))
             ld = int(e.shape[2])
             if len(self.chunks) == 1:
                 stage = e                     # one chunk: its rows are in staging order already, averaged from where they lie
             else:                             # the UNet's static output is overwritten by the next chunk
-                stage = self._out_buf(x, ld, "stage")
-                stage.view(NB, g.N, g.h * g.w, ld)[:, k0:k0 + n].copy_(e.view(NB, n, g.h * g.w, ld))
-        out = self._out_buf(x, ld, "out")
-        ops.window_average(stage, g, self._out_channels(), out=out, weights=self._weights_on(x.device))
+                stage = self._out_buf(x, ld, rows=P)
+                stage.view(NB, P, g.h * g.w, ld)[:, p0:p0 + n].copy_(e.view(NB, n, g.h * g.w, ld))
+        out = self._out_buf(x, ld)
+        average(stage, g, self._out_channels(), out=out, weights=self._weights_on(x.device))
         self.evals += 1
         return out
 

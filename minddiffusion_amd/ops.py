@@ -1143,7 +1143,25 @@ def window_offsets(length, window, stride):
     return offs + [length - window]
 
 
-class WindowGrid:
+class _HostTable:
+    """A host array the C entries validate and its device copy the kernels read, made on the first on(device), once."""
+
+    def __init__(self, host):
+        self.host = np.ascontiguousarray(host)
+        self._ptr = ctypes.c_void_p(self.host.ctypes.data)       # (the array is written in place, never replaced)
+        self._dev = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.host).to(device)
+        return self._dev[device]
+
+    def _host_ptr(self):
+        return self._ptr
+
+
+class WindowGrid(_HostTable):
     """The windows of one canvas: oy / ox (window_offsets per axis), window k = iy * nx + ix at (oy[iy], ox[ix]), and the
     int32 table [ny + nx] the kernels read -- on the host from construction, on a device from the first on(device), once.
     wrap_x: the x offsets are 0, s, 2s, ... while o < Wc (nx = ceil(Wc / s)) and a window at o covers the canvas columns
@@ -1161,14 +1179,7 @@ class WindowGrid:
             self.ox = window_offsets(self.Wc, self.w, stride_hw[1])
         self.ny, self.nx = len(self.oy), len(self.ox)
         self.N = self.ny * self.nx
-        self.host = np.ascontiguousarray(np.asarray(self.oy + self.ox, dtype=np.int32))
-        self._dev = {}
-
-    def on(self, device):
-        device = torch.device(device)
-        if device not in self._dev:
-            self._dev[device] = torch.from_numpy(self.host).to(device)
-        return self._dev[device]
+        super().__init__(np.asarray(self.oy + self.ox, dtype=np.int32))
 
     def origin(self, k):
         return self.oy[k // self.nx], self.ox[k % self.nx]
@@ -1186,29 +1197,16 @@ class WindowGrid:
             cx[(o + np.arange(self.w)) % self.Wc] += 1
         return cy[:, None] * cx[None, :]
 
-    def _host_ptr(self):
-        return ctypes.c_void_p(self.host.ctypes.data)
 
-
-class _IntTable:
-    """An int32 table the kernels read on the device and the C entries validate on the host: both copies, made once."""
+class _IntTable(_HostTable):
+    """An int32 table of window, region or pair numbers."""
 
     def __init__(self, values):
-        self.host = np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+        super().__init__(np.asarray(values, dtype=np.int32).reshape(-1))
         self.lo, self.hi = (int(self.host.min()), int(self.host.max())) if self.host.size else (0, -1)      # at construction
-        self._dev = {}
 
     def __len__(self):
         return int(self.host.shape[0])
-
-    def on(self, device):
-        device = torch.device(device)
-        if device not in self._dev:
-            self._dev[device] = torch.from_numpy(self.host).to(device)
-        return self._dev[device]
-
-    def _host_ptr(self):
-        return ctypes.c_void_p(self.host.ctypes.data)
 
 
 class WindowRows(_IntTable):
@@ -1232,7 +1230,7 @@ class RegionPlan:
         if not (a.sum(0, dtype=np.float64) > 0).all():
             raise _lib.MdxError("RegionPlan: the masks must sum to > 0 at every canvas pixel (a pixel no region claims has no "
                                 "output)")
-        self.grid, self.R, self.masks_host = grid, int(a.shape[0]), a
+        self.grid, self.R = grid, int(a.shape[0])
         pw, pr, first = [], [], [0]
         for k in range(grid.N):
             oy = grid.oy[k // grid.nx]
@@ -1245,13 +1243,8 @@ class RegionPlan:
         self.pairs = list(zip(pw, pr))
         self.P = len(pw)
         self.pair_window, self.pair_region, self.pair_first = _IntTable(pw), _IntTable(pr), _IntTable(first)
-        self._masks_dev = {}
-
-    def masks_on(self, device):
-        device = torch.device(device)
-        if device not in self._masks_dev:
-            self._masks_dev[device] = torch.from_numpy(self.masks_host).to(device)
-        return self._masks_dev[device]
+        masks = _HostTable(a)
+        self.masks_host, self.masks_on = masks.host, masks.on
 
 
 def _clamped(grid, what):
@@ -1259,22 +1252,44 @@ def _clamped(grid, what):
         raise _lib.MdxError(f"{what}: a wrapped grid (wrap_x) is read by window_gather_rows / window_average_regions")
 
 
+def _gather_dims(canvas, grid):
+    """NB, C of a gather's canvas [NB, C, Hc, Wc]."""
+    if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
+        raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
+    return int(canvas.shape[0]), int(canvas.shape[1])
+
+
+def _window_out(out, shape, like):
+    """The caller's `out` if it has `shape`, a fresh tensor of like's dtype and device without one."""
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != shape:
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {shape}")
+    return out
+
+
+def _average_io(windows, grid, P, out, weights):
+    """NB, ld, out of an average of P rows per canvas row: windows [NB * P, h * w, ld], weights [h, w] or None, out
+    [NB, Hc * Wc, ld]."""
+    if windows.dim() != 3 or windows.shape[0] % P or windows.shape[1] != grid.h * grid.w:
+        raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {P}, {grid.h * grid.w}, ld]")
+    NB, ld = int(windows.shape[0]) // P, int(windows.shape[2])
+    if weights is not None and tuple(weights.shape) != (grid.h, grid.w):
+        raise _lib.MdxError(f"weights: shape {tuple(weights.shape)}, expected {(grid.h, grid.w)}")
+    return NB, ld, _window_out(out, (NB, grid.Hc * grid.Wc, ld), windows)
+
+
 def window_gather(canvas, grid, k0=0, n=None, out=None):
     """Windows k0 .. k0 + n - 1 of canvas [NB, C, Hc, Wc] fp32 as [NB * n, C, h, w], window kk of canvas row j in output row
     j * n + kk.  One launch."""
     _chk(canvas, f32, "canvas"); _chk(out, f32, "out")
     _clamped(grid, "window_gather")
-    if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
-        raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
-    NB, C = int(canvas.shape[0]), int(canvas.shape[1])
+    NB, C = _gather_dims(canvas, grid)
     k0 = int(k0)
     n = grid.N - k0 if n is None else int(n)
     if k0 < 0 or n < 1 or k0 + n > grid.N:
         raise _lib.MdxError(f"window_gather: windows [{k0}, {k0} + {n}) are not inside the grid of {grid.ny} x {grid.nx}")
-    if out is None:
-        out = torch.empty((NB * n, C, grid.h, grid.w), dtype=f32, device=canvas.device)
-    elif tuple(out.shape) != (NB * n, C, grid.h, grid.w):
-        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB * n, C, grid.h, grid.w)}")
+    out = _window_out(out, (NB * n, C, grid.h, grid.w), canvas)
     _lib.check(_lib.load().mdx_window_gather_f32(_ptr(canvas), _ptr(out), _ptr(grid.on(canvas.device)), grid._host_ptr(), grid.ny,
                                                  grid.nx, k0, n, NB, C, grid.Hc, grid.Wc, grid.h, grid.w, _stream()),
                "mdx_window_gather_f32")
@@ -1287,15 +1302,7 @@ def window_average(windows, grid, C, out=None, weights=None):
     uniform.  Channels [C, ld) of the result are 0.  One launch."""
     _chk(windows, f16, "windows"); _chk(out, f16, "out"); _chk(weights, f32, "weights")
     _clamped(grid, "window_average")
-    if windows.dim() != 3 or windows.shape[0] % grid.N or windows.shape[1] != grid.h * grid.w:
-        raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {grid.N}, {grid.h * grid.w}, ld]")
-    NB, ld = int(windows.shape[0]) // grid.N, int(windows.shape[2])
-    if weights is not None and tuple(weights.shape) != (grid.h, grid.w):
-        raise _lib.MdxError(f"weights: shape {tuple(weights.shape)}, expected {(grid.h, grid.w)}")
-    if out is None:
-        out = torch.empty((NB, grid.Hc * grid.Wc, ld), dtype=f16, device=windows.device)
-    elif tuple(out.shape) != (NB, grid.Hc * grid.Wc, ld):
-        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB, grid.Hc * grid.Wc, ld)}")
+    NB, ld, out = _average_io(windows, grid, grid.N, out, weights)
     _lib.check(_lib.load().mdx_window_average_f16(_ptr(windows), _ptr(out), _ptr(weights), 0 if weights is None else weights.numel(),
                                                   _ptr(grid.on(windows.device)), grid._host_ptr(), grid.ny, grid.nx, NB, int(C), ld,
                                                   grid.Hc, grid.Wc, grid.h, grid.w, _stream()), "mdx_window_average_f16")
@@ -1307,17 +1314,13 @@ def window_gather_rows(canvas, grid, rows, out=None):
     [NB, C, Hc, Wc] fp32 as [NB * n, C, h, w], window rows[i] of canvas row j in output row j * n + i.  Reads a wrapped grid
     (grid.wrap_x) as well as a clamped one.  One launch."""
     _chk(canvas, f32, "canvas"); _chk(out, f32, "out")
-    if canvas.dim() != 4 or tuple(canvas.shape[2:]) != (grid.Hc, grid.Wc):
-        raise _lib.MdxError(f"canvas: shape {tuple(canvas.shape)}, expected [NB, C, {grid.Hc}, {grid.Wc}]")
+    NB, C = _gather_dims(canvas, grid)
     if not isinstance(rows, WindowRows):
         rows = WindowRows(rows)
-    NB, C, n = int(canvas.shape[0]), int(canvas.shape[1]), len(rows)
+    n = len(rows)
     if n < 1 or rows.lo < 0 or rows.hi >= grid.N:              # (the C entry checks the host table itself, entry by entry)
         raise _lib.MdxError(f"window_gather_rows: rows {rows.host.tolist()} are not inside the grid of {grid.ny} x {grid.nx}")
-    if out is None:
-        out = torch.empty((NB * n, C, grid.h, grid.w), dtype=f32, device=canvas.device)
-    elif tuple(out.shape) != (NB * n, C, grid.h, grid.w):
-        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB * n, C, grid.h, grid.w)}")
+    out = _window_out(out, (NB * n, C, grid.h, grid.w), canvas)
     _lib.check(_lib.load().mdx_window_gather_rows_f32(_ptr(canvas), _ptr(out), _ptr(grid.on(canvas.device)), grid._host_ptr(),
                                                       grid.ny, grid.nx, _ptr(rows.on(canvas.device)), rows._host_ptr(), n,
                                                       int(grid.wrap_x), NB, C, grid.Hc, grid.Wc, grid.h, grid.w, _stream()),
@@ -1334,15 +1337,7 @@ def window_average_regions(windows, grid, C, plan=None, out=None, weights=None):
     if plan is not None and plan.grid is not grid:
         raise _lib.MdxError("window_average_regions: the plan was made for another grid")
     P = grid.N if plan is None else plan.P
-    if windows.dim() != 3 or windows.shape[0] % P or windows.shape[1] != grid.h * grid.w:
-        raise _lib.MdxError(f"windows: shape {tuple(windows.shape)}, expected [NB * {P}, {grid.h * grid.w}, ld]")
-    NB, ld = int(windows.shape[0]) // P, int(windows.shape[2])
-    if weights is not None and tuple(weights.shape) != (grid.h, grid.w):
-        raise _lib.MdxError(f"weights: shape {tuple(weights.shape)}, expected {(grid.h, grid.w)}")
-    if out is None:
-        out = torch.empty((NB, grid.Hc * grid.Wc, ld), dtype=f16, device=windows.device)
-    elif tuple(out.shape) != (NB, grid.Hc * grid.Wc, ld):
-        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(NB, grid.Hc * grid.Wc, ld)}")
+    NB, ld, out = _average_io(windows, grid, P, out, weights)
     dev = windows.device
     if plan is None:
         tables, masks, R = (None,) * 5, None, 0

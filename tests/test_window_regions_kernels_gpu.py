@@ -1,4 +1,5 @@
-"""mdx_window_gather_rows_f32 and mdx_window_average_regions_f16 (csrc/window.hip) on the GPU.  The gather is a copy: torch.equal
+"""mdx_window_gather_rows_f32 and mdx_window_average_regions_f16 (csrc/window.hip; they share their kernels with the two plain
+entries, which are held equal to them here) on the GPU.  The gather is a copy: torch.equal
 to torch.roll plus slicing, with a window that straddles the seam, in its float4 and its scalar form, for a row table with
 repeats and for a sub-range, with a NaN sentinel around what it may write.  The average without regions is held bit for bit to
 the numpy restatement of the stated arithmetic (wrapped) and to the existing entry (not wrapped; and with one all-ones region);
@@ -84,6 +85,26 @@ def test_gather_rows_on_a_clamped_grid_is_the_existing_gather():
     assert torch.equal(ops.window_gather_rows(x, g, range(1, 4)), ops.window_gather(x, g, 1, 3))
 
 
+@pytest.mark.parametrize("Wc,misalign", [(20, False), (18, False), (20, True)])
+def test_a_range_and_its_row_table_gather_the_same_bits(Wc, misalign):
+    """The two gather entries share one kernel: a proper sub-range, and the row table that names it, on a grid the float4 form
+    takes (x offsets 0 4 8 12), on one it cannot take (0 4 8 10), and on the first with the canvas 4 bytes off a 16-byte
+    boundary (the scalar form again); a NaN row before and after what may be written stays NaN."""
+    from minddiffusion_amd import ops
+    shape = (2, 4, 8, Wc)
+    g = ops.WindowGrid(shape[2:], (8, 8), (4, 4))
+    assert g.ox == ([0, 4, 8, 12] if Wc == 20 else [0, 4, 8, 10]) and g.N == 4
+    store = torch.randn(2 * 4 * 8 * Wc + 1, device=DEV, generator=torch.Generator(DEV).manual_seed(7))
+    x = store[1:].view(shape) if misalign else store[1:].view(shape).clone()
+    assert x.data_ptr() % 16 == (4 if misalign else 0)
+    k0, n = 1, 2
+    bufs = torch.full((2, 2 * n + 2, 4, 8, 8), float("nan"), device=DEV)
+    ops.window_gather(x, g, k0, n, out=bufs[0, 1:1 + 2 * n])
+    ops.window_gather_rows(x, g, range(k0, k0 + n), out=bufs[1, 1:1 + 2 * n])
+    assert torch.equal(bufs[0, 1:-1], bufs[1, 1:-1]) and torch.equal(bufs[0, 1:-1], U.gather_ref(x, g.oy, g.ox, 8, 8, k0, n))
+    assert bool(torch.isnan(bufs[:, 0]).all()) and bool(torch.isnan(bufs[:, -1]).all())
+
+
 # ------------------------------------------------------------------------------------------------ the uniform wrapped average
 @pytest.mark.parametrize("weighted", [False, True])
 @pytest.mark.parametrize("name", WRAPPED)
@@ -125,6 +146,53 @@ def test_no_regions_and_one_all_ones_region_are_the_existing_entry_bit_for_bit(s
     assert plan.pairs == [(k, 0) for k in range(g.N)]
     assert torch.equal(ops.window_average_regions(win, g, 4, plan=plan, weights=wts), want)  # R == 1, M == 1
     assert bool(torch.isfinite(want).all())
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("ld,C", [(8, 4), (16, 4), (16, 11)])
+def test_the_two_average_entries_agree_on_wider_rows_of_a_two_row_grid(ld, C, weighted):
+    """The two average entries share one kernel: ld == 16 is two 16-byte chunks per pixel, C == 11 ends inside the second."""
+    from minddiffusion_amd import ops
+    from minddiffusion_amd.ldm.models.diffusion.windowed import gaussian_weights
+    g = ops.WindowGrid((12, 20), (8, 8), (4, 4))
+    assert (g.ny, g.nx) == (2, 4)
+    win = torch.from_numpy(np.random.RandomState(ld + C).randn(2 * g.N, 64, ld).astype(np.float16)).to(DEV)
+    wts = gaussian_weights(8, 8).to(DEV) if weighted else None
+    want = ops.window_average(win, g, C, weights=wts)
+    assert torch.equal(ops.window_average_regions(win, g, C, weights=wts), want)
+    assert bool(torch.isfinite(want).all()) and want[..., :C].any() and not want[..., C:].any()
+
+
+# ------------------------------------------------------------------------------------------------ the wrapper's shared buffers
+def test_plain_and_region_calls_on_one_wrapper_do_not_leak_into_each_other():
+    """A plain clamped call in several chunks, a region call and a plain call again on ONE WindowedDiffusion -- they share the
+    chunk loop, the staging buffer and the input buffers -- are each what a fresh wrapper gives, bit for bit."""
+    import _vpred_util as V
+    from minddiffusion_amd.ldm.models.diffusion.windowed import WindowedDiffusion
+    model, cfg, _ = V.tiny_eps_model()
+    gen = torch.Generator(DEV).manual_seed(11)
+    x = torch.randn((1, 4, 8, 32), device=DEV, generator=gen)
+    x_in, t = torch.cat([x, x]).contiguous(), torch.full((2,), 500., device=DEV)
+    ctxs = [torch.randn((2, V.T, cfg["context_dim"]), device=DEV, generator=gen).half() for _ in range(3)]
+    masks = RU.region_masks("ramp", 8, 32)
+    masks[2, :, 16:] = 0.0                                            # the third region touches the left windows only
+    new = lambda: WindowedDiffusion(model, (8, 8), (4, 4), max_unet_batch=8)
+
+    def plain(wm):
+        out = wm.apply_model_nhwc(x_in, t, ctxs[0], cfg_dup=True).clone()
+        assert wm.chunks == [(0, 4), (4, 3)] and wm.pairs == [(k, None) for k in range(7)] and not wm.grid.wrap_x
+        return out
+
+    def regions(wm):
+        with wm.regions(torch.from_numpy(masks), ctxs):
+            out = wm.apply_model_nhwc(x_in, t, ctxs[0], cfg_dup=True).clone()
+        assert wm.pairs == RU.pair_list(masks, wm.grid.oy, wm.grid.ox, 8, 8) and 7 < len(wm.pairs) < 21 and len(wm.chunks) > 1
+        return out
+
+    wm = new()
+    first, both, again = plain(wm), regions(wm), plain(wm)
+    assert wm.evals == 3 and torch.equal(first, plain(new())) and torch.equal(both, regions(new())) and torch.equal(again, first)
+    assert not torch.equal(both, first) and bool(torch.isfinite(both).all())
 
 
 # ------------------------------------------------------------------------------------------------ regions
