@@ -764,6 +764,45 @@ int mdx_slot_blend_f32(const float* x0, const float* keep, float* img, const uns
                        unsigned draw0, const float* blend_ab, const int* blend_on, const int* slot_start, const int* slot_len,
                        int cap, int tick, int B, int C, int HW, mdx_stream_t s);
 
+/* ---- Separable resampling (not in the reference; csrc/resample.hip): the enlargement between the two passes of
+ * DiffusionPipeline.hires.  One table-driven kernel: the interpolation mode never reaches the device, only tap tables do
+ * (minddiffusion_amd/resample.py computes them in float64 and rounds once to fp32, as mdx_mask_feather_f32's taps travel).
+ * in [B][C][H_in][W_in], out [B][C][H_out][W_out]: NCHW fp32, contiguous.  Tables, all on the device: y_start[H_out] int32 and
+ * y_w[H_out][Ty] fp32 for the rows, x_start[W_out] and x_w[W_out][Tx] for the columns; a row of a table that needs fewer taps is
+ * padded with zero weights.  Tap k of output column j reads input column e(x_start[j] + k): e clamps to [0, W_in - 1] (replicate
+ * edge), or with wrap_x != 0 is the index mod W_in, non-negative.  Rows always clamp.  The arithmetic, fixed:
+ *   1. horizontal first:  t = 0; for k ascending:  t = fmaf(x_w[j][k], in[..][e(x_start[j] + k)], t)
+ *   2. t is kept in fp32
+ *   3. vertical over the t values of the rows e(y_start[i] + k), the same way with y_w
+ *   4. no atomics: an output element depends on its own sample and plane only.
+ * Inputs must be finite where a tap reads them, zero-weight padding included (0 * inf is NaN).  16-byte stores where
+ * W_out % 4 == 0 and out is 16-byte aligned, scalar ones otherwise: an element gets the same bits either way.
+ * One launch; a block owns a 16 x 32 tile of outputs of one plane and stages the horizontally resampled strip it needs in LDS.
+ * The strip is sized from the geometry, ceil(15 * H_in / H_out) + Ty + 2 input rows: tables whose 16 consecutive output rows
+ * reach further (none of resample.tap_table's do) give wrong values there, never an access outside `in`.
+ * Refused before any launch (MDX_E_INVALID): null pointers, non-positive extents, a plane of more than 2^30 pixels, B * C > 65535,
+ * Tx or Ty outside [1, MDX_RESAMPLE_MAX_TAPS] (32 covers antialiased bicubic down to x1/8 and Lanczos-3 down to x1/5), an out
+ * that overlaps in, a tile whose strip and tables would exceed the kernel's 40 KiB of LDS (a very large downscale: beyond
+ * about x1/20 with one tap, x1/15 with 32; the message says so). */
+#define MDX_RESAMPLE_MAX_TAPS 32
+int mdx_resample_f32(const float* in, float* out, int B, int C, int H_in, int W_in, int H_out, int W_out, const int* y_start,
+                     const float* y_w, int Ty, const int* x_start, const float* x_w, int Tx, int wrap_x, mdx_stream_t s);
+/* The resample fused onto the start of an img2img run (hires with per-sample seeds), one launch: with r the value
+ * mdx_resample_f32 computes,
+ *   z0 = scale * r                       (one fp32 multiply)
+ *   xt = fmaf(a, z0, b * n)              (the q-sample statement of mdx_q_sample_f32)
+ * n = noise[b][c][i][j], or with noise == NULL the value mdx_randn_f32 gives sample b at (seeds[b], stream, draw), scale 1 and no
+ * dropout, for the NCHW flat index of the element inside its OUTPUT sample [C][H_out][W_out].  A passed noise wins over seeds.
+ * z0_out, xt_out, noise: [B][C][H_out][W_out].  Either output may be NULL, not both; xt_out needs a noise source.  Bit for bit:
+ * scale = 1 makes z0_out mdx_resample_f32's output, and xt_out is mdx_randn_f32 followed by mdx_q_sample_f32 on z0_out -- the
+ * kernels run the same device bodies (csrc/rng_device.h, csrc/qsample_device.h).  16-byte accesses where W_out % 4 == 0 and the
+ * outputs and noise are 16-byte aligned, scalar ones otherwise: the same bits.  Refused: what mdx_resample_f32 refuses, no
+ * output, xt_out without noise and seeds, C * H_out * W_out > 2^34, outputs that overlap in, noise or each other. */
+int mdx_resample_noised_f32(const float* in, int B, int C, int H_in, int W_in, int H_out, int W_out, const int* y_start,
+                            const float* y_w, int Ty, const int* x_start, const float* x_w, int Tx, int wrap_x, float scale,
+                            float a, float b, const float* noise, const unsigned long long* seeds, unsigned stream, unsigned draw,
+                            float* z0_out, float* xt_out, mdx_stream_t s);
+
 /* ---- Windowed UNet evaluation (not in the reference; MultiDiffusion, Bar-Tal et al. 2023; csrc/window.hip): a latent canvas
  * larger than the resolution the UNet was trained at is evaluated as a batch of overlapping windows of that resolution, and the
  * outputs are averaged where windows overlap.

@@ -177,6 +177,11 @@ SIGNATURES = {
                                     c_long, c_void_p]),
     "mdx_slot_blend_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint, c_uint, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mdx_resample_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "mdx_resample_noised_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_uint, c_uint,
+                                        c_void_p, c_void_p, c_void_p]),
     "mdx_window_gather_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p]),
     "mdx_window_average_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

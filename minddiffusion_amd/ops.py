@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import resample as _resample
 from ._lib import GemmDesc, EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU, OUT_ROWMAJOR, OUT_TRANSPOSED  # noqa: F401
 from ._lib import EPI_PRELU, OUT_D2S2  # noqa: F401
 
@@ -1453,6 +1454,93 @@ def slot_blend(x0, keep, img, seeds, stream, draw0, blend_ab, blend_on, slot_sta
                                               _ptr(blend_ab), _ptr(blend_on), _ptr(slot_start), _ptr(slot_len),
                                               int(blend_ab.shape[1]), int(tick), B, C, H * W, _stream()), "mdx_slot_blend_f32")
     return img
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Separable resampling (include/mdx.h: mdx_resample_f32 / mdx_resample_noised_f32, csrc/resample.hip; the tables:
+# minddiffusion_amd/resample.py)
+_TAP_TABLES = {}
+
+
+def _tap_tables(n_in, n_out, mode, antialias, wrap, device):
+    """(start int32 [n_out], w fp32 [n_out, T]) of one axis on `device`, uploaded once per (n_in, n_out, mode, antialias, wrap,
+    device)."""
+    key = (int(n_in), int(n_out), mode, bool(antialias), bool(wrap), torch.device(device))
+    if key not in _TAP_TABLES:
+        start, w = _resample.tap_table(n_in, n_out, mode, antialias, wrap)
+        _TAP_TABLES[key] = (torch.from_numpy(start).to(device), torch.from_numpy(np.ascontiguousarray(w)).to(device))
+    return _TAP_TABLES[key]
+
+
+def _resample_args(name, x, size, mode, antialias, wrap_x):
+    _chk(x, f32, "x")
+    if x.dim() != 4:
+        raise _lib.MdxError(f"{name}: x must be [B, C, H, W], got shape {tuple(x.shape)}")
+    if mode not in _resample.MODES:
+        raise _lib.MdxError(f"{name}: mode must be one of {_resample.MODES}, got {mode!r}")
+    B, C, H, W = (int(d) for d in x.shape)
+    Ho, Wo = int(size[0]), int(size[1])
+    if Ho <= 0 or Wo <= 0:
+        raise _lib.MdxError(f"{name}: size must be positive, got {tuple(size)}")
+    try:
+        ys, yw = _tap_tables(H, Ho, mode, Ho < H if antialias is None else antialias, False, x.device)
+        xs, xw = _tap_tables(W, Wo, mode, Wo < W if antialias is None else antialias, wrap_x, x.device)
+    except ValueError as e:
+        raise _lib.MdxError(f"{name}: {e}") from None
+    tables = (_ptr(ys), _ptr(yw), int(yw.shape[1]), _ptr(xs), _ptr(xw), int(xw.shape[1]), int(bool(wrap_x)))
+    return (B, C, H, W, Ho, Wo), tables
+
+
+def resample(x, size, mode="bicubic", antialias=None, wrap_x=False, out=None):
+    """x [B, C, H, W] fp32 resampled to size = (H_out, W_out), one launch.  mode: "nearest" (the integer rule (i * n_in) // n_out),
+    "bilinear", "bicubic" (F.interpolate(align_corners=False)'s definitions, antialias as torch's antialias=True) or "lanczos3"
+    (always antialiased).  antialias None: on for an axis that shrinks, off otherwise.  wrap_x: columns wrap around (a panorama)
+    instead of replicating the edge; rows always replicate.  An axis that keeps its size is copied bit for bit."""
+    dims, tables = _resample_args("resample", x, size, mode, antialias, wrap_x)
+    B, C, _, _, Ho, Wo = dims
+    _chk(out, f32, "out")
+    if out is None:
+        out = torch.empty((B, C, Ho, Wo), dtype=f32, device=x.device)
+    elif tuple(out.shape) != (B, C, Ho, Wo):
+        raise _lib.MdxError(f"out: shape {tuple(out.shape)}, expected {(B, C, Ho, Wo)}")
+    _lib.check(_lib.load().mdx_resample_f32(_ptr(x), _ptr(out), *dims, *tables, _stream()), "mdx_resample_f32")
+    return out
+
+
+def resample_noised(x, size, a, b, *, scale=1.0, noise=None, seeds=None, stream=RNG_ENCODE, draw=0, mode="bicubic",
+                    antialias=None, wrap_x=False, z0_out=None, xt_out=None):
+    """The resample fused onto the start of an img2img run, one launch: (z0, xt) with z0 = scale * resample(x, size, ...) and
+    xt = a * z0 + b * n -- bit for bit q_sample(z0, n, a, b).  n: `noise` [B, C, H_out, W_out], or drawn per sample from `seeds`
+    (ints, or ops.seeds_tensor's tensor) at (stream, draw) -- the bits of randn_seeded(seeds, stream, draw, (C, H_out, W_out)), never stored.
+    Exactly one of noise and seeds.  z0_out / xt_out: a tensor to write, None for a fresh one, False to leave that output out
+    (not both; without xt no noise source is needed)."""
+    dims, tables = _resample_args("resample_noised", x, size, mode, antialias, wrap_x)
+    B, C, _, _, Ho, Wo = dims
+    if z0_out is False and xt_out is False:
+        raise _lib.MdxError("resample_noised: no output (z0_out and xt_out are both False)")
+    if xt_out is not False and (noise is None) == (seeds is None):
+        raise _lib.MdxError("resample_noised: pass exactly one of noise and seeds")
+    _chk(noise, f32, "noise")
+    for name, t in (("z0_out", z0_out), ("xt_out", xt_out)):
+        _chk(None if t is False else t, f32, name)
+    if seeds is not None:
+        if not isinstance(seeds, torch.Tensor):
+            seeds = seeds_tensor(seeds, x.device)
+        if tuple(seeds.shape) != (B,):
+            raise _lib.MdxError(f"resample_noised: {tuple(seeds.shape)} seeds for a batch of {B} (one per sample)")
+        _chk(seeds, torch.int64, "seeds")
+        if not (0 <= int(stream) < (1 << 31) and 0 <= int(draw) < (1 << 32)):
+            raise _lib.MdxError(f"resample_noised: stream must be in [0, 2^31) and draw in [0, 2^32), got {stream!r}, {draw!r}")
+    shape = (B, C, Ho, Wo)
+    fresh = lambda t: None if t is False else torch.empty(shape, dtype=f32, device=x.device) if t is None else t
+    z0_out, xt_out = fresh(z0_out), fresh(xt_out)
+    for name, t in (("noise", noise), ("z0_out", z0_out), ("xt_out", xt_out)):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.MdxError(f"{name}: shape {tuple(t.shape)}, expected {shape}")
+    _lib.check(_lib.load().mdx_resample_noised_f32(_ptr(x), *dims, *tables, float(scale), float(a), float(b), _ptr(noise),
+                                                   _ptr(seeds), int(stream), int(draw), _ptr(z0_out), _ptr(xt_out), _stream()),
+               "mdx_resample_noised_f32")
+    return z0_out, xt_out
 
 
 # ---------------------------------------------------------------------------------------------------------------

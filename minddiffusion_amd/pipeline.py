@@ -39,6 +39,7 @@ class DiffusionPipeline:
                 sampler = (DDIMSampler if sampler == "ddim" else PLMSSampler)(model)
         self.sampler = sampler
         self.seam_cols = 0            # latent columns of circular padding per side around the decoder (windowed(wrap_x=True))
+        self._hires_kept = {}         # hires(): the inner pipeline of a windowed one, and one windowed pipeline per base size
 
     def start_noise(self, batch, shape, seed):
         """numpy RandomState(seed).randn -- the reference's own practice for reproducible x_T
@@ -452,6 +453,123 @@ class DiffusionPipeline:
         with self._region_scope("img2img", regions, c, uc, scale, z0.shape[2:], image_hw):
             samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, callback, img_callback,
                                         self._sampler_kw(guidance_rescale, seeds), mask=mask, x0=z0)
+        return self._decoded(samples) if decode else samples
+
+    # ---- hires fix: sample at the trained size, enlarge, re-sample the end of the schedule at the target size
+    HIRES_UPSCALERS = {"latent-nearest": "nearest", "latent-bilinear": "bilinear", "latent-bicubic": "bicubic",
+                       "image-bicubic": "bicubic", "image-lanczos3": "lanczos3"}
+
+    @property
+    def _windowed(self):
+        from .ldm.models.diffusion.windowed import WindowedDiffusion
+        return isinstance(self.model, WindowedDiffusion)
+
+    def upscale_latent(self, z, H, W, mode="bicubic"):
+        """z [B, C, h, w] resampled to the latent grid of an H x W image, [B, C, H / 8, W / 8]: one ops.resample launch.  On a
+        wrap_x pipeline the columns wrap around, so a panorama still closes."""
+        if H % 8 or W % 8 or H < 8 or W < 8:
+            raise MdxError(f"upscale_latent: H and W are in image pixels, positive multiples of 8, got {H!r} x {W!r}")
+        z = z.to(device=self.device, dtype=torch.float32).contiguous()
+        return ops.resample(z, (H // 8, W // 8), mode, wrap_x=bool(getattr(self.model, "wrap_x", False)))
+
+    def _hires_pipelines(self, H, W, base, second):
+        """(first, second): the pipeline of the first pass -- this one, or on a windowed pipeline one on its inner, un-windowed
+        model -- and of the second: `second` when given, this one when the target is the base size or this one is windowed,
+        else self.windowed(window=base), built once per base and kept so that its plans survive."""
+        kept = self._hires_kept
+        first = self
+        if self._windowed:
+            if "inner" not in kept:
+                kept["inner"] = DiffusionPipeline(self.model.inner, self._session_sampler(), self.device)
+            first = kept["inner"]
+        if second is None:
+            if (H, W) == base or self._windowed:
+                second = self
+            else:
+                if base not in kept:
+                    kept[base] = self.windowed(window=base)
+                second = kept[base]
+        return first, second
+
+    def hires(self, prompts=None, c=None, uc=None, H=1024, W=1024, base=(512, 512), upscaler="latent-bicubic", strength=0.6,
+              steps=50, hires_steps=None, scale=9.0, eta=0.0, seed=42, seeds=None, guidance_rescale=0.0, second=None,
+              decode=False, return_base=False, regions=None):
+        """Hires fix: a full `steps`-step run at base = (H0, W0), where the checkpoint composes well; the result enlarged to
+        H x W; and the last t_enc = int(strength * (hires_steps or steps)) steps of the schedule run again at the target size.
+
+        First pass: exactly self(..., H=base[0], W=base[1], steps=steps, ...); on a windowed pipeline it runs on the inner,
+        un-windowed model.  upscaler: "latent-nearest" / "latent-bilinear" / "latent-bicubic" resample the latent
+        (ops.resample; with seeds one fused ops.resample_noised launch that also noises it, stream ops.RNG_ENCODE, draw 0 at the
+        new shape -- what img2img(init_latent=, seeds=) draws); "image-bicubic" / "image-lanczos3" decode, clamp to [-1, 1],
+        resample the image and encode it as img2img(init_image=) does; a callable img [B, 3, h, w] in [-1, 1] ->
+        [B, 3, H', W'] (an SRGAN.sr_handle, anything else) takes the resample's place.  Second pass: on `second` -- default: this
+        pipeline when (H, W) == base or it is windowed, else self.windowed(window=base), built once and kept -- through the same
+        partial-run path as img2img, so samplers, v-prediction, guidance rescale, scale / guidance_rescale lists and seeds all
+        carry over; on a wrap_x second pipeline the upscale wraps around too.  regions: regional prompts of the second pass.
+        return_base: (result, first-pass latent).  Single rank; the hybrid (9-channel) model is refused."""
+        guidance_rescale = self.check_request_lists("hires", None, steps, scale, guidance_rescale, steps_list=False)
+        if hires_steps is not None and (isinstance(hires_steps, bool) or not isinstance(hires_steps, (int, np.integer))
+                                        or hires_steps < 1):
+            raise ValueError(f"hires: hires_steps must be a positive int or None, got {hires_steps!r}")
+        hsteps = int(steps if hires_steps is None else hires_steps)
+        self._check_strength("hires", strength, hsteps)
+        if D.world()[1] > 1:
+            raise MdxError("hires runs on a single rank (the sharded form is not built)")
+        try:
+            base = (int(base[0]), int(base[1]))
+        except (TypeError, IndexError, ValueError):
+            raise MdxError(f"hires: base is an (H, W) pair in image pixels, got {base!r}") from None
+        if any(v < 8 or v % 8 for v in (H, W) + base):
+            raise MdxError(f"hires: H, W and base are in image pixels, positive multiples of 8, got {H!r} x {W!r}, base {base!r}")
+        if getattr(getattr(self.model, "model", None), "conditioning_key", "crossattn") == "hybrid":
+            raise MdxError("hires: the hybrid (9-channel) inpainting model is not supported (inpaint() is its entry point)")
+        if not callable(upscaler) and upscaler not in self.HIRES_UPSCALERS:
+            raise ValueError(f"hires: upscaler must be one of {sorted(self.HIRES_UPSCALERS)} or a callable, got {upscaler!r}")
+        first, second = self._hires_pipelines(H, W, base, second)
+        second._check_regions_allowed("hires", regions)
+        c, uc = self._encoded(prompts, c, uc)
+        z_base = first(c=c, uc=uc, H=base[0], W=base[1], steps=steps, scale=scale, eta=eta, seed=seed, seeds=seeds,
+                       guidance_rescale=guidance_rescale)
+        wrap = bool(getattr(second.model, "wrap_x", False))
+        kw = dict(strength=strength, c=c, uc=uc, steps=hsteps, scale=scale, eta=eta, seed=seed, seeds=seeds,
+                  guidance_rescale=guidance_rescale, regions=regions, decode=decode)
+        if callable(upscaler) or upscaler.startswith("image-"):
+            img = torch.clamp(self.model.decode_first_stage(z_base).to(torch.float32), -1.0, 1.0).contiguous()
+            f = int(img.shape[-1]) // int(z_base.shape[-1])           # (the VAE's own factor: 8 for SD)
+            size = (H // 8 * f, W // 8 * f)
+            if callable(upscaler):
+                big = upscaler(img)
+                if not (isinstance(big, torch.Tensor) and tuple(big.shape) == tuple(img.shape[:2]) + size):
+                    raise MdxError(f"hires: the upscaler returned {tuple(getattr(big, 'shape', ()))}, expected "
+                                   f"{tuple(img.shape[:2]) + size}")
+            else:
+                big = ops.resample(img, size, self.HIRES_UPSCALERS[upscaler], wrap_x=wrap)
+            out = second.img2img(init_image=big, **kw)
+        elif seeds is None:
+            z_up = ops.resample(z_base, (H // 8, W // 8), self.HIRES_UPSCALERS[upscaler], wrap_x=wrap)
+            out = second.img2img(init_latent=z_up, **kw)
+        else:
+            out = second._hires_seeded(z_base, (H, W), self.HIRES_UPSCALERS[upscaler], wrap, strength, c, uc, hsteps, scale, eta,
+                                       seeds, guidance_rescale, regions, decode)
+        return (out, z_base) if return_base else out
+
+    def _hires_seeded(self, z_base, hw, mode, wrap, strength, c, uc, steps, scale, eta, seeds, guidance_rescale, regions, decode):
+        """img2img(init_latent=resample(z_base), seeds=) with the resample, the seeded draw and the q-sample as ONE launch
+        (ops.resample_noised): the same bits, two launches fewer, and neither the enlarged latent nor the noise is stored (no
+        mask blends here, so the start latent is all the run needs)."""
+        t_enc = self._check_strength("hires", strength, steps)
+        B = int(c.shape[0])
+        self.check_request_lists("hires", B, steps, scale, guidance_rescale, steps_list=False)
+        seeds = self.check_seeds(seeds, B)
+        if z_base.shape[0] != B:
+            raise MdxError(f"hires: {z_base.shape[0]} first-pass latents but {B} conditionings")
+        c, uc = self._on_device(c, uc, B)
+        start, a, b = self._partial_start(steps, t_enc, eta)
+        latent_hw = (hw[0] // 8, hw[1] // 8)
+        _, x_enc = ops.resample_noised(z_base, latent_hw, a, b, seeds=ops.seeds_tensor(seeds, self.device), stream=ops.RNG_ENCODE,
+                                       draw=0, mode=mode, wrap_x=wrap, z0_out=False)
+        with self._region_scope("hires", regions, c, uc, scale, latent_hw, hw):
+            samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, None, None, self._sampler_kw(guidance_rescale, seeds))
         return self._decoded(samples) if decode else samples
 
     # ---- inpainting: wukong-huahua/inpaint.py, image and mask in, composited image out
