@@ -20,16 +20,17 @@ input batch once, only the latent channels are refreshed per step.  `mask` / `x0
 Differences from the reference, both on the fp32 side of its fp16 arithmetic: the time grid and the schedule scalars
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
+One loop: schedule.dpm_steps gives every sample's launches, and the loop launches from a schedule.ScalarSteps (scalar S, scale and
+rescale: kernel arguments) or from a StepTable merged from the samples' plans and uploaded once (any of them per sample).
 """
 import numpy as np
 import torch
 
-from ..... import ops
 from ....._lib import MdxError
-from ..guided import (GuidedModel, StepTable, dpm_model_point, dpm_step_scalars, per_request, split_conditioning,
+from ..guided import (GuidedModel, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent, split_conditioning,
                       start_latent)
-from ..plms import check_guidance_rescale, check_seed_sources, check_seeds, noised_latent
-from .dpm_solver import NoiseScheduleVP, multistep_2m_plan
+from ..schedule import ScalarSteps, dpm_steps, per_request, pred_type, step_table
+from .dpm_solver import NoiseScheduleVP
 
 
 class DPMSolverSampler:
@@ -102,65 +103,31 @@ class DPMSolverSampler:
         size = (batch_size,) + tuple(shape)
         img = start_latent(x_T, check_seeds(seeds, batch_size, dev), size, dev, self.generator)
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
-        if per is not None:
-            return self._sample_per_request(ns, per, img, batch_size, shape, cond, uc, c_cat, uc_cat, dev, t_start, callback,
-                                            img_callback)
-        scale = float(unconditional_guidance_scale)
-        plan = multistep_2m_plan(ns, S, order=2 if S >= 2 else 1, lower_order_final=True, t_start=t_start)
-        # (S fractional timesteps; model_wrapper :316-322 builds the [uncond; cond] batch)
-        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
-                             [p["t_input"] for p in plan])
-        x0_bufs = [torch.empty_like(img), torch.empty_like(img)]    # data predictions at the last two grid points
-        x_next = torch.empty_like(img)
-        # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, in the step launch
-        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
-        for k, p in enumerate(plan):
-            eps_u, eps_c = guided(img, k)
-            cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
-            update = dpm_step_scalars(p) + (prev if p["c1"] != 0.0 else None, None, x_next, cur)
-            ops.sampler_update(img, eps_u, eps_c, scale, pred_type, [], (1., 0., 0., 0.), update, guidance_rescale, None,
-                               *dpm_model_point(p))
-            img, x_next = x_next, img
-            if callback:
-                callback(k)
-            if img_callback:
-                img_callback(cur, k)
-        return img, None
-
-    @staticmethod
-    def _step_table(ns, steps, scales, rescales, guided, t_start=None):
-        """(StepTable, model-input timesteps [n_calls, B], loop iterations) of a per-request run: sample b's rows are the
-        scalars of its own S[b]-step plan on iterations 0 .. S[b] - 1, inactive afterwards."""
-        by_steps = {s: multistep_2m_plan(ns, s, order=2 if s >= 2 else 1, lower_order_final=True, t_start=t_start)
-                    for s in sorted(set(steps))}
-        plans = [by_steps[s] for s in steps]
-        total = max(steps)
-        table = StepTable(scales, rescales, guided)
-        for k in range(total):
-            table.append([(dpm_model_point(pl[k]), (1., 0., 0., 0.), dpm_step_scalars(pl[k])) if k < len(pl) else None
-                          for pl in plans])
-        t_rows = [[pl[min(k, len(pl) - 1)]["t_input"] for pl in plans] for k in range(total)]      # ended: its last timestep
-        return table, np.array(t_rows, dtype=np.float32), total
-
-    def _sample_per_request(self, ns, per, img, batch_size, shape, cond, uc, c_cat, uc_cat, dev, t_start, callback,
-                            img_callback):
-        """sample() with per-sample S / scale / rescale (`per`, checked): the same loop on a StepTable.  Sample b's rows are
-        the scalars of its own plan (one multistep_2m_plan per distinct S); its previous data prediction is read only while
-        its row's c1 is non-zero, so a sample on its first-order final step ignores the pointer that is live for the others.
-        The data predictions ping-pong between two buffers and the launch writes only active rows, so on the iteration a
-        sample ends its last prediction is copied into the other buffer too: from then on both hold it, and whichever one
-        img_callback is handed shows the finished sample's last value."""
-        table, t_rows, total = self._step_table(ns, *per, not (uc is None and uc_cat is None), t_start)
-        ending = {k: [b for b, s in enumerate(per[0]) if s - 1 == k] for k in range(total - 1)}
-        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, per[1], dev, t_rows)
-        table.upload(dev)
+        # the launches of the run (schedule.dpm_steps) behind one surface: kernel arguments, or per request the rows of a table.
+        # Either way a sample's previous data prediction is read only while its own float32 c1 is non-zero.
+        counts = [S] * batch_size if per is None else per[0]
+        by_steps = {s: dpm_steps(ns, s, t_start) for s in sorted(set(counts))}
+        if per is None:
+            scale, total = float(unconditional_guidance_scale), S
+            steps, t_rows = ScalarSteps(by_steps[S], scale, guidance_rescale), [s.t_input for s in by_steps[S]]
+        else:
+            scale = per[1]
+            steps, t_rows, total = step_table([by_steps[s] for s in counts], scale, per[2], not (uc is None and uc_cat is None))
+            steps.upload(dev)
+        # (model_wrapper :316-322 builds the [uncond; cond] batch)
+        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
+        # The data predictions ping-pong between two buffers and a table launch writes only active rows, so on the iteration a
+        # sample ends its last prediction is copied into the other buffer too: whichever one img_callback is handed shows the
+        # finished sample's last value.  (Samples that end with the run -- all of them, with one S -- need no copy.)
+        ending = {k: [b for b, s in enumerate(counts) if s - 1 == k] for k in range(total - 1)}
         x0_bufs = [torch.empty_like(img), torch.empty_like(img)]
         x_next = torch.empty_like(img)
-        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
+        # model_wrapper, model_type "v" (dpm_solver.py:281-284): eps = alpha_t v + sigma_t x, in the step launch
+        pred = pred_type(self.model)
         for k in range(total):
             eps_u, eps_c = guided(img, k)
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
-            table.launch(k, img, eps_u, eps_c, pred_type, [], prev if table.any_sigma[k] else None, None, x_next, cur)
+            steps.launch(k, img, eps_u, eps_c, pred, [], prev if steps.any_sigma[k] else None, None, x_next, cur)
             for b in ending.get(k, ()):
                 prev[b].copy_(cur[b])
             img, x_next = x_next, img

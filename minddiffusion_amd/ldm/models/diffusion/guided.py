@@ -1,6 +1,7 @@
 """What PLMSSampler, DDIMSampler and DPMSolverSampler do before and inside their loops in the same way: the conditioning a
-caller may hand over (split_conditioning), the start latent (start_latent), and the model call of one step on the
-classifier-free-guidance batch (GuidedModel)."""
+caller may hand over (split_conditioning), the start latent and the other draws of a run with the checks of their sources
+(start_latent, check_seed_sources / check_seeds, noised_latent, _Draws; check_guidance_rescale), and the model call of one step
+on the classifier-free-guidance batch (use_cfg, GuidedModel).  Which launches a run makes with which scalars is schedule.py's."""
 import os
 
 import numpy as np
@@ -72,142 +73,91 @@ def start_latent(x_T, seeds, size, dev, generator):
     return torch.as_tensor(x_T).to(device=dev, dtype=torch.float32).contiguous().clone()
 
 
-# ---- the scalars of one fused step launch.  The scalar path hands them to ops.sampler_update, the per-request path writes
-# them into a StepTable row: both call these functions, so a row holds the very float32 the scalar call would have passed.
-PLMS_FIRST, PLMS_SECOND = (1., 0., 0., 0.), (.5, .5, 0., 0.)        # pseudo improved Euler (plms.py:231-235)
-PLMS_AB = ((1., 0., 0., 0.),                                         # no history: DDIM
-           (3. / 2, -1. / 2, 0., 0.),                                # Adams-Bashforth 2, plms.py:236-238
-           (23. / 12, -16. / 12, 5. / 12, 0.),                       # AB-3, plms.py:239-241
-           (55. / 24, -59. / 24, 37. / 24, -9. / 24))                # AB-4, plms.py:242-244
+def check_guidance_rescale(value):
+    """`guidance_rescale` (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4) as a float in
+    [0, 1]; anything else, NaN included, is a ValueError."""
+    phi = float(value)
+    if not 0. <= phi <= 1.:
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {value!r}")
+    return phi
 
 
-def ddim_step_scalars(alphas, alphas_prev, sqrt_one_minus_alphas, sigmas, index):
-    """(sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma) of get_x_prev_and_pred_x0 (plms.py:210-228) at grid
-    `index`, float32."""
-    a_t, a_prev = np.float32(alphas[index]), np.float32(alphas_prev[index])
-    sigma_t = np.float32(sigmas[index])
-    return (np.sqrt(a_t), np.float32(sqrt_one_minus_alphas[index]), np.sqrt(a_prev),
-            np.sqrt(np.float32(1.) - a_prev - sigma_t ** 2), sigma_t)
+def check_seed_sources(seeds, generator=None, **injected):
+    """A second source for the draws that `seeds=` covers -- the sampler's generator, or one of the test-injection keywords -- is a
+    caller's mistake: ValueError."""
+    if seeds is None:
+        return
+    if generator is not None:
+        raise ValueError("seeds= and a sampler generator are two sources for the same draws: pass one of them")
+    given = sorted(k for k, v in injected.items() if v is not None)
+    if given:
+        raise ValueError(f"seeds= and {', '.join(given)}= are two sources for the same draws: pass one of them")
 
 
-def dpm_step_scalars(p):
-    """The same five for update p of multistep_2m_plan, x_next = A x + c0 x0 + c1 x0_prev written as the step kernel's
-    sqrt_a_prev * pred_x0 + dir_coef * e' + sigma * noise (noise = x0_prev), float32."""
-    f = np.float32
-    return f(p["alpha"]), f(p["sigma"]), f(p["A"] * p["alpha"] + p["c0"]), f(p["A"] * p["sigma"]), f(p["c1"])
-
-
-def dpm_model_point(p):
-    """(alpha, sigma) where update p evaluates the model: the v -> eps conversion's coefficients, float32."""
-    return np.float32(p["alpha"]), np.float32(p["sigma"])
-
-
-# ---- per-request parameters: `scale`, `guidance_rescale` and `steps` as one value per sample of the batch
-def as_sequence(value):
-    """None for a scalar, else the list of a sequence / 1-d array / 1-d tensor."""
-    if isinstance(value, torch.Tensor):
-        return None if value.dim() == 0 else value.detach().cpu().tolist() if value.dim() == 1 else value
-    if isinstance(value, np.ndarray):
-        return None if value.ndim == 0 else value.tolist() if value.ndim == 1 else value
-    return list(value) if isinstance(value, (list, tuple)) else None
-
-
-def per_request(steps, scale, guidance_rescale, batch):
-    """None when all three are scalars (the scalar path); else (steps, scales, rescales) as lists of `batch` values -- a
-    scalar among them repeated -- checked: lengths equal the batch, every steps[b] an int >= 1, every rescale in [0, 1],
-    every scale finite.  `steps` None: the step count is not per request here (a run on a schedule already made)."""
-    seqs = {"steps": as_sequence(steps), "scale": as_sequence(scale), "guidance_rescale": as_sequence(guidance_rescale)}
-    if all(v is None for v in seqs.values()):
+def check_seeds(seeds, batch, device):
+    """`seeds=` of the samplers: None stays None; otherwise the int64 device tensor of `batch` per-sample seeds
+    (ops.seeds_tensor)."""
+    if seeds is None:
         return None
-    for name, v in seqs.items():
-        if v is not None and (not isinstance(v, list) or len(v) != batch):
-            n = len(v) if isinstance(v, list) else tuple(v.shape)
-            raise MdxError(f"{name}: {n} values for a batch of {batch}")
-    out_steps = None
-    if steps is not None:
-        out_steps = seqs["steps"] if seqs["steps"] is not None else [steps] * batch
-        for s in out_steps:      # an int: no bool, no float (4.0, NaN and inf included)
-            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or int(s) < 1:
-                raise ValueError(f"steps: every entry must be an int >= 1, got {s!r}")
-        out_steps = [int(s) for s in out_steps]
-    scales = [float(s) for s in (seqs["scale"] if seqs["scale"] is not None else [scale] * batch)]
-    if not all(np.isfinite(scales)):
-        raise ValueError(f"scale: every entry must be finite, got {scales!r}")
-    phis = seqs["guidance_rescale"] if seqs["guidance_rescale"] is not None else [guidance_rescale] * batch
-    for phi in phis:
-        if not 0. <= float(phi) <= 1.:
-            raise ValueError(f"guidance_rescale must be in [0, 1], got {phi!r}")
-    return out_steps, scales, [float(phi) for phi in phis]
+    seeds = ops.seeds_tensor(seeds, device)
+    if seeds.shape[0] != batch:
+        raise MdxError(f"seeds: {seeds.shape[0]} seeds for a batch of {batch}")
+    return seeds
 
 
-class StepTable:
-    """Every per-sample scalar of every fused step launch of one run, as ops.sampler_step_table reads it: a sampler appends, per
-    model evaluation and in loop order, the rows it would otherwise have passed as scalars; upload() then makes ONE
-    [n_calls, B, ops.STEP_ROW] device tensor, and launch k reads slice k of it.  Pure numpy until upload().
+def noised_latent(x0, a, b, noise, generator, seeds=None):
+    """stochastic_encode of every sampler: a * x0 + b * noise as one ops.q_sample launch into a fresh tensor; `noise` None is
+    drawn per sample from `seeds` (stream ops.RNG_ENCODE, draw 0), or without seeds from `generator`."""
+    if not (isinstance(x0, torch.Tensor) and x0.is_cuda):
+        raise MdxError("stochastic_encode: x0 must be a CUDA(HIP) tensor [B, C, H, W]")
+    x0 = x0.to(torch.float32).contiguous()
+    check_seed_sources(seeds, generator)
+    seeds = check_seeds(seeds, x0.shape[0], x0.device)
+    if noise is None and seeds is not None:
+        noise = ops.randn_seeded(seeds, ops.RNG_ENCODE, 0, tuple(x0.shape[1:]))
+    elif noise is None:
+        noise = torch.randn(x0.shape, device=x0.device, dtype=torch.float32, generator=generator)
+    noise = torch.as_tensor(noise).to(device=x0.device, dtype=torch.float32).contiguous()
+    return ops.q_sample(x0, noise, a, b)
 
-    scales / rescales: the guidance scale and guidance rescale of every sample.  guided: whether the run has an unconditional
-    half to combine (without one no row rescales, as in ops.sampler_update)."""
 
-    def __init__(self, scales, rescales, guided=True):
-        self.scales = np.asarray(scales, np.float32)
-        self.rescales = np.asarray(rescales, np.float32) if guided else np.zeros(len(scales), np.float32)
-        self.batch = int(self.scales.shape[0])
-        if self.rescales.shape != (self.batch,):
-            raise MdxError(f"StepTable: {self.rescales.shape[0]} guidance rescales for a batch of {self.batch}")
-        self.calls = []
-        self.uploads = 0
-        self.device_table = None
+class _Draws:
+    """The N(0, 1) draws inside the loop: per sample from `seeds` (one ops.randn_seeded launch each), else the injected
+    tensors (tests feed the oracle the same ones), else the sampler's generator."""
 
-    def append(self, rows):
-        """rows: one entry per sample -- None for a sample whose schedule has ended (an inactive row), else
-        (model_point, coef4, update5): (sqrt_at_model, sqrt_one_minus_at_model), the multistep coefficients, and
-        (sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma).  Returns the call's index."""
-        if self.device_table is not None:
-            raise MdxError("StepTable: append() after upload()")
-        if len(rows) != self.batch:
-            raise MdxError(f"StepTable: {len(rows)} rows for a batch of {self.batch}")
-        t = np.zeros((self.batch, ops.STEP_ROW), np.float32)
-        for b, row in enumerate(rows):
-            if row is None:
-                continue
-            model_point, coef, update = row
-            t[b, ops.STEP_ACTIVE] = 1.
-            t[b, ops.STEP_CFG_SCALE] = self.scales[b]
-            t[b, ops.STEP_RESCALE] = self.rescales[b]
-            t[b, ops.STEP_SQRT_AT_MODEL:ops.STEP_SQRT_ONE_MINUS_AT_MODEL + 1] = [float(v) for v in model_point]
-            t[b, ops.STEP_C0:ops.STEP_C0 + 4] = [float(v) for v in coef]
-            t[b, ops.STEP_SQRT_AT:ops.STEP_SIGMA + 1] = [float(v) for v in update]
-        self.calls.append(t)
-        return len(self.calls) - 1
+    def __init__(self, seeds, generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout):
+        self.seeds, self.generator, self.dev, self.shape = seeds, generator, dev, tuple(shape)
+        self.step_noises, self.dropout_masks, self.blend_noises = step_noises, dropout_masks, blend_noises
+        self.temperature, self.noise_dropout = temperature, noise_dropout
+        self.steps_drawn = 0
 
-    def host(self):
-        """The validated [n_calls, B, STEP_ROW] float32 array."""
-        t = np.stack(self.calls) if self.calls else np.zeros((0, self.batch, ops.STEP_ROW), np.float32)
-        if not np.isfinite(t).all():
-            k, b, j = (int(v[0]) for v in np.nonzero(~np.isfinite(t)))
-            raise ValueError(f"StepTable: call {k}, sample {b}: entry {j} is not finite")
-        on = t[..., ops.STEP_ACTIVE] != 0
-        phi = t[..., ops.STEP_RESCALE]
-        if ((phi < 0) | (phi > 1))[on].any():
-            raise ValueError("StepTable: guidance_rescale must be in [0, 1]")
-        if (t[..., ops.STEP_SQRT_AT][on] == 0).any():
-            raise ValueError("StepTable: sqrt_at == 0 on an active row (pred_x0 divides by it)")
-        return t
+    def step(self):
+        """temperature * N(0, 1) of the next eta > 0 step, after plms.py:224-225 `ops.dropout(noise, p=noise_dropout)`: zero
+        with probability p, the rest scaled by 1 / (1 - p) -- with seeds inside the one launch; dropout_masks[k] (1 = keep)
+        injects the mask of the k-th draw."""
+        k, p = self.steps_drawn, self.noise_dropout
+        self.steps_drawn += 1
+        if self.seeds is not None:
+            return ops.randn_seeded(self.seeds, ops.RNG_STEP, k, self.shape[1:], scale=self.temperature, dropout=p)
+        if self.step_noises is not None:
+            noise = torch.as_tensor(self.step_noises[k]).to(device=self.dev, dtype=torch.float32) * self.temperature
+        else:
+            noise = torch.randn(self.shape, device=self.dev, dtype=torch.float32, generator=self.generator) * self.temperature
+        if p > 0.:
+            if self.dropout_masks is not None:
+                keep = torch.as_tensor(self.dropout_masks[k]).to(device=self.dev, dtype=torch.float32)
+            else:
+                keep = (torch.rand(self.shape, device=self.dev, generator=self.generator) >= p).to(torch.float32)
+            noise = noise * keep / (1. - float(p))
+        return noise
 
-    def upload(self, device):
-        """The one host-to-device copy of the run; afterwards self.device_table[k] is the table of call k."""
-        t = self.host()
-        self.active = t[..., ops.STEP_ACTIVE] != 0
-        self.any_rescale = [bool(v) for v in (self.active & (t[..., ops.STEP_RESCALE] != 0)).any(1)]
-        self.any_sigma = [bool(v) for v in (self.active & (t[..., ops.STEP_SIGMA] != 0)).any(1)]
-        self.device_table = torch.as_tensor(t).to(device)
-        self.uploads += 1
-        return self.device_table
-
-    def launch(self, k, x, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0, x_model=None):
-        """Call k of the run: one ops.sampler_step_table launch on slice k."""
-        ops.sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0,
-                               self.device_table[k], self.any_rescale[k] and out_u is not None)
+    def blend(self, i, x0):
+        """The q_sample noise of the mask blend at loop index i (plms.py:153-157; WK: q_sample gets explicit noise)."""
+        if self.seeds is not None:
+            return ops.randn_seeded(self.seeds, ops.RNG_BLEND, i, self.shape[1:])
+        if self.blend_noises is not None:
+            return torch.as_tensor(self.blend_noises[i]).to(device=self.dev, dtype=torch.float32)
+        return torch.randn(x0.shape, device=self.dev, dtype=torch.float32, generator=self.generator)
 
 
 def use_cfg(uc, uc_cat, scale):

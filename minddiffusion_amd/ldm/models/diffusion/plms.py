@@ -21,7 +21,9 @@ stochastic_encode noise -- is one mdx_randn_f32 launch keyed by the sample's own
 depend on the batch it is served in; without it the sampler's generator draws for the whole batch, as before.
 Per-request parameters (not in the reference): S, unconditional_guidance_scale and guidance_rescale given as one value per
 sample -- every step is then ONE mdx_sampler_step_table_f32 launch that reads each sample's scalars from its row of a table
-built and uploaded once before the loop (guided.StepTable); scalars keep the three entries above.
+built and uploaded once before the loop (schedule.StepTable); scalars keep the three entries above.
+Either way the loop launches from ONE steps object made before it: schedule.ddim_steps says which launches a sample's run makes
+with which scalars, and a schedule.ScalarSteps or an uploaded StepTable hands launch k its scalars (arguments / a table slice).
 """
 import itertools
 
@@ -31,95 +33,9 @@ import torch
 from .... import ops
 from ...._lib import MdxError
 from ...modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps
-from .guided import (PLMS_AB, PLMS_FIRST, PLMS_SECOND, GuidedModel, StepTable, _first_tensor, ddim_step_scalars, per_request,
+from .guided import (GuidedModel, _Draws, _first_tensor, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent,
                      split_conditioning, start_latent)
-
-
-def check_guidance_rescale(value):
-    """`guidance_rescale` (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4) as a float in
-    [0, 1]; anything else, NaN included, is a ValueError."""
-    phi = float(value)
-    if not 0. <= phi <= 1.:
-        raise ValueError(f"guidance_rescale must be in [0, 1], got {value!r}")
-    return phi
-
-
-def check_seed_sources(seeds, generator=None, **injected):
-    """A second source for the draws that `seeds=` covers -- the sampler's generator, or one of the test-injection keywords -- is a
-    caller's mistake: ValueError."""
-    if seeds is None:
-        return
-    if generator is not None:
-        raise ValueError("seeds= and a sampler generator are two sources for the same draws: pass one of them")
-    given = sorted(k for k, v in injected.items() if v is not None)
-    if given:
-        raise ValueError(f"seeds= and {', '.join(given)}= are two sources for the same draws: pass one of them")
-
-
-def check_seeds(seeds, batch, device):
-    """`seeds=` of the samplers: None stays None; otherwise the int64 device tensor of `batch` per-sample seeds
-    (ops.seeds_tensor)."""
-    if seeds is None:
-        return None
-    seeds = ops.seeds_tensor(seeds, device)
-    if seeds.shape[0] != batch:
-        raise MdxError(f"seeds: {seeds.shape[0]} seeds for a batch of {batch}")
-    return seeds
-
-
-def noised_latent(x0, a, b, noise, generator, seeds=None):
-    """stochastic_encode of every sampler: a * x0 + b * noise as one ops.q_sample launch into a fresh tensor; `noise` None is
-    drawn per sample from `seeds` (stream ops.RNG_ENCODE, draw 0), or without seeds from `generator`."""
-    if not (isinstance(x0, torch.Tensor) and x0.is_cuda):
-        raise MdxError("stochastic_encode: x0 must be a CUDA(HIP) tensor [B, C, H, W]")
-    x0 = x0.to(torch.float32).contiguous()
-    check_seed_sources(seeds, generator)
-    seeds = check_seeds(seeds, x0.shape[0], x0.device)
-    if noise is None and seeds is not None:
-        noise = ops.randn_seeded(seeds, ops.RNG_ENCODE, 0, tuple(x0.shape[1:]))
-    elif noise is None:
-        noise = torch.randn(x0.shape, device=x0.device, dtype=torch.float32, generator=generator)
-    noise = torch.as_tensor(noise).to(device=x0.device, dtype=torch.float32).contiguous()
-    return ops.q_sample(x0, noise, a, b)
-
-
-class _Draws:
-    """The N(0, 1) draws inside the loop: per sample from `seeds` (one ops.randn_seeded launch each), else the injected
-    tensors (tests feed the oracle the same ones), else the sampler's generator."""
-
-    def __init__(self, seeds, generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout):
-        self.seeds, self.generator, self.dev, self.shape = seeds, generator, dev, tuple(shape)
-        self.step_noises, self.dropout_masks, self.blend_noises = step_noises, dropout_masks, blend_noises
-        self.temperature, self.noise_dropout = temperature, noise_dropout
-        self.steps_drawn = 0
-
-    def step(self):
-        """temperature * N(0, 1) of the next eta > 0 step, after plms.py:224-225 `ops.dropout(noise, p=noise_dropout)`: zero
-        with probability p, the rest scaled by 1 / (1 - p) -- with seeds inside the one launch; dropout_masks[k] (1 = keep)
-        injects the mask of the k-th draw."""
-        k, p = self.steps_drawn, self.noise_dropout
-        self.steps_drawn += 1
-        if self.seeds is not None:
-            return ops.randn_seeded(self.seeds, ops.RNG_STEP, k, self.shape[1:], scale=self.temperature, dropout=p)
-        if self.step_noises is not None:
-            noise = torch.as_tensor(self.step_noises[k]).to(device=self.dev, dtype=torch.float32) * self.temperature
-        else:
-            noise = torch.randn(self.shape, device=self.dev, dtype=torch.float32, generator=self.generator) * self.temperature
-        if p > 0.:
-            if self.dropout_masks is not None:
-                keep = torch.as_tensor(self.dropout_masks[k]).to(device=self.dev, dtype=torch.float32)
-            else:
-                keep = (torch.rand(self.shape, device=self.dev, generator=self.generator) >= p).to(torch.float32)
-            noise = noise * keep / (1. - float(p))
-        return noise
-
-    def blend(self, i, x0):
-        """The q_sample noise of the mask blend at loop index i (plms.py:153-157; WK: q_sample gets explicit noise)."""
-        if self.seeds is not None:
-            return ops.randn_seeded(self.seeds, ops.RNG_BLEND, i, self.shape[1:])
-        if self.blend_noises is not None:
-            return torch.as_tensor(self.blend_noises[i]).to(device=self.dev, dtype=torch.float32)
-        return torch.randn(x0.shape, device=self.dev, dtype=torch.float32, generator=self.generator)
+from .schedule import ScalarSteps, ddim_steps, per_request, pred_type, step_table
 
 
 class _SamplerBase:
@@ -195,7 +111,7 @@ class _SamplerBase:
             by_steps = {}
             for s_b in sorted(set(per[0])):                          # ends on max(S): the schedule the sampler keeps
                 self.make_schedule(ddim_num_steps=s_b, ddim_eta=eta, verbose=verbose)
-                by_steps[s_b] = self._time_grid(False, None, None)
+                by_steps[s_b] = self.time_grid(False, None, None)
             grids = [by_steps[s_b] for s_b in per[0]]
         else:
             self.make_schedule(ddim_num_steps=S if per is None else per[0][0], ddim_eta=eta, verbose=verbose)
@@ -275,7 +191,7 @@ class _SamplerBase:
                                   **test_injection_kwargs)
 
     # ---- which timesteps, and which tables `index` selects from (plms.py:134-142, 205-208)
-    def _time_grid(self, ddim_use_original_steps, timesteps, t_start):
+    def time_grid(self, ddim_use_original_steps, timesteps, t_start):
         """(time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas): the timesteps in loop order (descending) and the
         tables the grid index selects from.  t_start keeps the last t_start steps."""
         if ddim_use_original_steps:
@@ -312,37 +228,6 @@ class _SamplerBase:
         if not 0. <= float(noise_dropout) < 1.:
             raise ValueError("noise_dropout must be in [0, 1)")
 
-    def _step_table(self, grids, scales, rescales, guided):
-        """(StepTable, model-input timesteps [n_calls, B], loop iterations) of a per-request run: grids[b] is sample b's own
-        _time_grid(), of S[b] steps.  Sample b is active on iterations 0 .. S[b] - 1, at grid index S[b] - 1 - i; the launches
-        are the scalar loop's, in its order: for PLMS the two of the pseudo improved Euler step on iteration 0 (the second
-        evaluates the model at each sample's own min(1, S[b] - 1); its timesteps are the LAST row), then AB-2 / 3 / 4."""
-        n = [int(g[0].shape[0]) for g in grids]
-        total = max(n)
-        table = StepTable(scales, rescales, guided)
-
-        def rows(i, coef, i_model=None):
-            out = []
-            for (time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas), n_b in zip(grids, n):
-                if i >= n_b:
-                    out.append(None)
-                    continue
-                tm = int(time_range[i if i_model is None else min(i_model, n_b - 1)])
-                out.append(((self.sqrt_alphas_cumprod[tm], self.sqrt_one_minus_alphas_cumprod[tm]), coef,
-                            ddim_step_scalars(alphas, alphas_prev, sqrt_one_minus_alphas, sigmas, n_b - i - 1)))
-            return out
-
-        t_rows = [[g[0][min(i, n_b - 1)] for g, n_b in zip(grids, n)] for i in range(total)]    # ended: its last timestep
-        for i in range(total):
-            if self.multistep and i == 0:
-                table.append(rows(0, PLMS_FIRST))
-                table.append(rows(0, PLMS_SECOND, 1))
-            else:
-                table.append(rows(i, PLMS_AB[min(i, 3)] if self.multistep else PLMS_AB[0]))
-        if self.multistep:
-            t_rows.append([g[0][min(1, n_b - 1)] for g, n_b in zip(grids, n)])
-        return table, np.array(t_rows, dtype=np.float32), total
-
     # ---- plms.py:124-179 + 182-247
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
@@ -354,7 +239,7 @@ class _SamplerBase:
         mask / x0 blend of every step is one ops.q_sample launch, in place.
         unconditional_guidance_scale / guidance_rescale: a scalar, or one value per sample -- then every step is one
         ops.sampler_step_table launch on the rows of a StepTable built and uploaded before the loop (sample()).
-        grids (sample() passes it, nothing else does): one _time_grid() per sample, each sample its own step count.
+        grids (sample() passes it, nothing else does): one time_grid() per sample, each sample its own step count.
         In order: validate, normalise the conditioning and draw the start latent, select the time grid, build the guided model
         call, loop."""
         per = per_request(None, unconditional_guidance_scale, guidance_rescale, shape[0])
@@ -371,8 +256,8 @@ class _SamplerBase:
         # per-sample seeds: every draw below becomes one ops.randn_seeded launch, (stream, draw) = what it is for and which one
         seeds = check_seeds(seeds, b, dev)
         img = start_latent(x_T, seeds, shape, dev, self.generator)
-        time_range, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas = self._time_grid(ddim_use_original_steps, timesteps,
-                                                                                         t_start)
+        grid = self.time_grid(ddim_use_original_steps, timesteps, t_start)
+        time_range = grid[0]
         total_steps = int(time_range.shape[0])
         if verbose:
             print(f"Running {type(self).__name__} Sampling with {total_steps} timesteps")
@@ -385,16 +270,18 @@ class _SamplerBase:
                 if mask.dim() != 4 or mask.shape[1] not in (1, shape[1]):
                     raise MdxError(f"mask must be [B, 1, H, W] or [B, C, H, W], got {tuple(mask.shape)}")
                 mask = mask.expand((b, mask.shape[1]) + tuple(shape[2:])).contiguous()
-        table, table_calls = None, itertools.count()
-        if per is not None:
-            # every scalar of every launch, from each sample's own grid, and the model-input timesteps [n_calls, B]
-            table, t_rows, total_steps = self._step_table(grids or [(time_range, alphas, alphas_prev, sqrt_one_minus_alphas,
-                                                                     sigmas)] * b, per[1], per[2],
-                                                          not (uc is None and uc_cat is None))
-            guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
-            table.upload(dev)
+        # every scalar of every launch (schedule.ddim_steps) behind one surface: kernel arguments, or per request the rows of a
+        # table.  second_row: the row of the guided model's timesteps that PLMS' second evaluation reads
+        if per is None:
+            steps, t_rows = ScalarSteps(ddim_steps(self, grid, self.multistep), scale, guidance_rescale), time_range
+            second_row = min(1, total_steps - 1)
         else:
-            guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, time_range)
+            plans = [ddim_steps(self, g, self.multistep) for g in grids or [grid] * b]
+            steps, t_rows, total_steps = step_table(plans, per[1], per[2], not (uc is None and uc_cat is None),
+                                                    second_call_row=self.multistep)
+            steps.upload(dev)
+            second_row = total_steps                                  # the one step_table appended after the loop's
+        guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
         draws = _Draws(seeds, self.generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout)
 
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
@@ -409,20 +296,15 @@ class _SamplerBase:
         # was evaluated at; everything after that -- history, pred_x0, x_prev -- is the eps path.  Guidance rescale: the
         # CFG-combined output of every model evaluation is pulled back to the conditional output's per-sample std inside the
         # step launch.  ops.sampler_update picks the entry.
-        pred_type = ops.PRED_V if getattr(self.model, "parameterization", "eps") == "v" else ops.PRED_EPS
+        pred = pred_type(self.model)
+        calls = itertools.count()
 
-        def step(x, eps_u, eps_c, index, coef, olds, e_out, x_out, p_out, xm=None, tm=None):
-            """One get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] * olds[k-1], e_t = the
-            CFG-combined model output (optionally written to e_out).  xm / tm: the image and timestep the model output
-            was evaluated at (what a score corrector is handed, plms.py:201, and where a v output is converted to eps).
-            Per request all of these scalars are the StepTable's: the launches take its slices in the order they were built."""
-            if table is not None:
-                k = next(table_calls)
-                table.launch(k, x, eps_u, eps_c, pred_type, olds, draws.step() if table.any_sigma[k] else None, e_out,
-                             x_out, p_out, xm)
-                return
-            s_at, s_1mat, s_aprev, dir_coef, sigma_t = ddim_step_scalars(alphas, alphas_prev, sqrt_one_minus_alphas, sigmas,
-                                                                          index)
+        def step(x, eps_u, eps_c, olds, e_out, x_out, p_out, xm=None):
+            """The next launch of the run: one get_x_prev_and_pred_x0 (plms.py:210-228) on e' = coef[0] * e_t + sum coef[k] *
+            olds[k-1], e_t = the CFG-combined model output (optionally written to e_out), with the scalars `steps` holds for it.
+            xm: the image the model output was evaluated at when not x (what a score corrector is handed, plms.py:201, and where
+            a v output is converted to eps).  The two hooks are scalar-only: they read steps.plan."""
+            k = next(calls)
             if score_corrector is not None:
                 # e_t leaves the fused kernel (pass 1: CFG combine only -- the rescale belongs to the combine that produces
                 # e_t, so to this pass), goes through the caller's modify_score, and re-enters as a single NHWC fp16 model
@@ -430,7 +312,7 @@ class _SamplerBase:
                 # (a corrector implies an eps model -- _check_options -- so hook_e holds eps and PRED_EPS is the whole story)
                 ops.sampler_update(x, eps_u, eps_c, scale, ops.PRED_EPS, [], (1., 0., 0., 0.),
                                    (1., 0., 1., 0., 0., None, hook_e, hook_x, None), guidance_rescale)
-                tvec = torch.full((b,), int(tm), device=dev, dtype=torch.long)
+                tvec = torch.full((b,), int(steps.plan[k].t_input), device=dev, dtype=torch.long)
                 e_mod = score_corrector.modify_score(self.model, hook_e, x if xm is None else xm, tvec, cond,
                                                      **corrector_kwargs)
                 e_mod = torch.as_tensor(e_mod).to(device=dev, dtype=torch.float32).contiguous()
@@ -438,17 +320,15 @@ class _SamplerBase:
                     raise MdxError(f"score_corrector returned shape {tuple(e_mod.shape)}, expected {tuple(x.shape)}")
                 eps_c = ops.nchw_to_nhwc(e_mod, (x.shape[1] + 7) // 8 * 8)
                 eps_u = None
-            noise = draws.step() if float(sigma_t) != 0.0 else None
+            noise = draws.step() if steps.any_sigma[k] else None
             if quantize_denoised and p_out is None:
                 p_out = hook_p
-            update = (s_at, s_1mat, s_aprev, dir_coef, sigma_t, noise, e_out, x_out, p_out)
-            ops.sampler_update(x, eps_u, eps_c, scale, pred_type, olds, coef, update, guidance_rescale, xm,
-                               self.sqrt_alphas_cumprod[int(tm)], self.sqrt_one_minus_alphas_cumprod[int(tm)])
+            steps.launch(k, x, eps_u, eps_c, pred, olds, noise, e_out, x_out, p_out, xm)
             if quantize_denoised:
                 # pred_x0, _, *_ = first_stage_model.quantize(pred_x0) (plms.py:218-219); x_prev is linear in pred_x0
                 q = self.model.first_stage_model.quantize(p_out)[0]
                 q = torch.as_tensor(q).to(device=dev, dtype=torch.float32)
-                x_out.add_((q - p_out) * float(s_aprev))
+                x_out.add_((q - p_out) * float(steps.plan[k].update[2]))        # sqrt_a_prev
                 p_out.copy_(q)
 
         # (per request with step counts that differ, time_range is the longest grid -- sample() made that schedule last -- and
@@ -466,22 +346,16 @@ class _SamplerBase:
                     img = img_orig * mask + (1. - mask) * img
             eps_u, eps_c = guided(img, i)
             if not self.multistep:
-                step(img, eps_u, eps_c, index, PLMS_AB[0], [], None, x_next, pred_x0, tm=step_t)
+                step(img, eps_u, eps_c, [], None, x_next, pred_x0)
             else:
                 e_buf = pool.pop()
-                n_old = len(hist)
-                if n_old == 0:
+                if not hist:
                     # Pseudo Improved Euler (2nd order), plms.py:231-235: S+1 UNet calls in total
-                    step(img, eps_u, eps_c, index, PLMS_FIRST, [], e_buf, x_next, None, tm=step_t)
-                    i_next = min(i + 1, total_steps - 1)
-                    # which row of the guided model's timesteps the second evaluation reads: step i_next's -- per request the
-                    # row _step_table appended after the loop's, each sample's own min(1, S[b] - 1)
-                    second_row = i_next if table is None else total_steps
+                    step(img, eps_u, eps_c, [], e_buf, x_next, None)
                     eps_u2, eps_c2 = guided(x_next, second_row)
-                    step(img, eps_u2, eps_c2, index, PLMS_SECOND, [e_buf], None, x_next, pred_x0,
-                         xm=x_next, tm=time_range[i_next])
+                    step(img, eps_u2, eps_c2, [e_buf], None, x_next, pred_x0, xm=x_next)
                 else:             # Adams-Bashforth 2 / 3 / 4, plms.py:236-244
-                    step(img, eps_u, eps_c, index, PLMS_AB[n_old], hist[:n_old], e_buf, x_next, pred_x0, tm=step_t)
+                    step(img, eps_u, eps_c, hist, e_buf, x_next, pred_x0)
                 hist.insert(0, e_buf)
                 if len(hist) > 3:
                     pool.append(hist.pop())

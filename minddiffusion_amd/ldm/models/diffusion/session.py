@@ -3,8 +3,8 @@ into a free slot of a batch that is already running, runs its own complete sched
 finishes, and the slot is refilled.  Neither reference tree has this; sample() / __call__ are untouched.
 
 Three layers:
-  * request_rows()      the rows and model-input timesteps of ONE request, from the functions the samplers' per-request path
-                        uses (a one-sample StepTable): numpy only.
+  * request_rows()      the rows and model-input timesteps of ONE request: its plan (schedule.ddim_steps / dpm_steps, as the
+                        samplers build theirs) merged into a one-sample StepTable by schedule.step_table: numpy only.
   * SlotScheduler       which request sits in which slot on which tick: a FIFO into the lowest free slot.  It mirrors every
                         slot's position by counting and never reads the device.
   * SamplingSession     the device state (written only when a request is admitted) and the launches of one tick:
@@ -21,44 +21,38 @@ from .... import distributed as D
 from .... import ops
 from ...._lib import MdxError
 from ...modules.encoders import WINDOW
-from .guided import per_request
+from .ddim import DDIMSampler
+from .dpm_solver import DPMSolverSampler
+from .dpm_solver.dpm_solver import NoiseScheduleVP
+from .schedule import check_strength, ddim_steps, dpm_partial_start, dpm_steps, per_request, pred_type, step_table
 
 SAMPLERS = ("ddim", "dpm_solver")
 _REFUSED_KEYWORDS = ("mask", "x0", "score_corrector", "quantize_x0")
 
 
-def _dpm_start(sampler_obj, steps, t_enc):
-    """The continuous time the last t_enc of `steps` DPM-Solver steps begin at (DiffusionPipeline._partial_start)."""
-    t_0 = 1.0 / sampler_obj.alphas_cumprod.shape[0]
-    return t_0 + (1.0 - t_0) * t_enc / steps
-
-
 def request_rows(model, sampler, steps, scale, guidance_rescale=0.0, eta=0.0, t_enc=None):
     """(rows [n, ops.STEP_ROW] float32, t_input [n] float32) of one request: the rows a StepTable holds for it served
-    as a batch of one -- built by the samplers' own _step_table, so by ddim_step_scalars / PLMS_AB[0] or dpm_step_scalars /
-    dpm_model_point, and validated by StepTable.host() (finite, phi in [0, 1], sqrt_at != 0) -- and the model-input timestep of
-    every evaluation.  `model` needs what a sampler reads before it touches the device (the schedule arrays).
+    as a batch of one -- its plan from schedule.ddim_steps (on the sampler's own time_grid) or schedule.dpm_steps, merged by
+    schedule.step_table and validated by StepTable.host() (finite, phi in [0, 1], sqrt_at != 0) -- and the model-input timestep
+    of every evaluation.  `model` needs what a sampler reads before it touches the device (the schedule arrays).
     t_enc None: the full run, n = steps.  Otherwise the partial run of an img2img request, n = t_enc: the last t_enc steps of
     the `steps`-step schedule, as decode(t_start=t_enc) (DDIM) or sample(S=t_enc, t_start=) (DPM-Solver) walk them."""
     n = steps if t_enc is None else int(t_enc)
     if not 1 <= n <= steps:
         raise ValueError(f"t_enc must be an integer in [1, {steps}] (the model evaluations that remain), got {t_enc!r}")
     if sampler == "ddim":
-        from .ddim import DDIMSampler
         s = DDIMSampler(model)
         s.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)      # IndexError: no grid for this step count
-        table, t_rows, total = s._step_table([s._time_grid(False, None, t_enc)], [scale], [guidance_rescale], True)
+        plan = ddim_steps(s, s.time_grid(False, None, t_enc), False)
     elif sampler == "dpm_solver":
-        from .dpm_solver import DPMSolverSampler
-        from .dpm_solver.dpm_solver import NoiseScheduleVP
         if eta != 0.0:
             raise ValueError("eta: DPM-Solver draws no step noise, eta must be 0")
-        d = DPMSolverSampler(model)
-        ns = NoiseScheduleVP("discrete", alphas_cumprod=d.alphas_cumprod)
-        table, t_rows, total = DPMSolverSampler._step_table(ns, [n], [scale], [guidance_rescale], True,
-                                                            t_start=None if t_enc is None else _dpm_start(d, steps, n))
+        ac = DPMSolverSampler(model).alphas_cumprod
+        plan = dpm_steps(NoiseScheduleVP("discrete", alphas_cumprod=ac), n,
+                         None if t_enc is None else dpm_partial_start(ac.shape[0], steps, n))
     else:
         raise ValueError(f"sampler must be one of {SAMPLERS} in a session, got {sampler!r}")
+    table, t_rows, total = step_table([plan], [scale], [guidance_rescale], True)
     rows = table.host()[:, 0]
     assert rows.shape == (n, ops.STEP_ROW) and total == n
     return np.ascontiguousarray(rows), np.ascontiguousarray(t_rows[:, 0], dtype=np.float32)
@@ -68,13 +62,11 @@ def start_coefficients(model, sampler, steps, t_enc, eta=0.0):
     """(a, b) of x = a z0 + b noise at the level an img2img request starts from: the sampler's own q_coefficients at the start
     DiffusionPipeline._partial_start selects (grid index t_enc of the `steps`-step schedule; for DPM-Solver the continuous time)."""
     if sampler == "ddim":
-        from .ddim import DDIMSampler
         s = DDIMSampler(model)
         s.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
         return s.q_coefficients(t_enc)
-    from .dpm_solver import DPMSolverSampler
     d = DPMSolverSampler(model)
-    return d.q_coefficients(_dpm_start(d, steps, t_enc))
+    return d.q_coefficients(dpm_partial_start(d.alphas_cumprod.shape[0], steps, t_enc))
 
 
 def blend_coefficients(model, t_input):
@@ -133,8 +125,7 @@ def check_init(sampler, steps, shape, vae=None, init_latent=None, init_image=Non
             if v is not None:
                 raise ValueError(f"submit: {k} needs an init (init_latent= or init_image=)")
         return None, None, None, None
-    from ....pipeline import DiffusionPipeline
-    t_enc = DiffusionPipeline._check_strength("submit", 0.75 if strength is None else strength, steps)
+    t_enc = check_strength("submit", 0.75 if strength is None else strength, steps)
     C, h, w = shape
     if keep_mask is not None:
         if sampler == "dpm_solver":
@@ -278,7 +269,7 @@ class SamplingSession:
         self.shape = (4, H // 8, W // 8)
         self.context_len, self.cap = int(context_len), int(max_steps)
         self.temperature, self.noise_dropout = float(temperature), float(noise_dropout)
-        self.pred_type = ops.PRED_V if getattr(model, "parameterization", "eps") == "v" else ops.PRED_EPS
+        self.pred_type = pred_type(model)
         dev = self.device = torch.device(device) if device is not None else unet.device
         if hasattr(unet, "set_max_context_len") and self.context_len > int(unet.max_context_len):
             unet.set_max_context_len(80 * -(-self.context_len // 80))

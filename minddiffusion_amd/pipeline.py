@@ -20,8 +20,9 @@ from . import distributed as D
 from . import ops
 from ._lib import MdxError
 from .ldm.models.diffusion.ddim import DDIMSampler
-from .ldm.models.diffusion.guided import as_sequence, per_request, use_cfg
-from .ldm.models.diffusion.plms import PLMSSampler, check_guidance_rescale
+from .ldm.models.diffusion.guided import check_guidance_rescale, use_cfg
+from .ldm.models.diffusion.plms import PLMSSampler
+from .ldm.models.diffusion.schedule import as_sequence, check_strength, dpm_partial_start, per_request
 from .ldm.modules.encoders import WINDOW, pad_conditioning
 
 
@@ -129,7 +130,7 @@ class DiffusionPipeline:
     @staticmethod
     def check_request_lists(what, batch, steps, scale, guidance_rescale, steps_list=True):
         """`steps`, `scale` and `guidance_rescale` of a call, each one value or one per sample of the batch (the samplers'
-        per-request form, guided.per_request): the checked guidance_rescale.  batch None: the lengths are the sampler's to
+        per-request form, schedule.per_request): the checked guidance_rescale.  batch None: the lengths are the sampler's to
         check.  steps_list False: a partial run -- `strength` fixes one grid for the whole batch -- takes one step count.
         Any list needs a single rank."""
         seq = {k: as_sequence(v) is not None for k, v in (("steps", steps), ("scale", scale),
@@ -147,23 +148,12 @@ class DiffusionPipeline:
         per_request(steps, scale, guidance_rescale, batch)
         return guidance_rescale
 
-    @staticmethod
-    def _check_strength(what, strength, steps):
-        """t_enc = int(strength * steps), the steps of the `steps`-step schedule that remain to run."""
-        if not 0.0 < float(strength) <= 1.0:
-            raise ValueError(f"{what}: strength must be in (0, 1], got {strength!r}")
-        t_enc = int(float(strength) * steps)
-        if t_enc == 0:
-            raise ValueError(f"{what}: strength {strength!r} leaves no step of {steps} to run")
-        return t_enc
-
     def _partial_start(self, steps, t_enc, eta):
         """(start, a, b): where the last t_enc of `steps` steps begin -- a grid index for PLMS / DDIM, for DPM-Solver the
         continuous time t_0 + (T - t_0) * t_enc / steps of the full run's own intervals -- and the forward-process coefficients
         a * x0 + b * noise of that level."""
         if self._dpm:
-            t_0 = 1.0 / self.sampler.alphas_cumprod.shape[0]
-            start = t_0 + (1.0 - t_0) * t_enc / steps
+            start = dpm_partial_start(self.sampler.alphas_cumprod.shape[0], steps, t_enc)
         else:
             self.sampler.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=False)
             start = t_enc
@@ -419,7 +409,7 @@ class DiffusionPipeline:
         self._check_regions_allowed("img2img", regions)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
-        t_enc = self._check_strength("img2img", strength, steps)
+        t_enc = check_strength("img2img", strength, steps)
         if D.world()[1] > 1:
             raise MdxError("img2img runs on a single rank (the sharded form is not built)")
         if mask is not None and self._dpm:
@@ -512,7 +502,7 @@ class DiffusionPipeline:
                                         or hires_steps < 1):
             raise ValueError(f"hires: hires_steps must be a positive int or None, got {hires_steps!r}")
         hsteps = int(steps if hires_steps is None else hires_steps)
-        self._check_strength("hires", strength, hsteps)
+        check_strength("hires", strength, hsteps)
         if D.world()[1] > 1:
             raise MdxError("hires runs on a single rank (the sharded form is not built)")
         try:
@@ -557,7 +547,7 @@ class DiffusionPipeline:
         """img2img(init_latent=resample(z_base), seeds=) with the resample, the seeded draw and the q-sample as ONE launch
         (ops.resample_noised): the same bits, two launches fewer, and neither the enlarged latent nor the noise is stored (no
         mask blends here, so the start latent is all the run needs)."""
-        t_enc = self._check_strength("hires", strength, steps)
+        t_enc = check_strength("hires", strength, steps)
         B = int(c.shape[0])
         self.check_request_lists("hires", B, steps, scale, guidance_rescale, steps_list=False)
         seeds = self.check_seeds(seeds, B)
@@ -649,7 +639,7 @@ class DiffusionPipeline:
         self._check_regions_allowed("inpaint", regions)
         if output not in ("float", "uint8"):
             raise ValueError(f"inpaint: output must be 'float' or 'uint8', got {output!r}")
-        t_enc = self._check_strength("inpaint", strength, steps)
+        t_enc = check_strength("inpaint", strength, steps)
         mask_blur = float(mask_blur)
         if not mask_blur >= 0.0:
             raise ValueError(f"inpaint: mask_blur must be >= 0, got {mask_blur!r}")

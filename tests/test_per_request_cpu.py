@@ -1,13 +1,13 @@
 """Per-request steps / guidance scale / guidance rescale -- the parts that need no GPU: the StepTable every sampler builds
 before its loop holds, per sample, the very float32 scalars the scalar path computes for that sample's step count alone
-(through the shared functions of guided.py), rows beyond a sample's last step are inactive, the model-input timesteps follow
+(through the shared functions of schedule.py), rows beyond a sample's last step are inactive, the model-input timesteps follow
 each sample's own grid; and the validation of the builder and of the pipeline's list checks."""
 import numpy as np
 import pytest
 
 from minddiffusion_amd import ops
 from minddiffusion_amd._lib import MdxError
-from minddiffusion_amd.ldm.models.diffusion import guided as G
+from minddiffusion_amd.ldm.models.diffusion import schedule as G
 from minddiffusion_amd.ldm.models.diffusion.ddim import DDIMSampler
 from minddiffusion_amd.ldm.models.diffusion.dpm_solver import DPMSolverSampler
 from minddiffusion_amd.ldm.models.diffusion.dpm_solver.dpm_solver import NoiseScheduleVP, multistep_2m_plan
@@ -68,17 +68,18 @@ def test_plms_ddim_table_rows_are_each_samples_own_scalars(cls, eta):
     grids = {}
     for s in sorted(set(STEPS)):
         sampler.make_schedule(s, ddim_eta=eta, verbose=False)
-        grids[s] = sampler._time_grid(False, None, None)
-    table, t_rows, total = sampler._step_table([grids[s] for s in STEPS], SCALES, PHIS, True)
-    host = table.host()
+        grids[s] = sampler.time_grid(False, None, None)
     multistep = cls is PLMSSampler
+    table, t_rows, total = G.step_table([G.ddim_steps(sampler, grids[s], multistep) for s in STEPS], SCALES, PHIS, True,
+                                        second_call_row=multistep)
+    host = table.host()
     assert total == max(STEPS) and host.shape == (total + int(multistep), len(STEPS), ops.STEP_ROW)
     assert t_rows.shape == (total + int(multistep), len(STEPS))
     for b, s in enumerate(STEPS):
         # what the scalar path does for S = s alone (plms_sampling's loop): its own sampler, schedule and grid
         alone = cls(model)
         alone.make_schedule(s, ddim_eta=eta, verbose=False)
-        time_range, alphas, alphas_prev, sqrt_1m, sigmas = alone._time_grid(False, None, None)
+        time_range, alphas, alphas_prev, sqrt_1m, sigmas = alone.time_grid(False, None, None)
         assert time_range.shape[0] == s
         point = lambda t: (alone.sqrt_alphas_cumprod[int(t)], alone.sqrt_one_minus_alphas_cumprod[int(t)])
         k = 0
@@ -109,7 +110,7 @@ def test_plms_ddim_table_rows_are_each_samples_own_scalars(cls, eta):
 def test_dpm_table_rows_are_each_samples_own_plan():
     model = StubModel()
     ns = NoiseScheduleVP("discrete", alphas_cumprod=DPMSolverSampler(model).alphas_cumprod)
-    table, t_rows, total = DPMSolverSampler._step_table(ns, STEPS, SCALES, PHIS, True)
+    table, t_rows, total = G.step_table([G.dpm_steps(ns, s) for s in STEPS], SCALES, PHIS, True)
     host = table.host()
     assert total == max(STEPS) and host.shape == (total, len(STEPS), ops.STEP_ROW) and t_rows.shape == (total, len(STEPS))
     f = np.float32

@@ -142,7 +142,7 @@ def test_scalar_arguments_never_reach_the_table_entry(tiny, ops, monkeypatch, pa
 @pytest.mark.parametrize("kind", KINDS)
 def test_the_table_goes_up_once_per_run(tiny, kind, monkeypatch):
     """One StepTable per sample(), uploaded once before the loop; inside the loop the launches read slices of that tensor."""
-    from minddiffusion_amd.ldm.models.diffusion import guided as G
+    from minddiffusion_amd.ldm.models.diffusion import schedule as G
     tables, seen = [], []
     real = G.StepTable.upload
 
@@ -159,6 +159,27 @@ def test_the_table_goes_up_once_per_run(tiny, kind, monkeypatch):
     n_calls = max(STEPS) + int(kind == "plms")
     assert tuple(tables[0].device_table.shape) == (n_calls, 3, 16) and tables[0].device_table.is_cuda
     assert len(seen) == max(STEPS) and set(seen) == {(1, tables[0].device_table.data_ptr(), 1)}
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_list_run_launches_the_table_entry_once_per_evaluation_and_no_scalar_entry(tiny, ops, kind, monkeypatch):
+    """S = [2, 4]: max(S) launches of ops.sampler_step_table (one more for PLMS' double first step), none of the three scalar
+    entries, one upload."""
+    from minddiffusion_amd.ldm.models.diffusion import schedule as SCH
+    S = [2, 4]
+    count = {}
+    for entry in ("sampler_step", "sampler_step_pred", "sampler_step_rescale", "sampler_step_table"):
+        def counted(*a, _real=getattr(ops, entry), _entry=entry, **k):
+            count[_entry] = count.get(_entry, 0) + 1
+            return _real(*a, **k)
+        monkeypatch.setattr(ops, entry, counted)
+    uploads = []
+    real = SCH.StepTable.upload
+    monkeypatch.setattr(SCH.StepTable, "upload", lambda self, device: (uploads.append(self), real(self, device))[1])
+    got = run(tiny, "v", kind, S, SCALES[:2], PHIS[:2], rows=slice(0, 2))
+    assert bool(torch.isfinite(got).all())
+    assert count == {"sampler_step_table": max(S) + int(kind == "plms")}
+    assert len(uploads) == 1 and uploads[0].uploads == 1
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -9,6 +9,7 @@ import pytest
 
 from minddiffusion_amd import _lib, ops
 from minddiffusion_amd._lib import MdxError
+from minddiffusion_amd.ldm.models.diffusion import schedule as SCH
 from minddiffusion_amd.ldm.models.diffusion import session as S
 from minddiffusion_amd.ldm.models.diffusion.ddim import DDIMSampler
 from minddiffusion_amd.ldm.models.diffusion.dpm_solver import DPMSolverSampler
@@ -98,11 +99,12 @@ def test_ddim_request_rows_are_the_step_tables(eta):
     grids = []
     for s in steps:
         sampler.make_schedule(s, ddim_eta=eta, verbose=False)
-        grids.append(sampler._time_grid(False, None, None))
-    mixed, t_mixed, _ = sampler._step_table(grids, scales, phis, True)
+        grids.append(sampler.time_grid(False, None, None))
+    plans = [SCH.ddim_steps(sampler, g, False) for g in grids]
+    mixed, t_mixed, _ = SCH.step_table(plans, scales, phis, True)
     for b, s in enumerate(steps):
         rows, t_in = S.request_rows(model, "ddim", s, scales[b], phis[b], eta)
-        one, t_one, _ = sampler._step_table([grids[b]], [scales[b]], [phis[b]], True)
+        one, t_one, _ = SCH.step_table([plans[b]], [scales[b]], [phis[b]], True)
         assert rows.dtype == np.float32 and rows.shape == (s, ops.STEP_ROW) and t_in.shape == (s,)
         assert np.array_equal(rows.view(np.uint32), one.host()[:, 0].view(np.uint32))
         assert np.array_equal(rows.view(np.uint32), mixed.host()[:s, b].view(np.uint32))      # and row b of a mixed batch
@@ -116,10 +118,10 @@ def test_dpm_request_rows_are_the_step_tables():
     model = StubModel()
     ns = NoiseScheduleVP("discrete", alphas_cumprod=DPMSolverSampler(model).alphas_cumprod)
     steps, scales, phis = [1, 3, 4, 2], [1.5, 3.0, 7.5, 2.0], [0.0, 0.7, 0.3, 1.0]
-    mixed, t_mixed, _ = DPMSolverSampler._step_table(ns, steps, scales, phis, True)
+    mixed, t_mixed, _ = SCH.step_table([SCH.dpm_steps(ns, s) for s in steps], scales, phis, True)
     for b, s in enumerate(steps):
         rows, t_in = S.request_rows(model, "dpm_solver", s, scales[b], phis[b])
-        one, t_one, _ = DPMSolverSampler._step_table(ns, [s], [scales[b]], [phis[b]], True)
+        one, t_one, _ = SCH.step_table([SCH.dpm_steps(ns, s)], [scales[b]], [phis[b]], True)
         assert np.array_equal(rows.view(np.uint32), one.host()[:, 0].view(np.uint32))
         assert np.array_equal(rows.view(np.uint32), mixed.host()[:s, b].view(np.uint32))
         assert np.array_equal(t_in, t_one[:, 0]) and np.array_equal(t_in, t_mixed[:s, b])

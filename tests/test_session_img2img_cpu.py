@@ -10,11 +10,11 @@ import torch
 
 from minddiffusion_amd import _lib, ops
 from minddiffusion_amd._lib import MdxError
+from minddiffusion_amd.ldm.models.diffusion import schedule as SCH
 from minddiffusion_amd.ldm.models.diffusion import session as S
 from minddiffusion_amd.ldm.models.diffusion.ddim import DDIMSampler
 from minddiffusion_amd.ldm.models.diffusion.dpm_solver import DPMSolverSampler
 from minddiffusion_amd.ldm.models.diffusion.dpm_solver.dpm_solver import NoiseScheduleVP
-from minddiffusion_amd.pipeline import DiffusionPipeline
 from test_per_request_cpu import StubModel
 from test_session_cpu import Recorder
 
@@ -43,10 +43,10 @@ def test_the_new_keywords_are_validated():
     for bad in (0.0, -0.1, 1.01, float("nan")):
         with pytest.raises(ValueError, match=r"strength must be in \(0, 1\]"):
             chk(init_latent=z0, strength=bad)
-    with pytest.raises(ValueError) as e:                                # t_enc == 0: the message of _check_strength
+    with pytest.raises(ValueError) as e:                                # t_enc == 0: the message of check_strength
         chk(init_latent=z0, strength=0.2)
     with pytest.raises(ValueError) as want:
-        DiffusionPipeline._check_strength("submit", 0.2, 4)
+        SCH.check_strength("submit", 0.2, 4)
     assert str(e.value) == str(want.value) and "leaves no step of 4 to run" in str(e.value)
     with pytest.raises(NotImplementedError, match="mask blending is implemented by PLMSSampler / DDIMSampler"):
         chk("dpm_solver", init_latent=z0, keep_mask=keep)
@@ -118,8 +118,8 @@ def test_ddim_partial_rows_are_the_step_tables(eta):
     sampler = DDIMSampler(model)
     for steps, t_enc, scale, phi in ((4, 2, 1.5, 0.0), (4, 3, 3.0, 0.7), (2, 1, 7.5, 0.3), (4, 4, 2.0, 1.0), (50, 30, 5.0, 0.0)):
         sampler.make_schedule(steps, ddim_eta=eta, verbose=False)
-        grid = sampler._time_grid(False, None, t_enc)
-        one, t_one, total = sampler._step_table([grid], [scale], [phi], True)
+        grid = sampler.time_grid(False, None, t_enc)
+        one, t_one, total = SCH.step_table([SCH.ddim_steps(sampler, grid, False)], [scale], [phi], True)
         rows, t_in = S.request_rows(model, "ddim", steps, scale, phi, eta, t_enc=t_enc)
         assert total == t_enc and rows.shape == (t_enc, ops.STEP_ROW) and rows.dtype == np.float32
         assert np.array_equal(rows.view(np.uint32), one.host()[:, 0].view(np.uint32))
@@ -128,7 +128,8 @@ def test_ddim_partial_rows_are_the_step_tables(eta):
         assert np.array_equal(full[steps - t_enc:].view(np.uint32), rows.view(np.uint32))    # the tail of the full run
         assert np.array_equal(t_full[steps - t_enc:], t_in)
         # the full form is what it was: the rows of the whole grid
-        whole, t_whole, _ = sampler._step_table([sampler._time_grid(False, None, None)], [scale], [phi], True)
+        whole, t_whole, _ = SCH.step_table([SCH.ddim_steps(sampler, sampler.time_grid(False, None, None), False)], [scale],
+                                           [phi], True)
         assert np.array_equal(full.view(np.uint32), whole.host()[:, 0].view(np.uint32)) and np.array_equal(t_full, t_whole[:, 0])
         # the start level and the blend coefficients: the sampler's own tables
         a, b = S.start_coefficients(model, "ddim", steps, t_enc, eta)
@@ -150,14 +151,14 @@ def test_dpm_partial_rows_are_the_step_tables():
     t_0 = 1.0 / d.alphas_cumprod.shape[0]
     for steps, t_enc, scale, phi in ((4, 3, 1.5, 0.0), (6, 3, 3.0, 0.7), (4, 4, 7.5, 0.3), (4, 1, 2.0, 1.0)):
         start = t_0 + (1.0 - t_0) * t_enc / steps
-        one, t_one, total = DPMSolverSampler._step_table(ns, [t_enc], [scale], [phi], True, t_start=start)
+        one, t_one, total = SCH.step_table([SCH.dpm_steps(ns, t_enc, start)], [scale], [phi], True)
         rows, t_in = S.request_rows(model, "dpm_solver", steps, scale, phi, t_enc=t_enc)
         assert total == t_enc and rows.shape == (t_enc, ops.STEP_ROW)
         assert np.array_equal(rows.view(np.uint32), one.host()[:, 0].view(np.uint32)) and np.array_equal(t_in, t_one[:, 0])
         assert rows[0, ops.STEP_SIGMA] == 0          # c1 of a newcomer's first row: the previous prediction is not read
         assert S.start_coefficients(model, "dpm_solver", steps, t_enc) == d.q_coefficients(start)
         full, t_full = S.request_rows(model, "dpm_solver", steps, scale, phi)
-        whole, t_whole, _ = DPMSolverSampler._step_table(ns, [steps], [scale], [phi], True)
+        whole, t_whole, _ = SCH.step_table([SCH.dpm_steps(ns, steps)], [scale], [phi], True)
         assert np.array_equal(full.view(np.uint32), whole.host()[:, 0].view(np.uint32)) and np.array_equal(t_full, t_whole[:, 0])
 
 
