@@ -592,6 +592,53 @@ int mdx_sampler_step_slots_f32(const float* x, const float* x_model, const void*
 int mdx_slot_gather_f32(const float* src, const int* slot_start, const int* slot_len, int cap, int tick, float* dst, int B, long n,
                         int reps, mdx_stream_t s);
 
+/* ---- the step launch of the whole DPM-Solver (dpm_solver.py:332-1123: orders 1-3, multistep and singlestep, data and noise
+ * prediction form, dynamic thresholding): the model value of one evaluation and the linear form every update of the solver is
+ * (dpm_solver.solver_plan folds the reference's difference terms into the coefficients), ONE launch.
+ * x_base, x_model: NCHW fp32 [B][C][H][W]; out_u (NULL = no guidance) / out_c: UNet outputs, NHWC fp16 [B][HW][out_ld], first C
+ * channels used.  Per element, in this order (N = C * H * W per sample):
+ *   1. m = out_c, or out_u + cfg_scale * (out_c - out_u) with out_u
+ *   2. m = f[b] * m       guidance rescale, f[b] as mdx_sampler_step_rescale_f32 defines it (on the outputs as stored, before
+ *                         any conversion); only with guidance_rescale != 0 and out_u
+ *   3. e = m                                  pred_type == MDX_PRED_EPS
+ *        = alpha_m * m + sigma_m * x_model    pred_type == MDX_PRED_V       (dpm_solver.py:281-284)
+ *   4. val = e                                value_type == MDX_VALUE_EPS   (noise_prediction_fn)
+ *          = (x_model - sigma_m * e) / alpha_m   value_type == MDX_VALUE_X0 (data_prediction_fn :370-373), an IEEE divide
+ *   5. thresholding != 0 (:374-383, MDX_VALUE_X0 only): with k = (int)((N - 1) * 0.995) and a <= b the k-th and (k+1)-th
+ *      smallest |val| of sample b (0-based, ties counted),
+ *        s = a + (b - a) * 0.995f      each operation rounded to fp32, nothing fused
+ *        s = max(s, max_val)
+ *        val = min(max(val, -s), s) / s
+ *      a and b are found EXACTLY: a radix select (8-bit digits, most significant first) on the bit patterns of |val|, which
+ *      order as unsigned integers; b = a if at least k + 2 values are <= a, else the smallest value above a.  This is the
+ *      reference's interpolation between two order statistics, not torch.quantile's.  A NaN orders above every number.
+ *   6. model_out = val
+ *   7. x_out = A * x_base + c0 * val + c1 * h1 + c2 * h2
+ * A term of 7 whose coefficient is exactly 0 is SKIPPED, not multiplied: its tensor (x_base for A, h1, h2) is not read and
+ * may hold anything (h1 / h2 may then be NULL).  (alpha_m, sigma_m): the schedule point the model was evaluated at, where
+ * x_model is the latent it was evaluated on; x_base is the latent the update starts from (in a singlestep update the latent at
+ * the start of the step while x_model is the intermediate point).
+ * Outputs: model_out, x_out (NCHW fp32, required); model_pre_out (NCHW fp32, may be NULL): val before step 5 -- equal to
+ * model_out without thresholding; thr_out (device [B] fp32, may be NULL): s, written only with thresholding; factor_out
+ * (device [B] fp32, may be NULL): f, 1.0 where step 2 does not apply.
+ * Two launch forms.  SPREAD (no rescale, no thresholding): the elements are dealt to many workgroups.  OWNED (either of them):
+ * one 1024-thread workgroup per sample, which reduces the statistics and / or selects the order statistics and then applies the
+ * update; with thresholding the values of step 4 wait in model_out between the passes.
+ * Aliasing: x_out may be x_base and / or x_model, element for element (the same pointer).  Nothing else may overlap: no
+ * output with another output, no output with an input that is read.
+ * Refused before any launch (MDX_E_INVALID): a NULL x_base, x_model, out_c, model_out or x_out; a non-zero c1 / c2 with a NULL
+ * h1 / h2; B, C, H, W <= 0 or out_ld < C; C * H * W above 2^31 - 1; an unknown pred_type or value_type;
+ * alpha_m == 0 with MDX_VALUE_X0; thresholding with MDX_VALUE_EPS or with C * H * W < 2; thresholding with max_val not finite
+ * or <= 0; guidance_rescale outside [0, 1] or not finite, or != 0 with out_u and C * H * W < 2; an overlap other than the
+ * allowed aliases. */
+#define MDX_VALUE_X0 0
+#define MDX_VALUE_EPS 1
+int mdx_sampler_step_lin_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                             float cfg_scale, int pred_type, float guidance_rescale, int value_type, float alpha_m,
+                             float sigma_m, int thresholding, float max_val, const float* h1, const float* h2, float A,
+                             float c0, float c1, float c2, float* model_out, float* x_out, float* model_pre_out,
+                             float* thr_out, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

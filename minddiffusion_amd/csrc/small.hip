@@ -472,6 +472,285 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_slots_rescale_ke
     step_row_owned<PRED>(p, slot_row(sp, blockIdx.x), sp.factor_out, part);
 }
 
+// ------------------------------------------------------------------ the DPM-Solver step launch (mdx_sampler_step_lin_f32)
+// The model value of one evaluation (data or noise prediction, optionally thresholded) and the linear form
+// x_out = A x_base + c0 val + c1 h1 + c2 h2 that every update of the solver is; include/mdx.h has the contract.  The host
+// keeps a history pointer only for a non-zero coefficient and sets phi = 0 without an unconditional half, so the kernels test
+// pointers and A / phi only.  No __restrict__: x_out may be x_base and / or x_model, element for element -- every kernel below
+// reads element i of both before it stores element i of x_out, in the same thread.
+struct LinParams {
+    const float* x_base;
+    const float* x_model;
+    const f16* out_u;
+    const f16* out_c;
+    const float* h1;
+    const float* h2;
+    float* model_out;
+    float* x_out;
+    float* model_pre_out;
+    float* thr_out;
+    float* factor_out;
+    int out_ld, B, C, HW;
+    float cfg_scale, am, sm, A, c0, c1, c2, phi, max_val;
+    unsigned k;               // thresholding: the rank (0-based) of the lower of the two order statistics
+    int thresholding;
+};
+
+// steps 3 and 4: the CFG-combined (and rescaled) model output m to the model value
+template <int PRED, int VALUE>
+__device__ __forceinline__ float lin_value(const LinParams& p, float m, float xm) {
+    float e = m;
+    if constexpr (PRED == MDX_PRED_V) e = p.am * m + p.sm * xm;      // eps = a v + b x_m (dpm_solver.py:281-284)
+    if constexpr (VALUE == MDX_VALUE_X0) return (xm - p.sm * e) / p.am;
+    return e;
+}
+
+template <int PRED, int VALUE>
+constexpr bool lin_reads_x_model = PRED == MDX_PRED_V || VALUE == MDX_VALUE_X0;
+
+// step 7; a skipped term's operand is whatever the caller left in the register
+__device__ __forceinline__ float lin_form(const LinParams& p, float val, float xb, float h1, float h2) {
+    float xo = p.c0 * val;
+    if (p.A != 0.f) xo += p.A * xb;
+    if (p.h1) xo += p.c1 * h1;
+    if (p.h2) xo += p.c2 * h2;
+    return xo;
+}
+
+// SPREAD: sampler_step_kernel's grid and element order
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p) {
+    mdx_kernarg_touch<sizeof(LinParams)>();
+    const size_t total = (size_t)p.B * p.C * p.HW;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int pix = (int)(i % p.HW);
+        const size_t bc = i / p.HW;
+        const int c = (int)(bc % p.C);
+        const int b = (int)(bc / p.C);
+        const size_t ei = ((size_t)b * p.HW + pix) * p.out_ld + c;
+        float m = (float)p.out_c[ei];
+        if (p.out_u) {
+            const float eu = (float)p.out_u[ei];
+            m = eu + p.cfg_scale * (m - eu);
+        }
+        float xm = 0.f, xb = 0.f, h1 = 0.f, h2 = 0.f;
+        if constexpr (lin_reads_x_model<PRED, VALUE>) xm = p.x_model[i];
+        if (p.A != 0.f) xb = p.x_base[i];
+        if (p.h1) h1 = p.h1[i];
+        if (p.h2) h2 = p.h2[i];
+        const float val = lin_value<PRED, VALUE>(p, m, xm);
+        p.model_out[i] = val;
+        if (p.model_pre_out) p.model_pre_out[i] = val;
+        p.x_out[i] = lin_form(p, val, xb, h1, h2);
+    }
+}
+
+// OWNED, the passes over a sample, U elements of a thread at a time as rescale_apply does it (all loads, then the
+// arithmetic and the stores).  Every pass deals element j to thread j % RESCALE_THREADS.
+constexpr int LIN_U = 4;
+
+// Steps 1-4 (and, without thresholding, 6 and 7).  PARK: the values wait in model_out for the selection.
+template <int PRED, int VALUE, bool PARK>
+__device__ __forceinline__ void lin_owned_values(const LinParams& p, float f, int b) {
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW, HW = p.HW;
+    const f16* oc = p.out_c + (size_t)b * HW * p.out_ld;
+    const f16* ou = p.out_u ? p.out_u + (size_t)b * HW * p.out_ld : nullptr;
+    const size_t base = (size_t)b * N;
+    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
+        float m[LIN_U], xm[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U];
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            xm[u] = xb[u] = h1[u] = h2[u] = 0.f;
+            if (j < N) {
+                const size_t i = base + j;
+                const unsigned c = j / HW;
+                const size_t ei = (size_t)(j - c * HW) * p.out_ld + c;
+                m[u] = (float)oc[ei];
+                if (ou) {
+                    const float eu = (float)ou[ei];
+                    m[u] = eu + p.cfg_scale * (m[u] - eu);
+                }
+                if constexpr (lin_reads_x_model<PRED, VALUE>) xm[u] = p.x_model[i];
+                if constexpr (!PARK) {
+                    if (p.A != 0.f) xb[u] = p.x_base[i];
+                    if (p.h1) h1[u] = p.h1[i];
+                    if (p.h2) h2[u] = p.h2[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                const size_t i = base + j;
+                const float val = lin_value<PRED, VALUE>(p, m[u] * f, xm[u]);
+                p.model_out[i] = val;
+                if (p.model_pre_out) p.model_pre_out[i] = val;
+                if constexpr (!PARK) p.x_out[i] = lin_form(p, val, xb[u], h1[u], h2[u]);
+            }
+        }
+    }
+}
+
+// Step 5's s for the sample whose parked values are vals[0 .. N): the same bits in every thread.  |v| as a bit pattern orders
+// as an unsigned integer, so the k-th smallest is found digit by digit, most significant first: a pass counts, per value of
+// the digit, the candidates (the values that share the digits found so far), and wave 0 finds the digit in which the running
+// count passes the rank.  Counting is exact whatever the values are, so every pass finds exactly one digit and nothing below
+// is indexed by data except hist[digit], digit < 256.  Most candidates of the first pass share two or three digits (the high
+// exponent bits), so a wave first counts the digit of its first live lane, twice, with one atomic each, and leaves only the
+// rest to per-lane atomics.
+__device__ __forceinline__ float lin_threshold_s(const LinParams& p, const float* vals, unsigned N, unsigned* hist,
+                                                 unsigned* sel) {
+    const int lane = threadIdx.x & 63;
+    unsigned prefix = 0, rank = p.k, count_eq = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+        __syncthreads();
+        const unsigned himask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+        for (unsigned j0 = 0; j0 < N; j0 += RESCALE_THREADS) {      // the same trips in every thread: ballots below
+            const unsigned j = j0 + threadIdx.x;
+            const unsigned bits = j < N ? __float_as_uint(vals[j]) & 0x7fffffffu : 0u;
+            bool live = j < N && (bits & himask) == prefix;
+            const unsigned digit = (bits >> shift) & 255u;
+#pragma unroll
+            for (int peel = 0; peel < 2; ++peel) {
+                const unsigned long long any = __ballot(live);
+                if (any != 0) {
+                    const int first = __ffsll((long long)any) - 1;
+                    const unsigned d = (unsigned)__shfl((int)digit, first, 64);
+                    const unsigned long long same = __ballot(live && digit == d);
+                    if (lane == first) atomicAdd(&hist[d], (unsigned)__popcll(same));
+                    live = live && digit != d;
+                }
+            }
+            if (live) atomicAdd(&hist[digit], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const unsigned h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+            const unsigned sum = h0 + h1 + h2 + h3;
+            unsigned inc = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned t = (unsigned)__shfl_up((int)inc, o, 64);
+                if (lane >= o) inc += t;
+            }
+            const unsigned exc = inc - sum;
+            if (exc <= rank && rank < inc) {        // one lane: the candidates number more than the rank
+                unsigned r = rank - exc, d = 4 * lane, n = h0;
+                if (r >= h0) {
+                    r -= h0, d += 1, n = h1;
+                    if (r >= h1) {
+                        r -= h1, d += 1, n = h2;
+                        if (r >= h2) r -= h2, d += 1, n = h3;
+                    }
+                }
+                sel[0] = d;
+                sel[1] = r;
+                sel[2] = n;
+            }
+        }
+        __syncthreads();
+        prefix |= (sel[0] & 255u) << shift;
+        rank = sel[1];
+        count_eq = sel[2];
+    }
+    // a = the k-th smallest; (k - rank) values lie below it and count_eq equal it.  b, the (k+1)-th: a again if the values <= a
+    // number k + 2 or more, else the smallest value above a (there is one: k + 1 <= N - 1).
+    unsigned b_bits = prefix;
+    if (p.k - rank + count_eq < p.k + 2) {      // the same in every thread
+        unsigned lo = 0xffffffffu;
+        for (unsigned j = threadIdx.x; j < N; j += RESCALE_THREADS) {
+            const unsigned bits = __float_as_uint(vals[j]) & 0x7fffffffu;
+            if (bits > prefix && bits < lo) lo = bits;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned t = (unsigned)__shfl_xor((int)lo, o, 64);
+            lo = t < lo ? t : lo;
+        }
+        if (lane == 0) hist[threadIdx.x >> 6] = lo;     // (hist was last read before the barrier above)
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < RESCALE_THREADS / 64; ++w) lo = hist[w] < lo ? hist[w] : lo;
+        b_bits = lo;
+    }
+    const float a = __uint_as_float(prefix), bv = __uint_as_float(b_bits);
+    float s;
+    {
+#pragma clang fp contract(off)
+        const float d = bv - a;
+        const float t = d * 0.995f;
+        s = a + t;
+    }
+    return fmaxf(s, p.max_val);
+}
+
+// Steps 5-7 on the parked values.
+__device__ __forceinline__ void lin_owned_finish(const LinParams& p, float s, int b) {
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW;
+    const size_t base = (size_t)b * N;
+    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
+        float v[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U];
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            v[u] = xb[u] = h1[u] = h2[u] = 0.f;
+            if (j < N) {
+                const size_t i = base + j;
+                v[u] = p.model_out[i];
+                if (p.A != 0.f) xb[u] = p.x_base[i];
+                if (p.h1) h1[u] = p.h1[i];
+                if (p.h2) h2[u] = p.h2[i];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                const size_t i = base + j;
+                const float val = fminf(fmaxf(v[u], -s), s) / s;
+                p.model_out[i] = val;
+                p.x_out[i] = lin_form(p, val, xb[u], h1[u], h2[u]);
+            }
+        }
+    }
+}
+
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel(const LinParams p) {
+    mdx_kernarg_touch<sizeof(LinParams)>();
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sel[4];
+    const int b = blockIdx.x;
+    float f = 1.f;
+    if (p.phi != 0.f) {         // rescale_factor reads these fields only
+        StepParams sp{};
+        sp.eps_u = p.out_u;
+        sp.eps_c = p.out_c;
+        sp.eps_ld = p.out_ld;
+        sp.C = p.C;
+        sp.HW = p.HW;
+        sp.cfg_scale = p.cfg_scale;
+        f = rescale_factor(sp, p.phi, b, part);
+    }
+    if (p.factor_out && threadIdx.x == 0) p.factor_out[b] = f;
+    if constexpr (VALUE == MDX_VALUE_X0) {
+        if (p.thresholding) {
+            lin_owned_values<PRED, VALUE, true>(p, f, b);
+            __syncthreads();        // (a thread reads back only what it parked itself; the barrier is for sel / hist)
+            const unsigned N = (unsigned)p.C * (unsigned)p.HW;
+            const float s = lin_threshold_s(p, p.model_out + (size_t)b * N, N, hist, sel);
+            if (p.thr_out && threadIdx.x == 0) p.thr_out[b] = s;
+            lin_owned_finish(p, s, b);
+            return;
+        }
+    }
+    lin_owned_values<PRED, VALUE, false>(p, f, b);
+}
+
 // ------------------------------------------------------------------ per-slot row gather (mdx_slot_gather_f32)
 // dst[r * B + b][:] = src[b][pos_b][:] for the active slots: gridDim.x workgroups share slot blockIdx.y.  V == 4 moves 16 bytes
 // per lane (n % 4 == 0 and both bases 16-byte aligned: the host decides), V == 1 one float.
@@ -811,6 +1090,112 @@ extern "C" int mdx_slot_gather_f32(const float* src, const int* slot_start, cons
         hipLaunchKernelGGL(slot_gather_kernel<1>, grid, dim3(SLOT_GATHER_THREADS), 0, (hipStream_t)s, src, slot_start, slot_len,
                            cap, tick, dst, B, (size_t)n, reps);
     MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
+}
+
+// ---- mdx_sampler_step_lin_f32
+static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || na == 0 || nb == 0) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+template <int PRED, int VALUE>
+static void sampler_step_lin_run(const LinParams& p, bool owned, hipStream_t st) {
+    if (owned)
+        hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE>), dim3(p.B), dim3(RESCALE_THREADS), 0, st, p);
+    else
+        hipLaunchKernelGGL((sampler_step_lin_kernel<PRED, VALUE>), dim3(grid_for((size_t)p.B * p.C * p.HW)), dim3(256), 0, st, p);
+}
+
+extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
+                                        int out_ld, float cfg_scale, int pred_type, float guidance_rescale, int value_type,
+                                        float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
+                                        const float* h2, float A, float c0, float c1, float c2, float* model_out,
+                                        float* x_out, float* model_pre_out, float* thr_out, float* factor_out, int B, int C,
+                                        int H, int W, mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_lin_f32";
+    MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
+    MDX_REQUIRE(value_type == MDX_VALUE_X0 || value_type == MDX_VALUE_EPS, "%s: unknown value_type %d", fn, value_type);
+    MDX_REQUIRE(x_base && x_model && out_c && model_out && x_out, "%s: null pointer", fn);
+    MDX_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && out_ld >= C, "%s: bad extents", fn);
+    const size_t N = (size_t)C * H * W;
+    MDX_REQUIRE(N <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
+    MDX_REQUIRE((c1 == 0.f || h1) && (c2 == 0.f || h2), "%s: non-zero history coefficient without its model value", fn);
+    MDX_REQUIRE(value_type != MDX_VALUE_X0 || alpha_m != 0.f, "%s: alpha_m == 0 (the data prediction divides by it)", fn);
+    MDX_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "%s: guidance_rescale %g is not in [0, 1]", fn,
+                (double)guidance_rescale);
+    const bool rescale = guidance_rescale != 0.f && out_u;
+    MDX_REQUIRE(!rescale || N >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
+    if (thresholding) {
+        MDX_REQUIRE(value_type == MDX_VALUE_X0, "%s: thresholding acts on a data prediction (MDX_VALUE_X0)", fn);
+        MDX_REQUIRE(N >= 2, "%s: thresholding needs two order statistics, C * H * W >= 2", fn);
+        MDX_REQUIRE(max_val > 0.f && max_val <= 3.402823466e38f, "%s: max_val %g is not a finite positive number", fn,
+                    (double)max_val);
+    }
+    // the only aliases: x_out == x_base, x_out == x_model.  An input whose term is skipped is not read and may lie anywhere.
+    const size_t nx = (size_t)B * N * sizeof(float), nh = (((size_t)B * H * W - 1) * out_ld + C) * sizeof(f16);
+    const struct { const void* ptr; size_t bytes; const char* name; } outs[] = {
+        {model_out, nx, "model_out"}, {x_out, nx, "x_out"}, {model_pre_out, nx, "model_pre_out"},
+        {thr_out, B * sizeof(float), "thr_out"}, {factor_out, B * sizeof(float), "factor_out"}},
+      ins[] = {{A != 0.f ? x_base : nullptr, nx, "x_base"}, {x_model, nx, "x_model"}, {out_u, nh, "out_u"}, {out_c, nh, "out_c"},
+               {c1 != 0.f ? h1 : nullptr, nx, "h1"}, {c2 != 0.f ? h2 : nullptr, nx, "h2"}};
+    for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
+        for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); ++i) {
+            const bool allowed = o == 1 && i < 2 && outs[o].ptr == ins[i].ptr;
+            MDX_REQUIRE(allowed || !bytes_overlap(outs[o].ptr, outs[o].bytes, ins[i].ptr, ins[i].bytes),
+                        "%s: %s overlaps %s (only x_out may alias x_base / x_model, element for element)", fn, outs[o].name,
+                        ins[i].name);
+        }
+        for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); ++q)
+            MDX_REQUIRE(!bytes_overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes), "%s: %s overlaps %s", fn,
+                        outs[o].name, outs[q].name);
+    }
+    LinParams p{};
+    p.x_base = x_base;
+    p.x_model = x_model;
+    p.out_u = (const f16*)out_u;
+    p.out_c = (const f16*)out_c;
+    p.h1 = c1 != 0.f ? h1 : nullptr;
+    p.h2 = c2 != 0.f ? h2 : nullptr;
+    p.model_out = model_out;
+    p.x_out = x_out;
+    p.model_pre_out = model_pre_out;
+    p.thr_out = thr_out;
+    p.factor_out = factor_out;
+    p.out_ld = out_ld;
+    p.B = B;
+    p.C = C;
+    p.HW = H * W;
+    p.cfg_scale = cfg_scale;
+    p.am = alpha_m;
+    p.sm = sigma_m;
+    p.A = A;
+    p.c0 = c0;
+    p.c1 = c1;
+    p.c2 = c2;
+    p.phi = rescale ? guidance_rescale : 0.f;
+    p.max_val = max_val;
+    p.k = (unsigned)((double)(N - 1) * 0.995);
+    p.thresholding = thresholding != 0;
+    const bool owned = rescale || p.thresholding;
+    hipStream_t st = (hipStream_t)s;
+    if (pred_type == MDX_PRED_V && value_type == MDX_VALUE_X0)
+        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_X0>(p, owned, st);
+    else if (pred_type == MDX_PRED_V)
+        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_EPS>(p, owned, st);
+    else if (value_type == MDX_VALUE_X0)
+        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_X0>(p, owned, st);
+    else
+        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_EPS>(p, owned, st);
+    MDX_LAUNCH_CHECK(fn);
+    if (!owned && factor_out) {      // f == 1 everywhere, as mdx_sampler_step_rescale_f32 reports it
+        const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)factor_out, 0x3f800000 /* 1.0f */, (size_t)B, st);
+        if (e != hipSuccess) {
+            mdx_set_error("%s: factor_out fill failed: %s", fn, hipGetErrorString(e));
+            return MDX_E_HIP;
+        }
+    }
     return MDX_OK;
 }
 

@@ -4,6 +4,10 @@ data-prediction form (``multistep_dpm_solver_second_update`` :742-797, first-ord
 
 Everything here is float64 numpy on S+1 scalars; the per-element work of a step is ONE launch of the fused
 ``mdx_sampler_step_f32`` kernel (see sampler.py), so there is no tensor math in this file.
+
+``multistep_2m_plan`` is that wiring.  ``solver_plan`` (below it) is the whole of ``DPM_Solver.sample`` -- orders 1-3, multistep,
+singlestep ("DPM-Solver-fast") and singlestep_fixed, the three grids, both solver types, both prediction forms,
+denoise_to_zero -- as one record per model evaluation, each followed by one ``mdx_sampler_step_lin_f32`` launch (solver.py).
 """
 import numpy as np
 
@@ -95,4 +99,248 @@ def multistep_2m_plan(ns, steps, order=2, lower_order_final=True, t_start=None):
             c0, c1 = -phi * (1.0 + 0.5 / r0), 0.5 * phi / r0
         plan.append(dict(t=ts[k], t_next=ts[k + 1], t_input=float(ns.model_input_time(ts[k])), alpha=alpha[k],
                          sigma=sigma[k], A=A, c0=c0, c1=c1, order=step_order))
+    return plan
+
+
+# ------------------------------------------------------------------ the whole solver: DPM_Solver.sample(...) as launches
+# Every model evaluation of a run is followed by exactly ONE launch of the linear form (mdx_sampler_step_lin_f32)
+#     x_out = A * x_base + c0 * m_cur + c1 * h1 + c2 * h2
+# m_cur: the model value (data or noise prediction) the launch computes from the UNet output at (x_model, t); h1, h2: model
+# values stored by earlier launches; x_base: the latent the update starts from -- in a singlestep update the latent at the
+# start of the step, while x_model is the intermediate point x_s1 / x_s2.  The reference's difference terms (D1, D2 and the
+# (model_s1 - model_s) brackets) are folded into c0 .. c2 here: each update's formula is evaluated on the unit vectors
+# standing for the model values it combines, so what is written below is the reference's formula, not its expansion.
+# A coefficient that is exactly 0 means the launch skips the term (and never reads its buffer).
+#
+# Buffer roles are symbolic.  Latents: "x" (the latent at the start of the step; the run's start and result) and "y" (the
+# intermediate point of a singlestep update); a launch may write the buffer it reads (element for element).  Model values:
+# three slots "m0", "m1", "m2"; a launch stores m_cur in the slot it does not read.
+SKIP_TYPES = ("logSNR", "time_uniform", "time_quadratic")
+VALUE_X0, VALUE_EPS = "x0", "eps"
+
+
+def get_time_steps(ns, skip_type, t_T, t_0, N):
+    """DPM_Solver.get_time_steps :395-422, N + 1 times from t_T down to t_0, float64 (the reference's fp16 casts of the
+    logSNR endpoints and of the time_uniform grid are not reproduced, see the module docstring)."""
+    if skip_type == "logSNR":
+        lam = np.linspace(ns.marginal_lambda(t_T), ns.marginal_lambda(t_0), N + 1)
+        ts = ns.inverse_lambda(lam)
+        ts[0], ts[-1] = t_T, t_0        # the round trip through the interpolation leaves the ends a few ulp off
+        return ts
+    if skip_type == "time_uniform":
+        return np.linspace(t_T, t_0, N + 1)
+    if skip_type == "time_quadratic":
+        ts = np.linspace(t_T ** 0.5, t_0 ** 0.5, N + 1) ** 2
+        ts[0], ts[-1] = t_T, t_0
+        return ts
+    raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+
+
+def singlestep_orders(steps, order):
+    """The order of every outer step of "DPM-Solver-fast" and the number K of outer intervals a logSNR grid gets
+    (get_orders_and_timesteps_for_singlestep_solver :454-473)."""
+    if order == 3:
+        K = steps // 3 + 1
+        if steps % 3 == 0:
+            orders = [3] * (K - 2) + [2, 1]
+        elif steps % 3 == 1:
+            orders = [3] * (K - 1) + [1]
+        else:
+            orders = [3] * (K - 1) + [2]
+    elif order == 2:
+        if steps % 2 == 0:
+            K = steps // 2
+            orders = [2] * K
+        else:
+            K = steps // 2 + 1
+            orders = [2] * (K - 1) + [1]
+    elif order == 1:
+        K = steps       # (:470 sets K = 1, which leaves a logSNR grid of 2 points for `steps` updates: an index error there)
+        orders = [1] * steps
+    else:
+        raise ValueError("'order' must be '1' or '2' or '3'.")
+    return orders, K
+
+
+class _Form:
+    """What the two prediction forms differ in: with predict_x0 (DPM-Solver++) x is carried by sigma, the model value by
+    alpha and the exponent is -h; in the noise form x is carried by alpha, the model value by sigma, the exponent is +h and
+    the constant of the phi functions changes sign."""
+
+    def __init__(self, ns, predict_x0):
+        self.ns, self.x0 = ns, predict_x0
+
+    def carry(self, s, t):
+        ns = self.ns
+        if self.x0:
+            return float(ns.marginal_std(t) / ns.marginal_std(s))
+        return float(np.exp(ns.marginal_log_mean_coeff(t) - ns.marginal_log_mean_coeff(s)))
+
+    def weight(self, t):
+        return float(self.ns.marginal_alpha(t) if self.x0 else self.ns.marginal_std(t))
+
+    def phi_1(self, h):
+        return float(np.expm1(-h if self.x0 else h))
+
+    def first(self, s, t, h):
+        """dpm_solver_first_update :509-532: (A, coefficient of model_s)."""
+        return self.carry(s, t), -self.weight(t) * self.phi_1(h)
+
+
+_E = np.eye(3)
+
+
+def _singlestep_second(f, s, s1, t, h, r1, solver_type):
+    """singlestep_dpm_solver_second_update :566-612: (A, c) of the launch to s1 and of the launch to t, c over
+    (model_s, model_s1)."""
+    m_s, m_s1 = _E[0], _E[1]
+    to_s1 = (f.carry(s, s1), -f.weight(s1) * f.phi_1(r1 * h) * m_s)
+    w, phi_1 = f.weight(t), f.phi_1(h)
+    if solver_type == "dpm_solver":
+        c = -w * phi_1 * m_s - (0.5 / r1) * w * phi_1 * (m_s1 - m_s)
+    elif f.x0:
+        c = -w * phi_1 * m_s + (1. / r1) * w * (phi_1 / h + 1.) * (m_s1 - m_s)
+    else:
+        c = -w * phi_1 * m_s - (1. / r1) * w * (phi_1 / h - 1.) * (m_s1 - m_s)
+    return to_s1, (f.carry(s, t), c)
+
+
+def _singlestep_third(f, s, s1, s2, t, h, r1, r2, solver_type):
+    """singlestep_dpm_solver_third_update :658-735: the launches to s1, s2 and t, c over (model_s, model_s1, model_s2)."""
+    m_s, m_s1, m_s2 = _E
+    sign = 1. if f.x0 else -1.
+    phi_11, phi_12, phi_1 = f.phi_1(r1 * h), f.phi_1(r2 * h), f.phi_1(h)
+    phi_22 = phi_12 / (r2 * h) + sign
+    phi_2 = phi_1 / h + sign
+    phi_3 = phi_2 / h - 0.5
+    w2, w = f.weight(s2), f.weight(t)
+    to_s1 = (f.carry(s, s1), -f.weight(s1) * phi_11 * m_s)
+    to_s2 = (f.carry(s, s2), -w2 * phi_12 * m_s + sign * (r2 / r1) * w2 * phi_22 * (m_s1 - m_s))
+    if solver_type == "dpm_solver":
+        c = -w * phi_1 * m_s + sign * (1. / r2) * w * phi_2 * (m_s2 - m_s)
+    else:
+        D1_0 = (1. / r1) * (m_s1 - m_s)
+        D1_1 = (1. / r2) * (m_s2 - m_s)
+        D1 = (r2 * D1_0 - r1 * D1_1) / (r2 - r1)
+        D2 = 2. * (D1_1 - D1_0) / (r2 - r1)
+        c = -w * phi_1 * m_s + sign * w * phi_2 * D1 - w * phi_3 * D2
+    return to_s1, to_s2, (f.carry(s, t), c)
+
+
+def _multistep(f, lam_prev, s, t, h, step_order, solver_type):
+    """multistep_dpm_solver_update :874-895 from s to t: (A, c) with c over (model_prev_0, model_prev_1, model_prev_2), the
+    newest first.  lam_prev: lambda at the times of model_prev_0, model_prev_1, model_prev_2 (as many as there are)."""
+    p0, p1, p2 = _E
+    w, phi_1 = f.weight(t), f.phi_1(h)
+    sign = 1. if f.x0 else -1.
+    A = f.carry(s, t)
+    if step_order == 1:
+        return A, -w * phi_1 * p0
+    r0 = (lam_prev[0] - lam_prev[1]) / h
+    D1_0 = (1. / r0) * (p0 - p1)
+    if step_order == 2:         # multistep_dpm_solver_second_update :771-796
+        if solver_type == "dpm_solver":
+            return A, -w * phi_1 * p0 - 0.5 * w * phi_1 * D1_0
+        return A, -w * phi_1 * p0 + sign * w * (phi_1 / h + sign) * D1_0
+    r1 = (lam_prev[1] - lam_prev[2]) / h        # multistep_dpm_solver_third_update :822-843 (one form for both solver types)
+    D1_1 = (1. / r1) * (p1 - p2)
+    D1 = D1_0 + (r0 / (r0 + r1)) * (D1_0 - D1_1)
+    D2 = (1. / (r0 + r1)) * (D1_0 - D1_1)
+    return A, -w * phi_1 * p0 + sign * w * (phi_1 / h + sign) * D1 - w * ((phi_1 + sign * h) / h ** 2 - 0.5) * D2
+
+
+def _record(ns, t, value, A, c, base, model, hist, store, out, order, t_next):
+    c = [float(v) for v in c] + [0.] * (3 - len(c))
+    return dict(t=float(t), t_next=float(t_next), t_input=float(ns.model_input_time(t)), alpha_m=float(ns.marginal_alpha(t)),
+                sigma_m=float(ns.marginal_std(t)), value=value, A=float(A), c0=c[0], c1=c[1], c2=c[2], base=base, model=model,
+                h1=hist[0] if c[1] != 0. else None, h2=hist[1] if c[2] != 0. else None, store=store, out=out, order=order)
+
+
+def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep", solver_type="dpm_solver", predict_x0=True,
+                lower_order_final=True, denoise_to_zero=False, t_start=None, t_end=None):
+    """DPM_Solver(predict_x0=...).sample(steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero,
+    solver_type) :958-1123 as one record per MODEL EVALUATION, in order; each evaluation is followed by one launch of
+        x_out = A * x_base + c0 * m_cur + c1 * h1 + c2 * h2.
+    A record: t, t_input (model_input_time(t)), (alpha_m, sigma_m) at t, value ("x0" | "eps": what m_cur is), A, c0, c1, c2,
+    the buffer roles base / model / out ("x" | "y"), h1 / h2 (the slots read, None for a zero coefficient), store (the slot
+    m_cur goes to), order (of the update the evaluation belongs to) and t_next (the time of x_out).  The run starts with the
+    latent in "x" and ends with the result there.
+    multistep: `steps` evaluations, the first order - 1 updates of lower order, the last ones too under 15 steps with
+    lower_order_final; the last target gets no evaluation.  singlestep: the DPM-Solver-fast order lists, `steps` evaluations.
+    singlestep_fixed: steps // order updates of `order`.  denoise_to_zero: one more evaluation at t_0 whose data prediction
+    is the result (A = 0, c0 = 1)."""
+    if method == "adaptive":
+        raise NotImplementedError("method 'adaptive' is not planned: its step size needs a device-to-host error norm every "
+                                  "step, and a plan is made before the first launch")
+    if method not in ("multistep", "singlestep", "singlestep_fixed"):
+        raise ValueError("Got wrong method {}, need to be 'singlestep' or 'multistep' or 'singlestep_fixed' or 'adaptive'"
+                         .format(method))
+    if order not in (1, 2, 3) or isinstance(order, bool):
+        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+    if solver_type not in ("dpm_solver", "taylor"):
+        raise ValueError("'solver_type' must be either 'dpm_solver' or 'taylor', got {}".format(solver_type))
+    if skip_type not in SKIP_TYPES:
+        raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+    need = 1 if method == "singlestep" else order        # (:1065 asserts it for multistep; a fixed-order run needs one update)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < need:
+        raise ValueError("steps must be an int >= {} for method {} of order {}, got {!r}".format(need, method, order, steps))
+    steps = int(steps)
+    t_0 = 1.0 / ns.total_N if t_end is None else float(t_end)
+    t_T = ns.T if t_start is None else float(t_start)
+    if not 0. < t_0 < t_T <= ns.T:
+        raise ValueError("the run goes from t_start down to t_end: need 0 < t_end < t_start <= {}, got t_start {!r}, t_end {!r}"
+                         .format(ns.T, t_T, t_0))
+    f = _Form(ns, bool(predict_x0))
+    value = VALUE_X0 if predict_x0 else VALUE_EPS
+    lam_of = lambda t: float(ns.marginal_lambda(t))
+    plan = []
+    if method == "multistep":
+        ts = get_time_steps(ns, skip_type, t_T, t_0, steps)
+        lam = ns.marginal_lambda(ts)
+        slots = ["m0", "m1", "m2"]      # slots[0]: where this evaluation's value goes; slots[1], slots[2]: the two before it
+        for k in range(steps):
+            step = k + 1
+            if step < order:
+                step_order = step                               # init by the lower-order solvers (:1073-1078)
+            elif lower_order_final and steps < 15:
+                step_order = min(order, steps + 1 - step)       # :1082-1085
+            else:
+                step_order = order
+            A, c = _multistep(f, [lam[k - j] for j in range(step_order)], ts[k], ts[k + 1], lam[k + 1] - lam[k], step_order,
+                              solver_type)
+            plan.append(_record(ns, ts[k], value, A, c, "x", "x", slots[1:], slots[0], "x", step_order, ts[k + 1]))
+            slots = [slots[2], slots[0], slots[1]]
+    else:
+        if method == "singlestep":
+            orders, K = singlestep_orders(steps, order)
+            if skip_type == "logSNR":
+                outer = get_time_steps(ns, skip_type, t_T, t_0, K)      # "to reproduce the results in DPM-Solver paper" :474-476
+            else:
+                outer = get_time_steps(ns, skip_type, t_T, t_0, steps)[np.cumsum([0] + orders)]
+        else:
+            orders = [order] * (steps // order)
+            outer = get_time_steps(ns, skip_type, t_T, t_0, len(orders))
+        for i, o in enumerate(orders):
+            s, t = float(outer[i]), float(outer[i + 1])
+            lam_in = ns.marginal_lambda(get_time_steps(ns, skip_type, s, t, o))     # r1, r2 from the inner grid (:1110-1119)
+            lam_s, h = lam_of(s), lam_of(t) - lam_of(s)
+            if o == 1:
+                A, c0 = f.first(s, t, h)
+                plan.append(_record(ns, s, value, A, [c0], "x", "x", [None, None], "m0", "x", 1, t))
+                continue
+            r1 = float((lam_in[1] - lam_in[0]) / (lam_in[-1] - lam_in[0]))
+            s1 = float(ns.inverse_lambda(lam_s + r1 * h))
+            if o == 2:
+                (A1, c_1), (A, c) = _singlestep_second(f, s, s1, t, h, r1, solver_type)
+                plan.append(_record(ns, s, value, A1, [c_1[0]], "x", "x", [None, None], "m0", "y", 2, s1))
+                plan.append(_record(ns, s1, value, A, [c[1], c[0]], "x", "y", ["m0", None], "m1", "x", 2, t))
+                continue
+            r2 = float((lam_in[2] - lam_in[0]) / (lam_in[-1] - lam_in[0]))
+            s2 = float(ns.inverse_lambda(lam_s + r2 * h))
+            (A1, c_1), (A2, c_2), (A, c) = _singlestep_third(f, s, s1, s2, t, h, r1, r2, solver_type)
+            plan.append(_record(ns, s, value, A1, [c_1[0]], "x", "x", [None, None], "m0", "y", 3, s1))
+            plan.append(_record(ns, s1, value, A2, [c_2[1], c_2[0]], "x", "y", ["m0", None], "m1", "y", 3, s2))
+            plan.append(_record(ns, s2, value, A, [c[2], c[0], c[1]], "x", "y", ["m0", "m1"], "m2", "x", 3, t))
+    if denoise_to_zero:             # denoise_to_zero_fn :482-486: the data prediction at t_0, whatever the form of the run
+        plan.append(_record(ns, t_0, VALUE_X0, 0., [1.], "x", "x", [None, None], "m0", "x", 1, 0.))
     return plan

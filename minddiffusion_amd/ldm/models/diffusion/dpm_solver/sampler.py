@@ -20,6 +20,11 @@ input batch once, only the latent channels are refreshed per step.  `mask` / `x0
 Differences from the reference, both on the fp32 side of its fp16 arithmetic: the time grid and the schedule scalars
 are float64 on the host (the reference casts the grid to fp16, dpm_solver.py:415), and x stays fp32 (sampler.py:88
 casts the start noise to fp16).
+The rest of the reference's solver -- orders 1-3, singlestep / singlestep_fixed, the logSNR and time_quadratic grids, the
+'taylor' solver type, the noise-prediction form, dynamic thresholding, denoise_to_zero, t_end -- is reached through sample()'s
+solver options (or the constructor's defaults for them): any option off its default runs dpm_solver.solver_plan's records through
+solver.run_solver_plan, one ``mdx_sampler_step_lin_f32`` launch per model evaluation.  The wired configuration below stays on
+the launches it has always made.
 One loop: schedule.dpm_steps gives every sample's launches, and the loop launches from a schedule.ScalarSteps (scalar S, scale and
 rescale: kernel arguments) or from a StepTable merged from the samples' plans and uploaded once (any of them per sample).
 """
@@ -30,14 +35,30 @@ from ....._lib import MdxError
 from ..guided import (GuidedModel, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent, split_conditioning,
                       start_latent)
 from ..schedule import ScalarSteps, dpm_steps, per_request, pred_type, step_table
-from .dpm_solver import NoiseScheduleVP
+from .dpm_solver import NoiseScheduleVP, solver_plan
+from .solver import SOLVER_DEFAULTS, check_max_val, run_solver_plan
+
+
+def solver_options(defaults, given):
+    """The solver options of a run: `given` (None: not given) over `defaults`, and whether they are the wired configuration
+    (max_val counts only with thresholding on)."""
+    opts = {k: defaults[k] if given.get(k) is None else given[k] for k in SOLVER_DEFAULTS}
+    opts["max_val"] = check_max_val(opts["thresholding"], opts["max_val"])
+    return opts, all(opts[k] == v for k, v in SOLVER_DEFAULTS.items())
 
 
 class DPMSolverSampler:
     def __init__(self, model, **kwargs):
+        """kwargs: generator, and the defaults of sample()'s solver options (SOLVER_DEFAULTS' keys: order, skip_type, method,
+        solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end)."""
         self.model = model
         self.alphas_cumprod = np.asarray(model.alphas_cumprod, dtype=np.float64)
         self.generator = kwargs.get("generator", None)
+        self.solver = dict(SOLVER_DEFAULTS, **{k: v for k, v in kwargs.items() if k in SOLVER_DEFAULTS and v is not None})
+        opts, self.wired = solver_options(self.solver, {})
+        if not self.wired:      # a mistake shows where it is made: the plan of a short run, built and dropped
+            solver_plan(NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod), 3 * opts["order"],
+                        **{k: opts[k] for k in ("order", "skip_type", "method", "solver_type", "predict_x0", "t_end")})
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -65,8 +86,19 @@ class DPMSolverSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, guidance_rescale=0., t_start=None, seeds=None, **kwargs):
-        """t_start: a continuous time in (1 / N, T] -- the S evaluations then cover [t_start, 1 / N] instead of [T, 1 / N], from
+               unconditional_conditioning=None, guidance_rescale=0., t_start=None, seeds=None, order=None, skip_type=None,
+               method=None, solver_type=None, predict_x0=None, thresholding=None, max_val=None, denoise_to_zero=None,
+               lower_order_final=None, t_end=None, **kwargs):
+        """order, skip_type, method, solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end:
+        the options of the reference's DPM_Solver(...).sample(...) (dpm_solver.solver_plan); None: the sampler's default
+        (SOLVER_DEFAULTS unless the constructor was given another).  With every option at SOLVER_DEFAULTS -- multistep, order 2,
+        time_uniform, data prediction, no thresholding -- the run is the wired one described above, launch for launch.
+        Otherwise the plan's records are run by solver.run_solver_plan: S model evaluations (S + 1 with denoise_to_zero), each
+        followed by ONE ops.sampler_step_lin launch; callback(i) and img_callback(model value, i) fire once per evaluation,
+        where the model value is the data prediction, or with predict_x0=False the noise prediction.  seeds, x_T, t_start,
+        hybrid conditioning, v-prediction and guidance_rescale work as in the wired run.  Refused with non-default options:
+        per-request lists (below) -- the step table's rows hold the 2M update only.
+        t_start: a continuous time in (1 / N, T] -- the S evaluations then cover [t_start, 1 / N] instead of [T, 1 / N], from
         x_T = stochastic_encode(., t_start) (the reference's DPM_Solver.sample(t_start=), dpm_solver.py:958-1075).  S == 1 is a
         single first-order update.
         seeds: `batch_size` ints, one per sample -- x_T (the only draw of this sampler) of sample b then depends on seeds[b]
@@ -79,7 +111,15 @@ class DPMSolverSampler:
         guidance batch is used if any scale differs from 1; a sample whose scale is exactly 1.0 then goes through the
         combine eu + 1 * (ec - eu) and is not promised bit-equal to an unguided run.  Refused: an S list whose values DIFFER with
         t_start (a list that repeats one value is one grid and passes); any sequence with score_corrector or quantize_x0."""
+        opts, wired = solver_options(self.solver, dict(
+            order=order, skip_type=skip_type, method=method, solver_type=solver_type, predict_x0=predict_x0,
+            thresholding=thresholding, max_val=max_val, denoise_to_zero=denoise_to_zero, lower_order_final=lower_order_final,
+            t_end=t_end))
         per = per_request(S, unconditional_guidance_scale, guidance_rescale, batch_size)
+        if per is not None and not wired:
+            changed = sorted(k for k, v in SOLVER_DEFAULTS.items() if opts[k] != v)
+            raise ValueError(f"per-request S / guidance scale / guidance_rescale lists run on the step table, whose rows hold "
+                             f"the multistep order-2 update only: not with the solver options {', '.join(changed)}")
         if per is None:
             guidance_rescale = check_guidance_rescale(guidance_rescale)
         else:
@@ -103,6 +143,18 @@ class DPMSolverSampler:
         size = (batch_size,) + tuple(shape)
         img = start_latent(x_T, check_seeds(seeds, batch_size, dev), size, dev, self.generator)
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
+        if not wired:
+            # the whole solver: one loop over solver_plan's records, t_rows = every evaluation's t_input (one time-embedding
+            # table per run, as below)
+            plan = solver_plan(ns, S, order=opts["order"], skip_type=opts["skip_type"], method=opts["method"],
+                               solver_type=opts["solver_type"], predict_x0=opts["predict_x0"],
+                               lower_order_final=opts["lower_order_final"], denoise_to_zero=opts["denoise_to_zero"],
+                               t_start=t_start, t_end=opts["t_end"])
+            scale = float(unconditional_guidance_scale)
+            guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
+                                 [r["t_input"] for r in plan])
+            return run_solver_plan(plan, guided, img, scale, pred_type(self.model), guidance_rescale, opts["thresholding"],
+                                   opts["max_val"], callback, img_callback), None
         # the launches of the run (schedule.dpm_steps) behind one surface: kernel arguments, or per request the rows of a table.
         # Either way a sample's previous data prediction is read only while its own float32 c1 is non-zero.
         counts = [S] * batch_size if per is None else per[0]

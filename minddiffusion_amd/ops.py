@@ -834,6 +834,48 @@ def sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out
         _ptr(factor_out), B, C, H, W, _stream()), "mdx_sampler_step_table_f32")
 
 
+VALUE_X0, VALUE_EPS = 0, 1     # MDX_VALUE_* of include/mdx.h
+
+
+def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
+                     h1, h2, A, c0, c1, c2, model_out, x_out, thresholding=False, max_val=1., model_pre_out=None, thr_out=None,
+                     factor_out=None):
+    """The step launch of the whole DPM-Solver (see include/mdx.h): the model value `model_out` -- the data prediction
+    (VALUE_X0, dynamically thresholded at `max_val` if `thresholding`) or the noise prediction (VALUE_EPS) from the UNet
+    output halves out_u / out_c evaluated on x_model at the schedule point (alpha_m, sigma_m), after the CFG combine, the
+    guidance rescale and the v -> eps conversion -- and x_out = A x_base + c0 model_out + c1 h1 + c2 h2, in ONE launch.  A term
+    with a coefficient of exactly 0 is skipped (h1 / h2 may then be None).  x_out may be x_base and / or x_model; nothing else
+    may overlap.  Optional outputs: model_pre_out (the value before thresholding), thr_out [B] (the threshold s), factor_out
+    [B] (the rescale factor).  Every tensor's dtype, layout and extent is checked here: the library sees pointers only."""
+    _chk(x_base, f32, "x_base")
+    if x_base.dim() != 4:
+        raise _lib.MdxError(f"x_base: expected [B, C, H, W], got {tuple(x_base.shape)}")
+    B, C, H, W = x_base.shape
+    if x_model is None:
+        x_model = x_base
+    if out_c is None or model_out is None or x_out is None:
+        raise _lib.MdxError("sampler_step_lin: out_c, model_out and x_out are required")
+    for name, t in (("x_model", x_model), ("h1", h1), ("h2", h2), ("model_out", model_out), ("x_out", x_out),
+                    ("model_pre_out", model_pre_out)):
+        _chk(t, f32, name)
+        if t is not None and tuple(t.shape) != (B, C, H, W):
+            raise _lib.MdxError(f"{name}: expected {(B, C, H, W)}, got {tuple(t.shape)}")
+    ld = int(out_c.shape[-1])
+    for name, t in (("out_u", out_u), ("out_c", out_c)):
+        _chk(t, f16, name)
+        if t is not None and (int(t.shape[-1]) != ld or t.numel() != B * H * W * ld or ld < C):
+            raise _lib.MdxError(f"{name}: expected NHWC fp16 [{B}, {H * W}, {ld} >= {C}], got {tuple(t.shape)}")
+    for name, t in (("thr_out", thr_out), ("factor_out", factor_out)):
+        _chk(t, f32, name)
+        if t is not None and t.numel() < B:
+            raise _lib.MdxError(f"{name}: needs {B} elements, has {t.numel()}")
+    _lib.check(_lib.load().mdx_sampler_step_lin_f32(
+        _ptr(x_base), _ptr(x_model), _ptr(out_u), _ptr(out_c), ld, float(cfg_scale), int(pred_type), float(guidance_rescale),
+        int(value_type), float(alpha_m), float(sigma_m), int(bool(thresholding)), float(max_val), _ptr(h1), _ptr(h2), float(A),
+        float(c0), float(c1), float(c2), _ptr(model_out), _ptr(x_out), _ptr(model_pre_out), _ptr(thr_out), _ptr(factor_out),
+        B, C, H, W, _stream()), "mdx_sampler_step_lin_f32")
+
+
 # ---- sampling sessions (include/mdx.h, "slots"): the samples of a batch are slots that requests enter and leave
 def _chk_slots(B, slot_start, slot_len):
     for name, t in (("slot_start", slot_start), ("slot_len", slot_len)):

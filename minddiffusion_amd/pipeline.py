@@ -27,15 +27,24 @@ from .ldm.modules.encoders import WINDOW, pad_conditioning
 
 
 class DiffusionPipeline:
-    def __init__(self, model, sampler="ddim", device=None):
+    def __init__(self, model, sampler="ddim", device=None, solver=None):
+        """solver: with sampler='dpm_solver', the defaults of DPMSolverSampler's solver options -- dict(order=3,
+        skip_type="logSNR", method="singlestep", ...), see DPMSolverSampler.sample; every run of this pipeline, and of the
+        pipelines windowed() and hires() derive from it, then uses them."""
         self.model = model
         self.device = torch.device(device) if device is not None else model.unet.device
+        if solver is not None and sampler != "dpm_solver":
+            raise ValueError("solver= holds DPM-Solver options: pass sampler='dpm_solver' (or a DPMSolverSampler built with them)")
         if isinstance(sampler, str):
             if sampler not in ("ddim", "plms", "dpm_solver"):
                 raise ValueError("sampler must be 'ddim', 'plms' or 'dpm_solver'")
             if sampler == "dpm_solver":
                 from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
-                sampler = DPMSolverSampler(model)                      # txt2img.py --dpm_solver
+                from .ldm.models.diffusion.dpm_solver.solver import SOLVER_DEFAULTS
+                unknown = sorted(set(solver or {}) - set(SOLVER_DEFAULTS))
+                if unknown:
+                    raise ValueError(f"solver: unknown option(s) {', '.join(unknown)}; known: {', '.join(sorted(SOLVER_DEFAULTS))}")
+                sampler = DPMSolverSampler(model, **(solver or {}))    # txt2img.py --dpm_solver
             else:
                 sampler = (DDIMSampler if sampler == "ddim" else PLMSSampler)(model)
         self.sampler = sampler
@@ -92,6 +101,14 @@ class DiffusionPipeline:
         """DPM-Solver starts a partial run at a continuous time and has no decode(); PLMS / DDIM count grid steps."""
         from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
         return isinstance(self.sampler, DPMSolverSampler)
+
+    def _solver(self):
+        """The solver options this pipeline's DPMSolverSampler holds off their defaults (None: none, or another sampler): what a
+        derived pipeline's sampler is built with."""
+        if not self._dpm or self.sampler.wired:
+            return None
+        from .ldm.models.diffusion.dpm_solver.solver import SOLVER_DEFAULTS
+        return {k: v for k, v in self.sampler.solver.items() if v != SOLVER_DEFAULTS[k]}
 
     def _encoded(self, prompts, c, uc, required=True):
         """(c, uc) with one number of context windows: the prompts encoded (txt2img.py:246-251), or the tensors given."""
@@ -340,7 +357,7 @@ class DiffusionPipeline:
             raise MdxError(f"DiffusionPipeline.windowed: seam_pad is in image pixels, a multiple of 8 >= 0, got {seam_pad!r}")
         model = WindowedDiffusion(self.model, latent(window, "window"), latent(stride, "stride"), weights, max_unet_batch,
                                   wrap_x=wrap_x)
-        pipe = DiffusionPipeline(model, kind, self.device)
+        pipe = DiffusionPipeline(model, kind, self.device, solver=self._solver())
         pipe.seam_cols = int(seam_pad) // 8 if wrap_x else 0
         return pipe
 
@@ -359,6 +376,10 @@ class DiffusionPipeline:
         (submit / step / run_until_idle).  sampler: 'ddim' or 'dpm_solver' (default: the pipeline's; PLMS is refused).
         sample_posterior: whether submit(init_image=) requests sample the VAE posterior or take its mode."""
         from .ldm.models.diffusion.session import SamplingSession
+        if (sampler or self._session_sampler()) == "dpm_solver" and self._solver():
+            raise ValueError(f"DiffusionPipeline.session: a session's slots step through the slot kernels, whose rows hold the "
+                             f"multistep order-2 DPM-Solver update only: not with the solver options "
+                             f"{', '.join(sorted(self._solver()))} (pass sampler='ddim', or use a pipeline without solver=)")
         return SamplingSession(self.model, slots, H=H, W=W, sampler=sampler or self._session_sampler(),
                                context_len=context_len, max_steps=max_steps, temperature=temperature,
                                noise_dropout=noise_dropout, device=self.device, empty=empty, sample_posterior=sample_posterior)
@@ -470,7 +491,7 @@ class DiffusionPipeline:
         first = self
         if self._windowed:
             if "inner" not in kept:
-                kept["inner"] = DiffusionPipeline(self.model.inner, self._session_sampler(), self.device)
+                kept["inner"] = DiffusionPipeline(self.model.inner, self._session_sampler(), self.device, solver=self._solver())
             first = kept["inner"]
         if second is None:
             if (H, W) == base or self._windowed:

@@ -17,6 +17,10 @@ median over rounds of (replay time / launches), and rescale - pred, which is wha
 --table measures the table-driven entry beside the scalar entries it stands in for, the same way and in the same process:
   table / table_rescale  mdx_sampler_step_table_f32 with any_rescale 0 / 1 on rows that repeat the scalar calls' arguments
                          (any_rescale 1: every row rescales, as in the scalar rescale launch)
+--lin measures the DPM-Solver step launch (mdx_sampler_step_lin_f32, a third-order update) the same way beside pred / rescale:
+  lin / lin_rescale                       the spread form / the owned form with guidance_rescale = 0.7
+  lin_threshold / lin_rescale_threshold   the owned form with dynamic thresholding (the radix select), without / with rescale
+  select_us = lin_rescale_threshold - lin_rescale: what the selection and the second pass over the sample cost
 Prints one JSON line (and writes --out)."""
 import argparse
 import json
@@ -77,6 +81,32 @@ def bench_table(shape, launches, rounds, warmup):
     res = time_entries(shape, entries, launches, rounds, warmup)
     res["table_minus_pred_us"] = round(res["table_us"] - res["pred_us"], 3)
     res["table_rescale_minus_rescale_us"] = round(res["table_rescale_us"] - res["rescale_us"], 3)
+    return res
+
+
+def bench_lin(shape, launches, rounds, warmup):
+    """The DPM-Solver step launch beside the step it generalises: a third-order update (two stored model values read; the
+    model value and x_out written) on a v model with guidance."""
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    B, C, H, W = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    r32 = lambda: torch.randn(shape, device=dev, generator=g)
+    x, h1, h2 = r32(), r32(), r32()
+    out = torch.randn((2 * B, H * W, 8), device=dev, generator=g).half()
+    out_u, out_c = out[:B], out[B:]
+    m_out, x_out, p_out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    args = (x, None, out_u, out_c, 8, 7.5, ops.PRED_V, 0.8, 0.6, [], (1., 0., 0., 0.), 0.8, 0.6, 0.9, 0.5, 0.1, h1, None, x_out, p_out)
+
+    def lin(phi, thresholding):
+        ops.sampler_step_lin(x, None, out_u, out_c, 7.5, ops.PRED_V, phi, ops.VALUE_X0, 0.8, 0.6, h1, h2, 0.9, 0.3, -0.2, 0.1,
+                             m_out, x_out, thresholding=thresholding, max_val=1.0)
+    entries = {"pred": lambda: ops.sampler_step_pred(*args), "lin": lambda: lin(0., False),
+               "rescale": lambda: ops.sampler_step_rescale(*args, 0.7), "lin_rescale": lambda: lin(0.7, False),
+               "lin_threshold": lambda: lin(0., True), "lin_rescale_threshold": lambda: lin(0.7, True)}
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    res["select_us"] = round(res["lin_rescale_threshold_us"] - res["lin_rescale_us"], 3)
     return res
 
 
@@ -145,12 +175,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--noise", action="store_true", help="measure the stochastic step's noise preparation instead")
     ap.add_argument("--table", action="store_true", help="measure the table-driven entry beside the scalar entries instead")
+    ap.add_argument("--lin", action="store_true", help="measure the DPM-Solver step launch (mdx_sampler_step_lin_f32) instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("step_bench: needs a GPU")
-    bench = bench_noise if a.noise else bench_table if a.table else bench_shape
+    bench = bench_noise if a.noise else bench_table if a.table else bench_lin if a.lin else bench_shape
     res = {"launches": a.launches, "rounds": a.rounds, "shapes": [bench(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
     if a.noise:
         res["what"] = "noise preparation of a stochastic step, us per step"
