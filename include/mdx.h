@@ -639,6 +639,29 @@ int mdx_sampler_step_lin_f32(const float* x_base, const float* x_model, const vo
                              float c0, float c1, float c2, float* model_out, float* x_out, float* model_pre_out,
                              float* thr_out, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
 
+/* ---- the step launch of a STOCHASTIC update (dpm_solver.solver_plan with sde_eta > 0, "DPM++ 2M SDE"): every argument of
+ * mdx_sampler_step_lin_f32 with its meaning, steps 1-7 as above, and
+ *   8. x_out = (the value of step 7) + cn * z       one fma
+ * in the same ONE launch.  z ~ N(0, 1) per element comes from exactly one of two sources:
+ *   noise: NCHW fp32 [B][C][H][W], z = noise[i]; or
+ *   seeds: device [B] 64-bit seeds, z = the value mdx_randn_f32(seeds, stream, draw, scale 1, dropout 0) stores for element i
+ *          of sample b (counted from the sample's start) -- drawn inside the launch, bit for bit (Philox4x32-10 at counter
+ *          (i >> 2, draw, stream, 0) under key seeds[b], Box-Muller as described there), never stored.
+ * Sample b's noise depends on seeds[b] alone: a row of a batch is bit-equal to the B == 1 launch with that seed.
+ * cn == 0 IS mdx_sampler_step_lin_f32, bit for bit: neither source is read (both may be NULL, or point anywhere).
+ * Both launch forms carry step 8 (with thresholding it belongs to the finishing pass).  In them a thread works on the four
+ * consecutive elements of one Philox call, with either source, so the two sources give the same bits for the same z.
+ * Aliasing: as above -- x_out may be x_base and / or x_model; noise and seeds may overlap no output.
+ * Refused before any launch (MDX_E_INVALID): cn not finite; cn != 0 with both sources or with neither; stream >= 2^31 (the top
+ * bit belongs to the dropout decisions of a stream); everything mdx_sampler_step_lin_f32 refuses. */
+int mdx_sampler_step_lin_noise_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                                   float cfg_scale, int pred_type, float guidance_rescale, int value_type, float alpha_m,
+                                   float sigma_m, int thresholding, float max_val, const float* h1, const float* h2, float A,
+                                   float c0, float c1, float c2, float* model_out, float* x_out, float* model_pre_out,
+                                   float* thr_out, float* factor_out, float cn, const float* noise,
+                                   const unsigned long long* seeds, unsigned stream, unsigned draw, int B, int C, int H, int W,
+                                   mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

@@ -1,6 +1,7 @@
 // Small / elementwise kernels of the path: layout boundary, timestep embedding, small-M Dense,
 // fused sampler update, hardware-layout probes, and the library's error plumbing.
 #include "mdx_common.h"
+#include "rng_device.h"
 
 #include <string.h>
 
@@ -496,6 +497,40 @@ struct LinParams {
     int thresholding;
 };
 
+// Step 8 (mdx_sampler_step_lin_noise_f32): x_out = (step 7) + cn * z, one fma.  NOISE says where z comes from: a tensor, or
+// the generator -- quad_values<MODE_NORMAL> of rng_device.h at (seeds[b], stream, draw), scale 1, the bits mdx_randn_f32 stores.
+// One Philox call gives the four elements 4 q .. 4 q + 3 of a sample (counted from the sample's start: with C * HW % 4 != 0 the
+// last quad is partial, with HW % 4 != 0 a quad straddles two channels -- every element finds its own channel and pixel), so
+// quads are dealt, never drawn once per element: to threads in the SPREAD form, to lanes in the OWNED form (below).  Both
+// noise sources run the same statements on an element but the one that fetches z, so they agree to the bit.  The
+// LIN_NOISE_NONE instantiations are the kernels mdx_sampler_step_lin_f32 has always launched: they take LinParams alone.
+enum { LIN_NOISE_NONE = 0, LIN_NOISE_TENSOR = 1, LIN_NOISE_SEEDED = 2 };
+
+struct LinNoise {
+    float cn;
+    const float* noise;
+    const unsigned long long* seeds;
+    unsigned stream, draw;
+};
+
+struct LinNoiseParams {
+    LinParams l;
+    LinNoise n;
+};
+
+constexpr int LIN_U = 4;
+
+// the quad that starts at element j0 (a multiple of 4) of sample b
+__device__ __forceinline__ void lin_quad_z(const LinNoise& n, int b, unsigned j0, float (&z)[LIN_U]) {
+    RngParams r{};
+    r.stream = n.stream;
+    r.scale = 1.0f;
+    unsigned bits[4];
+    quad_values<MODE_NORMAL>(r, n.seeds[b], n.draw, j0 >> 2, bits);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) z[e] = __uint_as_float(bits[e]);
+}
+
 // steps 3 and 4: the CFG-combined (and rescaled) model output m to the model value
 template <int PRED, int VALUE>
 __device__ __forceinline__ float lin_value(const LinParams& p, float m, float xm) {
@@ -545,23 +580,104 @@ __global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p
     }
 }
 
-// OWNED, the passes over a sample, U elements of a thread at a time as rescale_apply does it (all loads, then the
-// arithmetic and the stores).  Every pass deals element j to thread j % RESCALE_THREADS.
-constexpr int LIN_U = 4;
+// SPREAD with step 8: a quad per thread and trip, all loads first (the draw's arithmetic then runs under their latency), then
+// the arithmetic and the stores -- a thread stores only elements it has read, so x_out may be x_base / x_model as above.
+// 64-thread workgroups: a quad is four elements, so the latent of a UNet batch still spreads over a hundred CUs and more.
+constexpr int LIN_NOISE_THREADS = 64;
 
-// Steps 1-4 (and, without thresholding, 6 and 7).  PARK: the values wait in model_out for the selection.
-template <int PRED, int VALUE, bool PARK>
-__device__ __forceinline__ void lin_owned_values(const LinParams& p, float f, int b) {
+template <int PRED, int VALUE, int NOISE>
+__global__ __launch_bounds__(LIN_NOISE_THREADS) void sampler_step_lin_noise_kernel(const LinNoiseParams q) {
+    mdx_kernarg_touch<sizeof(LinNoiseParams)>();
+    const LinParams& p = q.l;
+    const unsigned N = (unsigned)p.C * (unsigned)p.HW, HW = p.HW;       // the host refuses what does not fit 31 bits
+    const unsigned quads = (N + 3u) / 4u;
+    const size_t items = (size_t)p.B * quads;
+    for (size_t it = (size_t)blockIdx.x * LIN_NOISE_THREADS + threadIdx.x; it < items;
+         it += (size_t)gridDim.x * LIN_NOISE_THREADS) {
+        const int b = (int)(it / quads);
+        const unsigned j0 = (unsigned)(it - (size_t)b * quads) * 4u;
+        const size_t base = (size_t)b * N;
+        float m[LIN_U], xm[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U], z[LIN_U];
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u;
+            m[u] = xm[u] = xb[u] = h1[u] = h2[u] = z[u] = 0.f;
+            if (j < N) {
+                const size_t i = base + j;
+                const unsigned c = j / HW;
+                const size_t ei = ((size_t)b * HW + (j - c * HW)) * p.out_ld + c;
+                m[u] = (float)p.out_c[ei];
+                if (p.out_u) {
+                    const float eu = (float)p.out_u[ei];
+                    m[u] = eu + p.cfg_scale * (m[u] - eu);
+                }
+                if constexpr (lin_reads_x_model<PRED, VALUE>) xm[u] = p.x_model[i];
+                if (p.A != 0.f) xb[u] = p.x_base[i];
+                if (p.h1) h1[u] = p.h1[i];
+                if (p.h2) h2[u] = p.h2[i];
+                if constexpr (NOISE == LIN_NOISE_TENSOR) z[u] = q.n.noise[i];
+            }
+        }
+        if constexpr (NOISE == LIN_NOISE_SEEDED) lin_quad_z(q.n, b, j0, z);
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u;
+            if (j < N) {
+                const size_t i = base + j;
+                const float val = lin_value<PRED, VALUE>(p, m[u], xm[u]);
+                p.model_out[i] = val;
+                if (p.model_pre_out) p.model_pre_out[i] = val;
+                p.x_out[i] = __builtin_fmaf(q.n.cn, z[u], lin_form(p, val, xb[u], h1[u], h2[u]));
+            }
+        }
+    }
+}
+
+// OWNED, the passes over a sample, U elements of a thread at a time as rescale_apply does it (all loads, then the
+// arithmetic and the stores).  Every pass deals element j to thread j % RESCALE_THREADS, with and without noise: a lone
+// workgroup lives on coalesced loads (with quads dealt to its threads, four consecutive elements each, the launch measured
+// twice the time).  So the seeded instantiations deal the quads of a trip to LANES and the values travel by shuffle: in one
+// trip a wave works on LIN_U spans of 64 consecutive elements (64 apart from the sample's start: quad-aligned), 16 quads each,
+// 64 in all; lane L draws quad L & 15 of span L >> 4, and the element of span u in lane l takes value l & 3 of lane
+// 16 u + l / 4.  Their loops run the same trips in all lanes of a wave (the shuffles need every lane).
+template <int NOISE>
+__device__ __forceinline__ bool lin_owned_trip(unsigned j0, unsigned N) {
+    if constexpr (NOISE == LIN_NOISE_SEEDED)
+        return j0 - (threadIdx.x & 63u) < N;
+    else
+        return j0 < N;
+}
+
+// z of the thread's LIN_U elements j0 + u * RESCALE_THREADS of sample b
+__device__ __forceinline__ void lin_owned_z(const LinNoise& n, int b, unsigned j0, unsigned N, float (&z)[LIN_U]) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned start = (j0 - lane) + (lane >> 4) * RESCALE_THREADS + (lane & 15u) * 4u;
+    float zq[LIN_U] = {0.f, 0.f, 0.f, 0.f};
+    if (start < N) lin_quad_z(n, b, start, zq);
+#pragma unroll
+    for (int u = 0; u < LIN_U; ++u) {
+        const int src = u * 16 + (int)(lane >> 2);
+        const float a0 = __shfl(zq[0], src, 64), a1 = __shfl(zq[1], src, 64), a2 = __shfl(zq[2], src, 64),
+                    a3 = __shfl(zq[3], src, 64);
+        const unsigned e = lane & 3u;
+        z[u] = e == 0 ? a0 : e == 1 ? a1 : e == 2 ? a2 : a3;
+    }
+}
+
+// Steps 1-4 (and, without thresholding, 6, 7 and 8).  PARK: the values wait in model_out for the selection.
+template <int PRED, int VALUE, bool PARK, int NOISE>
+__device__ __forceinline__ void lin_owned_values(const LinParams& p, const LinNoise& n, float f, int b) {
     const unsigned N = (unsigned)p.C * (unsigned)p.HW, HW = p.HW;
     const f16* oc = p.out_c + (size_t)b * HW * p.out_ld;
     const f16* ou = p.out_u ? p.out_u + (size_t)b * HW * p.out_ld : nullptr;
     const size_t base = (size_t)b * N;
-    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
-        float m[LIN_U], xm[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U];
+    for (unsigned j0 = threadIdx.x; lin_owned_trip<NOISE>(j0, N); j0 += RESCALE_THREADS * LIN_U) {
+        float m[LIN_U], xm[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U], z[LIN_U];
 #pragma unroll
         for (int u = 0; u < LIN_U; ++u) {
             const unsigned j = j0 + u * RESCALE_THREADS;
             xm[u] = xb[u] = h1[u] = h2[u] = 0.f;
+            if constexpr (NOISE != LIN_NOISE_NONE) z[u] = 0.f;
             if (j < N) {
                 const size_t i = base + j;
                 const unsigned c = j / HW;
@@ -576,9 +692,11 @@ __device__ __forceinline__ void lin_owned_values(const LinParams& p, float f, in
                     if (p.A != 0.f) xb[u] = p.x_base[i];
                     if (p.h1) h1[u] = p.h1[i];
                     if (p.h2) h2[u] = p.h2[i];
+                    if constexpr (NOISE == LIN_NOISE_TENSOR) z[u] = n.noise[i];
                 }
             }
         }
+        if constexpr (!PARK && NOISE == LIN_NOISE_SEEDED) lin_owned_z(n, b, j0, N, z);
 #pragma unroll
         for (int u = 0; u < LIN_U; ++u) {
             const unsigned j = j0 + u * RESCALE_THREADS;
@@ -587,7 +705,11 @@ __device__ __forceinline__ void lin_owned_values(const LinParams& p, float f, in
                 const float val = lin_value<PRED, VALUE>(p, m[u] * f, xm[u]);
                 p.model_out[i] = val;
                 if (p.model_pre_out) p.model_pre_out[i] = val;
-                if constexpr (!PARK) p.x_out[i] = lin_form(p, val, xb[u], h1[u], h2[u]);
+                if constexpr (!PARK) {
+                    float xo = lin_form(p, val, xb[u], h1[u], h2[u]);
+                    if constexpr (NOISE != LIN_NOISE_NONE) xo = __builtin_fmaf(n.cn, z[u], xo);
+                    p.x_out[i] = xo;
+                }
             }
         }
     }
@@ -687,24 +809,28 @@ __device__ __forceinline__ float lin_threshold_s(const LinParams& p, const float
     return fmaxf(s, p.max_val);
 }
 
-// Steps 5-7 on the parked values.
-__device__ __forceinline__ void lin_owned_finish(const LinParams& p, float s, int b) {
+// Steps 5-8 on the parked values.
+template <int NOISE>
+__device__ __forceinline__ void lin_owned_finish(const LinParams& p, const LinNoise& n, float s, int b) {
     const unsigned N = (unsigned)p.C * (unsigned)p.HW;
     const size_t base = (size_t)b * N;
-    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
-        float v[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U];
+    for (unsigned j0 = threadIdx.x; lin_owned_trip<NOISE>(j0, N); j0 += RESCALE_THREADS * LIN_U) {
+        float v[LIN_U], xb[LIN_U], h1[LIN_U], h2[LIN_U], z[LIN_U];
 #pragma unroll
         for (int u = 0; u < LIN_U; ++u) {
             const unsigned j = j0 + u * RESCALE_THREADS;
             v[u] = xb[u] = h1[u] = h2[u] = 0.f;
+            if constexpr (NOISE != LIN_NOISE_NONE) z[u] = 0.f;
             if (j < N) {
                 const size_t i = base + j;
                 v[u] = p.model_out[i];
                 if (p.A != 0.f) xb[u] = p.x_base[i];
                 if (p.h1) h1[u] = p.h1[i];
                 if (p.h2) h2[u] = p.h2[i];
+                if constexpr (NOISE == LIN_NOISE_TENSOR) z[u] = n.noise[i];
             }
         }
+        if constexpr (NOISE == LIN_NOISE_SEEDED) lin_owned_z(n, b, j0, N, z);
 #pragma unroll
         for (int u = 0; u < LIN_U; ++u) {
             const unsigned j = j0 + u * RESCALE_THREADS;
@@ -712,18 +838,29 @@ __device__ __forceinline__ void lin_owned_finish(const LinParams& p, float s, in
                 const size_t i = base + j;
                 const float val = fminf(fmaxf(v[u], -s), s) / s;
                 p.model_out[i] = val;
-                p.x_out[i] = lin_form(p, val, xb[u], h1[u], h2[u]);
+                float xo = lin_form(p, val, xb[u], h1[u], h2[u]);
+                if constexpr (NOISE != LIN_NOISE_NONE) xo = __builtin_fmaf(n.cn, z[u], xo);
+                p.x_out[i] = xo;
             }
         }
     }
 }
 
-template <int PRED, int VALUE>
-__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel(const LinParams p) {
-    mdx_kernarg_touch<sizeof(LinParams)>();
+// OWNED: one kernel for both entries.  P is LinParams (mdx_sampler_step_lin_f32: NOISE is LIN_NOISE_NONE, the kernel that
+// entry has always launched) or LinNoiseParams.
+__device__ __forceinline__ const LinParams& lin_of(const LinParams& p) { return p; }
+__device__ __forceinline__ const LinParams& lin_of(const LinNoiseParams& q) { return q.l; }
+__device__ __forceinline__ LinNoise lin_noise_of(const LinParams&) { return LinNoise{}; }
+__device__ __forceinline__ LinNoise lin_noise_of(const LinNoiseParams& q) { return q.n; }
+
+template <int PRED, int VALUE, int NOISE, class P>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel(const P q) {
+    mdx_kernarg_touch<sizeof(P)>();
     __shared__ float part[RESCALE_THREADS / 64][4];
     __shared__ unsigned hist[256];
     __shared__ unsigned sel[4];
+    const LinParams& p = lin_of(q);
+    const LinNoise n = lin_noise_of(q);
     const int b = blockIdx.x;
     float f = 1.f;
     if (p.phi != 0.f) {         // rescale_factor reads these fields only
@@ -739,16 +876,16 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel
     if (p.factor_out && threadIdx.x == 0) p.factor_out[b] = f;
     if constexpr (VALUE == MDX_VALUE_X0) {
         if (p.thresholding) {
-            lin_owned_values<PRED, VALUE, true>(p, f, b);
+            lin_owned_values<PRED, VALUE, true, NOISE>(p, n, f, b);
             __syncthreads();        // (a thread reads back only what it parked itself; the barrier is for sel / hist)
             const unsigned N = (unsigned)p.C * (unsigned)p.HW;
             const float s = lin_threshold_s(p, p.model_out + (size_t)b * N, N, hist, sel);
             if (p.thr_out && threadIdx.x == 0) p.thr_out[b] = s;
-            lin_owned_finish(p, s, b);
+            lin_owned_finish<NOISE>(p, n, s, b);
             return;
         }
     }
-    lin_owned_values<PRED, VALUE, false>(p, f, b);
+    lin_owned_values<PRED, VALUE, false, NOISE>(p, n, f, b);
 }
 
 // ------------------------------------------------------------------ per-slot row gather (mdx_slot_gather_f32)
@@ -1100,21 +1237,39 @@ static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return x < y + nb && y < x + na;
 }
 
+template <int PRED, int VALUE, int NOISE>
+static void sampler_step_lin_noise_run(const LinNoiseParams& q, bool owned, hipStream_t st) {
+    if (owned) {
+        hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, NOISE, LinNoiseParams>), dim3(q.l.B), dim3(RESCALE_THREADS), 0, st, q);
+    } else {
+        const size_t items = (size_t)q.l.B * (((size_t)q.l.C * q.l.HW + 3) / 4);
+        const size_t blocks = (items + LIN_NOISE_THREADS - 1) / LIN_NOISE_THREADS;
+        hipLaunchKernelGGL((sampler_step_lin_noise_kernel<PRED, VALUE, NOISE>), dim3((unsigned)(blocks > 8192 ? 8192 : blocks)),
+                           dim3(LIN_NOISE_THREADS), 0, st, q);
+    }
+}
+
 template <int PRED, int VALUE>
-static void sampler_step_lin_run(const LinParams& p, bool owned, hipStream_t st) {
-    if (owned)
-        hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE>), dim3(p.B), dim3(RESCALE_THREADS), 0, st, p);
+static void sampler_step_lin_run(const LinParams& p, const LinNoise* nz, bool owned, hipStream_t st) {
+    if (nz) {
+        const LinNoiseParams q{p, *nz};
+        if (nz->seeds)
+            sampler_step_lin_noise_run<PRED, VALUE, LIN_NOISE_SEEDED>(q, owned, st);
+        else
+            sampler_step_lin_noise_run<PRED, VALUE, LIN_NOISE_TENSOR>(q, owned, st);
+    } else if (owned)
+        hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, LIN_NOISE_NONE, LinParams>), dim3(p.B), dim3(RESCALE_THREADS), 0, st, p);
     else
         hipLaunchKernelGGL((sampler_step_lin_kernel<PRED, VALUE>), dim3(grid_for((size_t)p.B * p.C * p.HW)), dim3(256), 0, st, p);
 }
 
-extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
-                                        int out_ld, float cfg_scale, int pred_type, float guidance_rescale, int value_type,
-                                        float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
-                                        const float* h2, float A, float c0, float c1, float c2, float* model_out,
-                                        float* x_out, float* model_pre_out, float* thr_out, float* factor_out, int B, int C,
-                                        int H, int W, mdx_stream_t s) {
-    const char* fn = "mdx_sampler_step_lin_f32";
+// Both entries: nz == nullptr is mdx_sampler_step_lin_f32's launch, kernel for kernel (the noise entry passes it for cn == 0).
+static int sampler_step_lin_entry(const char* fn, const float* x_base, const float* x_model, const void* out_u,
+                                  const void* out_c, int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
+                                  int value_type, float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
+                                  const float* h2, float A, float c0, float c1, float c2, float* model_out, float* x_out,
+                                  float* model_pre_out, float* thr_out, float* factor_out, const LinNoise* nz, int B, int C,
+                                  int H, int W, mdx_stream_t s) {
     MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
     MDX_REQUIRE(value_type == MDX_VALUE_X0 || value_type == MDX_VALUE_EPS, "%s: unknown value_type %d", fn, value_type);
     MDX_REQUIRE(x_base && x_model && out_c && model_out && x_out, "%s: null pointer", fn);
@@ -1139,7 +1294,8 @@ extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_mode
         {model_out, nx, "model_out"}, {x_out, nx, "x_out"}, {model_pre_out, nx, "model_pre_out"},
         {thr_out, B * sizeof(float), "thr_out"}, {factor_out, B * sizeof(float), "factor_out"}},
       ins[] = {{A != 0.f ? x_base : nullptr, nx, "x_base"}, {x_model, nx, "x_model"}, {out_u, nh, "out_u"}, {out_c, nh, "out_c"},
-               {c1 != 0.f ? h1 : nullptr, nx, "h1"}, {c2 != 0.f ? h2 : nullptr, nx, "h2"}};
+               {c1 != 0.f ? h1 : nullptr, nx, "h1"}, {c2 != 0.f ? h2 : nullptr, nx, "h2"},
+               {nz ? nz->noise : nullptr, nx, "noise"}, {nz ? nz->seeds : nullptr, B * sizeof(unsigned long long), "seeds"}};
     for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
         for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); ++i) {
             const bool allowed = o == 1 && i < 2 && outs[o].ptr == ins[i].ptr;
@@ -1181,13 +1337,13 @@ extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_mode
     const bool owned = rescale || p.thresholding;
     hipStream_t st = (hipStream_t)s;
     if (pred_type == MDX_PRED_V && value_type == MDX_VALUE_X0)
-        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_X0>(p, owned, st);
+        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_X0>(p, nz, owned, st);
     else if (pred_type == MDX_PRED_V)
-        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_EPS>(p, owned, st);
+        sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_EPS>(p, nz, owned, st);
     else if (value_type == MDX_VALUE_X0)
-        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_X0>(p, owned, st);
+        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_X0>(p, nz, owned, st);
     else
-        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_EPS>(p, owned, st);
+        sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_EPS>(p, nz, owned, st);
     MDX_LAUNCH_CHECK(fn);
     if (!owned && factor_out) {      // f == 1 everywhere, as mdx_sampler_step_rescale_f32 reports it
         const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)factor_out, 0x3f800000 /* 1.0f */, (size_t)B, st);
@@ -1197,6 +1353,35 @@ extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_mode
         }
     }
     return MDX_OK;
+}
+
+extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
+                                        int out_ld, float cfg_scale, int pred_type, float guidance_rescale, int value_type,
+                                        float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
+                                        const float* h2, float A, float c0, float c1, float c2, float* model_out,
+                                        float* x_out, float* model_pre_out, float* thr_out, float* factor_out, int B, int C,
+                                        int H, int W, mdx_stream_t s) {
+    return sampler_step_lin_entry("mdx_sampler_step_lin_f32", x_base, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
+                                  guidance_rescale, value_type, alpha_m, sigma_m, thresholding, max_val, h1, h2, A, c0, c1, c2,
+                                  model_out, x_out, model_pre_out, thr_out, factor_out, nullptr, B, C, H, W, s);
+}
+
+extern "C" int mdx_sampler_step_lin_noise_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
+                                              int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
+                                              int value_type, float alpha_m, float sigma_m, int thresholding, float max_val,
+                                              const float* h1, const float* h2, float A, float c0, float c1, float c2,
+                                              float* model_out, float* x_out, float* model_pre_out, float* thr_out,
+                                              float* factor_out, float cn, const float* noise, const unsigned long long* seeds,
+                                              unsigned stream, unsigned draw, int B, int C, int H, int W, mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_lin_noise_f32";
+    MDX_REQUIRE(cn >= -3.402823466e38f && cn <= 3.402823466e38f, "%s: cn %g is not finite", fn, (double)cn);
+    MDX_REQUIRE(stream < DROPOUT_STREAM_BIT, "%s: stream %u is not below 2^31", fn, stream);
+    MDX_REQUIRE(cn == 0.f || ((noise != nullptr) != (seeds != nullptr)),
+                "%s: cn != 0 takes exactly one noise source, noise or seeds (got %s)", fn, noise ? "both" : "neither");
+    const LinNoise nz{cn, noise, noise ? nullptr : seeds, stream, draw};
+    return sampler_step_lin_entry(fn, x_base, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, guidance_rescale, value_type,
+                                  alpha_m, sigma_m, thresholding, max_val, h1, h2, A, c0, c1, c2, model_out, x_out,
+                                  model_pre_out, thr_out, factor_out, cn != 0.f ? &nz : nullptr, B, C, H, W, s);
 }
 
 extern "C" int mdx_probe_mfma_32x32x16_f16(const void* a, const void* b, float* c, mdx_stream_t s) {

@@ -8,6 +8,9 @@ Everything here is float64 numpy on S+1 scalars; the per-element work of a step 
 ``multistep_2m_plan`` is that wiring.  ``solver_plan`` (below it) is the whole of ``DPM_Solver.sample`` -- orders 1-3, multistep,
 singlestep ("DPM-Solver-fast") and singlestep_fixed, the three grids, both solver types, both prediction forms,
 denoise_to_zero -- as one record per model evaluation, each followed by one ``mdx_sampler_step_lin_f32`` launch (solver.py).
+Two options the reference does not have ride on the same records: the Karras sigma grid (``skip_type="karras"``) and the SDE
+form of the first- and second-order multistep update (``sde_eta > 0``: "DPM++ 2M SDE"), whose record carries the noise
+coefficient ``cn`` of the ``mdx_sampler_step_lin_noise_f32`` launch.
 """
 import numpy as np
 
@@ -115,13 +118,29 @@ def multistep_2m_plan(ns, steps, order=2, lower_order_final=True, t_start=None):
 # Buffer roles are symbolic.  Latents: "x" (the latent at the start of the step; the run's start and result) and "y" (the
 # intermediate point of a singlestep update); a launch may write the buffer it reads (element for element).  Model values:
 # three slots "m0", "m1", "m2"; a launch stores m_cur in the slot it does not read.
-SKIP_TYPES = ("logSNR", "time_uniform", "time_quadratic")
+SKIP_TYPES = ("logSNR", "time_uniform", "time_quadratic", "karras")
 VALUE_X0, VALUE_EPS = "x0", "eps"
 
 
-def get_time_steps(ns, skip_type, t_T, t_0, N):
+def check_rho(rho):
+    """`rho` of the Karras grid as a finite float > 0."""
+    v = float(rho)
+    if not (np.isfinite(v) and v > 0.):
+        raise ValueError(f"rho must be a finite number > 0, got {rho!r}")
+    return v
+
+
+def get_time_steps(ns, skip_type, t_T, t_0, N, rho=7.):
     """DPM_Solver.get_time_steps :395-422, N + 1 times from t_T down to t_0, float64 (the reference's fp16 casts of the
-    logSNR endpoints and of the time_uniform grid are not reproduced, see the module docstring)."""
+    logSNR endpoints and of the time_uniform grid are not reproduced, see the module docstring).
+    "karras" (not in the reference; Karras et al. 2022, eq. 5, k-diffusion's get_sigmas_karras): with sigma(t) = exp(-lambda(t))
+    = sigma_t / alpha_t the points are uniform in sigma^(1 / rho), mapped back to times through inverse_lambda."""
+    if skip_type == "karras":
+        rho = check_rho(rho)
+        s_T, s_0 = np.exp(-ns.marginal_lambda(t_T)) ** (1. / rho), np.exp(-ns.marginal_lambda(t_0)) ** (1. / rho)
+        ts = ns.inverse_lambda(-rho * np.log(s_T + (np.arange(N + 1) / N) * (s_0 - s_T)))
+        ts[0], ts[-1] = t_T, t_0        # as for logSNR
+        return ts
     if skip_type == "logSNR":
         lam = np.linspace(ns.marginal_lambda(t_T), ns.marginal_lambda(t_0), N + 1)
         ts = ns.inverse_lambda(lam)
@@ -133,7 +152,8 @@ def get_time_steps(ns, skip_type, t_T, t_0, N):
         ts = np.linspace(t_T ** 0.5, t_0 ** 0.5, N + 1) ** 2
         ts[0], ts[-1] = t_T, t_0
         return ts
-    raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+    raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic' or 'karras'"
+                     .format(skip_type))
 
 
 def singlestep_orders(steps, order):
@@ -249,15 +269,51 @@ def _multistep(f, lam_prev, s, t, h, step_order, solver_type):
     return A, -w * phi_1 * p0 + sign * w * (phi_1 / h + sign) * D1 - w * ((phi_1 + sign * h) / h ** 2 - 0.5) * D2
 
 
-def _record(ns, t, value, A, c, base, model, hist, store, out, order, t_next):
+def _multistep_sde(ns, lam_prev, s, t, h, step_order, eta, s_noise):
+    """The data-prediction multistep update from s to t as an SDE step (not in the reference; diffusers' "sde-dpmsolver++",
+    k-diffusion's sample_dpmpp_2m_sde in its midpoint form): (A, c, cn) with c as _multistep has it and cn the coefficient of
+    the step's N(0, 1) draw.  The exact solution of the reverse SDE with the noise injection scaled by eta, the data prediction
+    held (order 1) or extrapolated linearly in lambda (order 2):
+        A = (sigma_t / sigma_s) e^{-eta h},  phi = expm1(-(1 + eta) h),  cn = s_noise sigma_t sqrt(-expm1(-2 eta h))
+    so that A^2 sigma_s^2 + cn^2 = sigma_t^2 (s_noise = 1) and A alpha_s + sum(c) = alpha_t whatever eta is."""
+    p0, p1, _ = _E
+    alpha_t, sigma_t = float(ns.marginal_alpha(t)), float(ns.marginal_std(t))
+    A = sigma_t / float(ns.marginal_std(s)) * float(np.exp(-eta * h))
+    phi = float(np.expm1(-(1. + eta) * h))
+    cn = s_noise * sigma_t * float(np.sqrt(-np.expm1(-2. * eta * h)))
+    if step_order == 1:
+        return A, -alpha_t * phi * p0, cn
+    r0 = (lam_prev[0] - lam_prev[1]) / h
+    return A, -alpha_t * phi * (1. + 0.5 / r0) * p0 + (0.5 * alpha_t * phi / r0) * p1, cn
+
+
+def check_sde(sde_eta, s_noise, method="multistep", order=2, predict_x0=True, solver_type="dpm_solver"):
+    """(sde_eta, s_noise) as finite floats >= 0; sde_eta > 0 only where the SDE update is defined: the data-prediction
+    multistep update of order 1 or 2 in its 'dpm_solver' (midpoint) form.  s_noise counts only with sde_eta > 0 (1.0 otherwise)."""
+    eta, sn = float(sde_eta), float(s_noise)
+    for name, v, given in (("sde_eta", eta, sde_eta), ("s_noise", sn, s_noise)):
+        if not (np.isfinite(v) and v >= 0.):
+            raise ValueError(f"{name} must be a finite number >= 0, got {given!r}")
+    if eta > 0.:
+        for bad, why in ((method != "multistep", f"method {method!r} (the SDE update is a multistep update)"),
+                         (order == 3, "order 3 (the SDE update is of order 1 or 2)"),
+                         (not predict_x0, "predict_x0=False (the SDE update is in data-prediction form)"),
+                         (solver_type == "taylor", "solver_type 'taylor' (the SDE update is the midpoint form, 'dpm_solver')")):
+            if bad:
+                raise ValueError(f"sde_eta > 0 is not defined with {why}")
+    return eta, sn if eta > 0. else 1.
+
+
+def _record(ns, t, value, A, c, base, model, hist, store, out, order, t_next, cn=0.):
     c = [float(v) for v in c] + [0.] * (3 - len(c))
     return dict(t=float(t), t_next=float(t_next), t_input=float(ns.model_input_time(t)), alpha_m=float(ns.marginal_alpha(t)),
                 sigma_m=float(ns.marginal_std(t)), value=value, A=float(A), c0=c[0], c1=c[1], c2=c[2], base=base, model=model,
-                h1=hist[0] if c[1] != 0. else None, h2=hist[1] if c[2] != 0. else None, store=store, out=out, order=order)
+                h1=hist[0] if c[1] != 0. else None, h2=hist[1] if c[2] != 0. else None, store=store, out=out, order=order,
+                cn=float(cn))
 
 
 def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep", solver_type="dpm_solver", predict_x0=True,
-                lower_order_final=True, denoise_to_zero=False, t_start=None, t_end=None):
+                lower_order_final=True, denoise_to_zero=False, t_start=None, t_end=None, rho=7., sde_eta=0., s_noise=1.):
     """DPM_Solver(predict_x0=...).sample(steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero,
     solver_type) :958-1123 as one record per MODEL EVALUATION, in order; each evaluation is followed by one launch of
         x_out = A * x_base + c0 * m_cur + c1 * h1 + c2 * h2.
@@ -268,7 +324,11 @@ def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep"
     multistep: `steps` evaluations, the first order - 1 updates of lower order, the last ones too under 15 steps with
     lower_order_final; the last target gets no evaluation.  singlestep: the DPM-Solver-fast order lists, `steps` evaluations.
     singlestep_fixed: steps // order updates of `order`.  denoise_to_zero: one more evaluation at t_0 whose data prediction
-    is the result (A = 0, c0 = 1)."""
+    is the result (A = 0, c0 = 1).
+    rho: the exponent of skip_type "karras" (read with that grid only).  sde_eta > 0: every multistep update is the SDE step
+    _multistep_sde describes and its record's launch adds cn * z, z ~ N(0, 1) fresh per record; a record also carries cn (0.0
+    for a deterministic update, denoise_to_zero's included) and draw, its index in the plan (the counter of its noise).
+    sde_eta == 0 takes the deterministic code path: A, c0 .. c2 are then what they have always been."""
     if method == "adaptive":
         raise NotImplementedError("method 'adaptive' is not planned: its step size needs a device-to-host error norm every "
                                   "step, and a plan is made before the first launch")
@@ -280,7 +340,10 @@ def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep"
     if solver_type not in ("dpm_solver", "taylor"):
         raise ValueError("'solver_type' must be either 'dpm_solver' or 'taylor', got {}".format(solver_type))
     if skip_type not in SKIP_TYPES:
-        raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+        raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic' or 'karras'"
+                         .format(skip_type))
+    rho = check_rho(rho) if skip_type == "karras" else 7.
+    sde_eta, s_noise = check_sde(sde_eta, s_noise, method, order, predict_x0, solver_type)
     need = 1 if method == "singlestep" else order        # (:1065 asserts it for multistep; a fixed-order run needs one update)
     if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < need:
         raise ValueError("steps must be an int >= {} for method {} of order {}, got {!r}".format(need, method, order, steps))
@@ -295,7 +358,7 @@ def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep"
     lam_of = lambda t: float(ns.marginal_lambda(t))
     plan = []
     if method == "multistep":
-        ts = get_time_steps(ns, skip_type, t_T, t_0, steps)
+        ts = get_time_steps(ns, skip_type, t_T, t_0, steps, rho)
         lam = ns.marginal_lambda(ts)
         slots = ["m0", "m1", "m2"]      # slots[0]: where this evaluation's value goes; slots[1], slots[2]: the two before it
         for k in range(steps):
@@ -306,23 +369,26 @@ def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep"
                 step_order = min(order, steps + 1 - step)       # :1082-1085
             else:
                 step_order = order
-            A, c = _multistep(f, [lam[k - j] for j in range(step_order)], ts[k], ts[k + 1], lam[k + 1] - lam[k], step_order,
-                              solver_type)
-            plan.append(_record(ns, ts[k], value, A, c, "x", "x", slots[1:], slots[0], "x", step_order, ts[k + 1]))
+            lam_prev, h, cn = [lam[k - j] for j in range(step_order)], lam[k + 1] - lam[k], 0.
+            if sde_eta > 0.:
+                A, c, cn = _multistep_sde(ns, lam_prev, ts[k], ts[k + 1], h, step_order, sde_eta, s_noise)
+            else:
+                A, c = _multistep(f, lam_prev, ts[k], ts[k + 1], h, step_order, solver_type)
+            plan.append(_record(ns, ts[k], value, A, c, "x", "x", slots[1:], slots[0], "x", step_order, ts[k + 1], cn))
             slots = [slots[2], slots[0], slots[1]]
     else:
         if method == "singlestep":
             orders, K = singlestep_orders(steps, order)
             if skip_type == "logSNR":
-                outer = get_time_steps(ns, skip_type, t_T, t_0, K)      # "to reproduce the results in DPM-Solver paper" :474-476
+                outer = get_time_steps(ns, skip_type, t_T, t_0, K, rho)     # "to reproduce the results in DPM-Solver paper" :474-476
             else:
-                outer = get_time_steps(ns, skip_type, t_T, t_0, steps)[np.cumsum([0] + orders)]
+                outer = get_time_steps(ns, skip_type, t_T, t_0, steps, rho)[np.cumsum([0] + orders)]
         else:
             orders = [order] * (steps // order)
-            outer = get_time_steps(ns, skip_type, t_T, t_0, len(orders))
+            outer = get_time_steps(ns, skip_type, t_T, t_0, len(orders), rho)
         for i, o in enumerate(orders):
             s, t = float(outer[i]), float(outer[i + 1])
-            lam_in = ns.marginal_lambda(get_time_steps(ns, skip_type, s, t, o))     # r1, r2 from the inner grid (:1110-1119)
+            lam_in = ns.marginal_lambda(get_time_steps(ns, skip_type, s, t, o, rho))    # r1, r2 from the inner grid (:1110-1119)
             lam_s, h = lam_of(s), lam_of(t) - lam_of(s)
             if o == 1:
                 A, c0 = f.first(s, t, h)
@@ -343,4 +409,6 @@ def solver_plan(ns, steps, order=2, skip_type="time_uniform", method="multistep"
             plan.append(_record(ns, s2, value, A, [c[2], c[0], c[1]], "x", "y", ["m0", "m1"], "m2", "x", 3, t))
     if denoise_to_zero:             # denoise_to_zero_fn :482-486: the data prediction at t_0, whatever the form of the run
         plan.append(_record(ns, t_0, VALUE_X0, 0., [1.], "x", "x", [None, None], "m0", "x", 1, 0.))
+    for i, r in enumerate(plan):
+        r["draw"] = i
     return plan

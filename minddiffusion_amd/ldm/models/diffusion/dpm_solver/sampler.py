@@ -25,6 +25,10 @@ The rest of the reference's solver -- orders 1-3, singlestep / singlestep_fixed,
 solver options (or the constructor's defaults for them): any option off its default runs dpm_solver.solver_plan's records through
 solver.run_solver_plan, one ``mdx_sampler_step_lin_f32`` launch per model evaluation.  The wired configuration below stays on
 the launches it has always made.
+Not in the reference: skip_type="karras" (the Karras sigma grid, exponent `rho`: "DPM++ 2M Karras") and sde_eta > 0 (the SDE
+form of the multistep update with fresh noise each step, scaled by `s_noise`: "DPM++ 2M SDE", diffusers' "sde-dpmsolver++") --
+solver options like the others; a stochastic record's launch is ``mdx_sampler_step_lin_noise_f32``, which draws its noise
+itself from the per-sample seeds.  `eta`, which the pipeline hands every sampler, stays ignored here as in the reference.
 One loop: schedule.dpm_steps gives every sample's launches, and the loop launches from a schedule.ScalarSteps (scalar S, scale and
 rescale: kernel arguments) or from a StepTable merged from the samples' plans and uploaded once (any of them per sample).
 """
@@ -35,22 +39,24 @@ from ....._lib import MdxError
 from ..guided import (GuidedModel, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent, split_conditioning,
                       start_latent)
 from ..schedule import ScalarSteps, dpm_steps, per_request, pred_type, step_table
-from .dpm_solver import NoiseScheduleVP, solver_plan
-from .solver import SOLVER_DEFAULTS, check_max_val, run_solver_plan
+from .dpm_solver import NoiseScheduleVP, check_rho, check_sde, solver_plan
+from .solver import PLAN_OPTIONS, SOLVER_DEFAULTS, check_max_val, run_solver_plan
 
 
 def solver_options(defaults, given):
     """The solver options of a run: `given` (None: not given) over `defaults`, and whether they are the wired configuration
-    (max_val counts only with thresholding on)."""
+    (max_val counts only with thresholding on, rho only with the "karras" grid, s_noise only with sde_eta > 0)."""
     opts = {k: defaults[k] if given.get(k) is None else given[k] for k in SOLVER_DEFAULTS}
     opts["max_val"] = check_max_val(opts["thresholding"], opts["max_val"])
+    opts["rho"] = check_rho(opts["rho"]) if opts["skip_type"] == "karras" else SOLVER_DEFAULTS["rho"]
+    opts["sde_eta"], opts["s_noise"] = check_sde(opts["sde_eta"], opts["s_noise"])      # (solver_plan checks what eta goes with)
     return opts, all(opts[k] == v for k, v in SOLVER_DEFAULTS.items())
 
 
 class DPMSolverSampler:
     def __init__(self, model, **kwargs):
         """kwargs: generator, and the defaults of sample()'s solver options (SOLVER_DEFAULTS' keys: order, skip_type, method,
-        solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end)."""
+        solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end, sde_eta, s_noise, rho)."""
         self.model = model
         self.alphas_cumprod = np.asarray(model.alphas_cumprod, dtype=np.float64)
         self.generator = kwargs.get("generator", None)
@@ -58,7 +64,7 @@ class DPMSolverSampler:
         opts, self.wired = solver_options(self.solver, {})
         if not self.wired:      # a mistake shows where it is made: the plan of a short run, built and dropped
             solver_plan(NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod), 3 * opts["order"],
-                        **{k: opts[k] for k in ("order", "skip_type", "method", "solver_type", "predict_x0", "t_end")})
+                        **{k: opts[k] for k in PLAN_OPTIONS if k != "denoise_to_zero"})
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -88,9 +94,10 @@ class DPMSolverSampler:
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, guidance_rescale=0., t_start=None, seeds=None, order=None, skip_type=None,
                method=None, solver_type=None, predict_x0=None, thresholding=None, max_val=None, denoise_to_zero=None,
-               lower_order_final=None, t_end=None, **kwargs):
+               lower_order_final=None, t_end=None, sde_eta=None, s_noise=None, rho=None, step_noises=None, **kwargs):
         """order, skip_type, method, solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end:
-        the options of the reference's DPM_Solver(...).sample(...) (dpm_solver.solver_plan); None: the sampler's default
+        the options of the reference's DPM_Solver(...).sample(...) (dpm_solver.solver_plan); sde_eta, s_noise, rho: the SDE
+        update and the Karras grid (solver_plan; not in the reference); None: the sampler's default
         (SOLVER_DEFAULTS unless the constructor was given another).  With every option at SOLVER_DEFAULTS -- multistep, order 2,
         time_uniform, data prediction, no thresholding -- the run is the wired one described above, launch for launch.
         Otherwise the plan's records are run by solver.run_solver_plan: S model evaluations (S + 1 with denoise_to_zero), each
@@ -101,8 +108,10 @@ class DPMSolverSampler:
         t_start: a continuous time in (1 / N, T] -- the S evaluations then cover [t_start, 1 / N] instead of [T, 1 / N], from
         x_T = stochastic_encode(., t_start) (the reference's DPM_Solver.sample(t_start=), dpm_solver.py:958-1075).  S == 1 is a
         single first-order update.
-        seeds: `batch_size` ints, one per sample -- x_T (the only draw of this sampler) of sample b then depends on seeds[b]
-        alone (ops.randn_seeded); None: the sampler's generator.
+        seeds: `batch_size` ints, one per sample -- x_T of sample b then depends on seeds[b] alone (ops.randn_seeded), and so
+        does its step noise with sde_eta > 0: stream ops.RNG_STEP, draw = the record's index, drawn INSIDE the step launch (no
+        launch and no tensor of its own); None: the sampler's generator, one torch.randn per stochastic record.  step_noises
+        (tests): step_noises[k] is record k's noise.  `eta` (the reference's keyword) is ignored as in the reference.
         Per request: S, unconditional_guidance_scale and guidance_rescale each take a scalar or `batch_size` values; with any
         sequence every step is one ops.sampler_step_table launch on the rows of a StepTable built and uploaded before the
         loop.  Sample b runs its own multistep_2m_plan of S[b] steps -- its order and its lower-order final step included -- on
@@ -114,7 +123,7 @@ class DPMSolverSampler:
         opts, wired = solver_options(self.solver, dict(
             order=order, skip_type=skip_type, method=method, solver_type=solver_type, predict_x0=predict_x0,
             thresholding=thresholding, max_val=max_val, denoise_to_zero=denoise_to_zero, lower_order_final=lower_order_final,
-            t_end=t_end))
+            t_end=t_end, sde_eta=sde_eta, s_noise=s_noise, rho=rho))
         per = per_request(S, unconditional_guidance_scale, guidance_rescale, batch_size)
         if per is not None and not wired:
             changed = sorted(k for k, v in SOLVER_DEFAULTS.items() if opts[k] != v)
@@ -128,7 +137,7 @@ class DPMSolverSampler:
                                  "score_corrector or quantize_x0")
             if len(set(per[0])) > 1 and t_start is not None:
                 raise ValueError("per-sample S with different values runs every sample's own full schedule: not with t_start")
-        check_seed_sources(seeds, self.generator)
+        check_seed_sources(seeds, self.generator, step_noises=step_noises)
         if t_start is not None:
             t_start = self._check_t_start(t_start)
         if conditioning is None:
@@ -141,20 +150,18 @@ class DPMSolverSampler:
         if cond is not None and cond.shape[0] != batch_size:
             print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
         size = (batch_size,) + tuple(shape)
-        img = start_latent(x_T, check_seeds(seeds, batch_size, dev), size, dev, self.generator)
+        seeds = check_seeds(seeds, batch_size, dev)
+        img = start_latent(x_T, seeds, size, dev, self.generator)
         ns = NoiseScheduleVP("discrete", alphas_cumprod=self.alphas_cumprod)
         if not wired:
             # the whole solver: one loop over solver_plan's records, t_rows = every evaluation's t_input (one time-embedding
             # table per run, as below)
-            plan = solver_plan(ns, S, order=opts["order"], skip_type=opts["skip_type"], method=opts["method"],
-                               solver_type=opts["solver_type"], predict_x0=opts["predict_x0"],
-                               lower_order_final=opts["lower_order_final"], denoise_to_zero=opts["denoise_to_zero"],
-                               t_start=t_start, t_end=opts["t_end"])
+            plan = solver_plan(ns, S, t_start=t_start, **{k: opts[k] for k in PLAN_OPTIONS})
             scale = float(unconditional_guidance_scale)
             guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
                                  [r["t_input"] for r in plan])
             return run_solver_plan(plan, guided, img, scale, pred_type(self.model), guidance_rescale, opts["thresholding"],
-                                   opts["max_val"], callback, img_callback), None
+                                   opts["max_val"], callback, img_callback, seeds, self.generator, step_noises), None
         # the launches of the run (schedule.dpm_steps) behind one surface: kernel arguments, or per request the rows of a table.
         # Either way a sample's previous data prediction is read only while its own float32 c1 is non-zero.
         counts = [S] * batch_size if per is None else per[0]

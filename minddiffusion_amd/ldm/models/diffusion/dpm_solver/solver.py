@@ -4,7 +4,9 @@
 The arithmetic is dpm_solver.solver_plan's (host, float64): one record per model evaluation.  run_solver_plan is the one loop
 that drives a plan -- DPMSolverSampler's non-default configurations and DPM_Solver.sample both end in it: per record one
 GuidedModel call (the UNet on the guidance batch) and ONE ops.sampler_step_lin launch, which turns the UNet output into the
-model value (CFG combine, guidance rescale, v -> eps, data prediction, dynamic thresholding) and forms the update.  The
+model value (CFG combine, guidance rescale, v -> eps, data prediction, dynamic thresholding) and forms the update; a record
+of a stochastic plan (sde_eta > 0: cn != 0) goes through ops.sampler_step_lin_noise instead, which adds cn * N(0, 1) in the
+same launch -- drawn inside it from per-sample seeds, or read from a tensor.  The
 latents ("x", "y") and the model-value slots ("m0" .. "m2") are allocated once; the plan's roles rotate them by reference.
 """
 import numpy as np
@@ -12,11 +14,14 @@ import torch
 
 from ..... import ops
 from ....._lib import MdxError
-from ..guided import GuidedModel, check_guidance_rescale
+from ..guided import GuidedModel, check_guidance_rescale, check_seed_sources, check_seeds
 from .dpm_solver import VALUE_X0, solver_plan
 
 SOLVER_DEFAULTS = dict(order=2, skip_type="time_uniform", method="multistep", solver_type="dpm_solver", predict_x0=True,
-                       thresholding=False, max_val=1., denoise_to_zero=False, lower_order_final=True, t_end=None)
+                       thresholding=False, max_val=1., denoise_to_zero=False, lower_order_final=True, t_end=None, sde_eta=0.,
+                       s_noise=1., rho=7.)
+PLAN_OPTIONS = ("order", "skip_type", "method", "solver_type", "predict_x0", "lower_order_final", "denoise_to_zero", "t_end", "rho",
+                "sde_eta", "s_noise")      # SOLVER_DEFAULTS' keys that are solver_plan's arguments
 
 
 def check_max_val(thresholding, max_val):
@@ -30,21 +35,33 @@ def check_max_val(thresholding, max_val):
 
 
 def run_solver_plan(plan, guided, x, scale, pred, guidance_rescale=0., thresholding=False, max_val=1., callback=None,
-                    img_callback=None):
+                    img_callback=None, seeds=None, generator=None, step_noises=None):
     """Run `plan` (solver_plan's records) from the latent x ([B, C, H, W] fp32, overwritten: the run's "x" buffer) with
     guided = GuidedModel(..., t_steps=[r["t_input"] for r in plan]); returns the result, which is x.  No device work in the
-    loop besides the model call and the step launch; callback(i) and img_callback(model value, i) fire once per evaluation."""
+    loop besides the model call and the step launch; callback(i) and img_callback(model value, i) fire once per evaluation.
+    The noise of a record with cn != 0 (a stochastic plan): with `seeds` (the [B] device tensor of check_seeds) drawn inside the
+    step launch, stream ops.RNG_STEP, draw = the record's index -- no launch and no tensor of its own; else step_noises[index]
+    (test injection); else one torch.randn from `generator`.  A record with cn == 0 makes the launch it has always made."""
     roles = {name for r in plan for name in (r["model"], r["base"], r["out"], r["store"])}
     bufs = {name: torch.empty_like(x) for name in sorted(roles - {"x"})}
     bufs["x"] = x
     for i, r in enumerate(plan):
         out_u, out_c = guided(bufs[r["model"]], i)
         x0 = r["value"] == VALUE_X0
-        ops.sampler_step_lin(bufs[r["base"]], bufs[r["model"]], out_u, out_c, scale, pred, guidance_rescale,
-                             ops.VALUE_X0 if x0 else ops.VALUE_EPS, r["alpha_m"], r["sigma_m"],
-                             None if r["h1"] is None else bufs[r["h1"]], None if r["h2"] is None else bufs[r["h2"]], r["A"],
-                             r["c0"], r["c1"], r["c2"], bufs[r["store"]], bufs[r["out"]], thresholding=thresholding and x0,
-                             max_val=max_val)
+        args = (bufs[r["base"]], bufs[r["model"]], out_u, out_c, scale, pred, guidance_rescale,
+                ops.VALUE_X0 if x0 else ops.VALUE_EPS, r["alpha_m"], r["sigma_m"],
+                None if r["h1"] is None else bufs[r["h1"]], None if r["h2"] is None else bufs[r["h2"]], r["A"],
+                r["c0"], r["c1"], r["c2"], bufs[r["store"]], bufs[r["out"]])
+        if r["cn"] == 0.:
+            ops.sampler_step_lin(*args, thresholding=thresholding and x0, max_val=max_val)
+        else:
+            noise = None
+            if seeds is None and step_noises is not None:
+                noise = torch.as_tensor(step_noises[r["draw"]]).to(device=x.device, dtype=torch.float32).contiguous()
+            elif seeds is None:
+                noise = torch.randn(x.shape, device=x.device, dtype=torch.float32, generator=generator)
+            ops.sampler_step_lin_noise(*args, r["cn"], noise=noise, seeds=seeds, stream=ops.RNG_STEP, draw=r["draw"],
+                                       thresholding=thresholding and x0, max_val=max_val)
         if callback:
             callback(i)
         if img_callback:
@@ -135,13 +152,18 @@ class DPM_Solver:
 
     def sample(self, x, steps=20, t_start=None, t_end=None, order=3, skip_type="time_uniform", method="singlestep",
                lower_order_final=True, denoise_to_zero=False, solver_type="dpm_solver", atol=0.0078, rtol=0.05, callback=None,
-               img_callback=None):
+               img_callback=None, rho=7., sde_eta=0., s_noise=1., seeds=None, generator=None, step_noises=None):
+        """rho (with skip_type="karras"), sde_eta, s_noise: solver_plan's options, not in the reference.  The noise of a
+        stochastic run (sde_eta > 0): per sample from `seeds` (one int per sample), drawn inside the step launches; else from
+        `generator` (None: torch's default); step_noises injects it for tests."""
         ns = self.noise_schedule
         plan = solver_plan(ns, steps, order=order, skip_type=skip_type, method=method, solver_type=solver_type,
                            predict_x0=self.predict_x0, lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
-                           t_start=t_start, t_end=t_end)
+                           t_start=t_start, t_end=t_end, rho=rho, sde_eta=sde_eta, s_noise=s_noise)
+        check_seed_sources(seeds, generator, step_noises=step_noises)
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4):
             raise MdxError("DPM_Solver.sample: x must be a CUDA(HIP) tensor [B, C, H, W]")
+        seeds = check_seeds(seeds, int(x.shape[0]), x.device)
         x = x.to(torch.float32).contiguous().clone()
         t_inputs = [r["t_input"] for r in plan]
         if isinstance(self.model, WrappedModel):
@@ -151,4 +173,4 @@ class DPM_Solver:
                                  None, 1., x.device, t_inputs)
             scale, pred = 1., ops.PRED_EPS
         return run_solver_plan(plan, guided, x, scale, pred, check_guidance_rescale(0.), self.thresholding, self.max_val,
-                               callback, img_callback)
+                               callback, img_callback, seeds, generator, step_noises)

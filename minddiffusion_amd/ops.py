@@ -837,16 +837,9 @@ def sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out
 VALUE_X0, VALUE_EPS = 0, 1     # MDX_VALUE_* of include/mdx.h
 
 
-def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
-                     h1, h2, A, c0, c1, c2, model_out, x_out, thresholding=False, max_val=1., model_pre_out=None, thr_out=None,
-                     factor_out=None):
-    """The step launch of the whole DPM-Solver (see include/mdx.h): the model value `model_out` -- the data prediction
-    (VALUE_X0, dynamically thresholded at `max_val` if `thresholding`) or the noise prediction (VALUE_EPS) from the UNet
-    output halves out_u / out_c evaluated on x_model at the schedule point (alpha_m, sigma_m), after the CFG combine, the
-    guidance rescale and the v -> eps conversion -- and x_out = A x_base + c0 model_out + c1 h1 + c2 h2, in ONE launch.  A term
-    with a coefficient of exactly 0 is skipped (h1 / h2 may then be None).  x_out may be x_base and / or x_model; nothing else
-    may overlap.  Optional outputs: model_pre_out (the value before thresholding), thr_out [B] (the threshold s), factor_out
-    [B] (the rescale factor).  Every tensor's dtype, layout and extent is checked here: the library sees pointers only."""
+def _step_lin_args(fn, x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m, h1,
+                   h2, A, c0, c1, c2, model_out, x_out, thresholding, max_val, model_pre_out, thr_out, factor_out):
+    """The checks of both step launches of the solver and the arguments they share, up to factor_out."""
     _chk(x_base, f32, "x_base")
     if x_base.dim() != 4:
         raise _lib.MdxError(f"x_base: expected [B, C, H, W], got {tuple(x_base.shape)}")
@@ -854,7 +847,7 @@ def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidan
     if x_model is None:
         x_model = x_base
     if out_c is None or model_out is None or x_out is None:
-        raise _lib.MdxError("sampler_step_lin: out_c, model_out and x_out are required")
+        raise _lib.MdxError(f"{fn}: out_c, model_out and x_out are required")
     for name, t in (("x_model", x_model), ("h1", h1), ("h2", h2), ("model_out", model_out), ("x_out", x_out),
                     ("model_pre_out", model_pre_out)):
         _chk(t, f32, name)
@@ -869,11 +862,51 @@ def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidan
         _chk(t, f32, name)
         if t is not None and t.numel() < B:
             raise _lib.MdxError(f"{name}: needs {B} elements, has {t.numel()}")
+    return (_ptr(x_base), _ptr(x_model), _ptr(out_u), _ptr(out_c), ld, float(cfg_scale), int(pred_type), float(guidance_rescale),
+            int(value_type), float(alpha_m), float(sigma_m), int(bool(thresholding)), float(max_val), _ptr(h1), _ptr(h2), float(A),
+            float(c0), float(c1), float(c2), _ptr(model_out), _ptr(x_out), _ptr(model_pre_out), _ptr(thr_out), _ptr(factor_out))
+
+
+def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
+                     h1, h2, A, c0, c1, c2, model_out, x_out, thresholding=False, max_val=1., model_pre_out=None, thr_out=None,
+                     factor_out=None):
+    """The step launch of the whole DPM-Solver (see include/mdx.h): the model value `model_out` -- the data prediction
+    (VALUE_X0, dynamically thresholded at `max_val` if `thresholding`) or the noise prediction (VALUE_EPS) from the UNet
+    output halves out_u / out_c evaluated on x_model at the schedule point (alpha_m, sigma_m), after the CFG combine, the
+    guidance rescale and the v -> eps conversion -- and x_out = A x_base + c0 model_out + c1 h1 + c2 h2, in ONE launch.  A term
+    with a coefficient of exactly 0 is skipped (h1 / h2 may then be None).  x_out may be x_base and / or x_model; nothing else
+    may overlap.  Optional outputs: model_pre_out (the value before thresholding), thr_out [B] (the threshold s), factor_out
+    [B] (the rescale factor).  Every tensor's dtype, layout and extent is checked here: the library sees pointers only."""
     _lib.check(_lib.load().mdx_sampler_step_lin_f32(
-        _ptr(x_base), _ptr(x_model), _ptr(out_u), _ptr(out_c), ld, float(cfg_scale), int(pred_type), float(guidance_rescale),
-        int(value_type), float(alpha_m), float(sigma_m), int(bool(thresholding)), float(max_val), _ptr(h1), _ptr(h2), float(A),
-        float(c0), float(c1), float(c2), _ptr(model_out), _ptr(x_out), _ptr(model_pre_out), _ptr(thr_out), _ptr(factor_out),
-        B, C, H, W, _stream()), "mdx_sampler_step_lin_f32")
+        *_step_lin_args("sampler_step_lin", x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type,
+                        alpha_m, sigma_m, h1, h2, A, c0, c1, c2, model_out, x_out, thresholding, max_val, model_pre_out, thr_out,
+                        factor_out), *x_base.shape, _stream()), "mdx_sampler_step_lin_f32")
+
+
+def sampler_step_lin_noise(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
+                           h1, h2, A, c0, c1, c2, model_out, x_out, cn, noise=None, seeds=None, stream=None, draw=0,
+                           thresholding=False, max_val=1., model_pre_out=None, thr_out=None, factor_out=None):
+    """sampler_step_lin for a stochastic update (mdx_sampler_step_lin_noise_f32): the same launch with x_out += cn * z, z ~
+    N(0, 1) from exactly one source -- `noise` [B, C, H, W] fp32, or `seeds` (ops.seeds_tensor, [B]): then z is drawn inside
+    the launch, the bits randn_seeded(seeds, stream, draw, (C, H, W)) would store, and sample b's noise depends on seeds[b]
+    alone.  stream: None = RNG_STEP.  cn == 0 is sampler_step_lin bit for bit and reads neither source.  noise may overlap no
+    output."""
+    args = _step_lin_args("sampler_step_lin_noise", x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale,
+                          value_type, alpha_m, sigma_m, h1, h2, A, c0, c1, c2, model_out, x_out, thresholding, max_val,
+                          model_pre_out, thr_out, factor_out)
+    B = int(x_base.shape[0])
+    _chk(noise, f32, "noise")
+    if noise is not None and tuple(noise.shape) != tuple(x_base.shape):
+        raise _lib.MdxError(f"noise: expected {tuple(x_base.shape)}, got {tuple(noise.shape)}")
+    if seeds is not None:
+        if not (isinstance(seeds, torch.Tensor) and tuple(seeds.shape) == (B,)):
+            raise _lib.MdxError(f"sampler_step_lin_noise: seeds must be a [{B}] int64 device tensor (ops.seeds_tensor)")
+        _chk(seeds, torch.int64, "seeds")
+    stream = RNG_STEP if stream is None else int(stream)
+    if not (0 <= stream < (1 << 31) and 0 <= int(draw) < (1 << 32)):
+        raise _lib.MdxError(f"sampler_step_lin_noise: stream must be in [0, 2^31) and draw in [0, 2^32), got {stream!r}, {draw!r}")
+    _lib.check(_lib.load().mdx_sampler_step_lin_noise_f32(*args, float(cn), _ptr(noise), _ptr(seeds), stream, int(draw),
+                                                          *x_base.shape, _stream()), "mdx_sampler_step_lin_noise_f32")
 
 
 # ---- sampling sessions (include/mdx.h, "slots"): the samples of a batch are slots that requests enter and leave

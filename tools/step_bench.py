@@ -21,6 +21,13 @@ median over rounds of (replay time / launches), and rescale - pred, which is wha
   lin / lin_rescale                       the spread form / the owned form with guidance_rescale = 0.7
   lin_threshold / lin_rescale_threshold   the owned form with dynamic thresholding (the radix select), without / with rescale
   select_us = lin_rescale_threshold - lin_rescale: what the selection and the second pass over the sample cost
+--sde measures the stochastic DPM-Solver step (mdx_sampler_step_lin_noise_f32, a 2M-SDE record: one stored model value read) the
+same way, in the spread form and (`_rescale`) the owned form with guidance_rescale = 0.7:
+  lin / lin_rescale                    mdx_sampler_step_lin_f32 alone, the deterministic record's launch
+  seeded / seeded_rescale              the noise drawn inside the launch from per-sample seeds
+  tensor / tensor_rescale              the noise read from a tensor (no launch for the tensor counted)
+  three / three_rescale                the three launches the seeded launch replaces: ops.randn_seeded, the lin launch, an axpy
+  draw_us = seeded - lin: what drawing inside the launch costs; saved_us = three - seeded
 Prints one JSON line (and writes --out)."""
 import argparse
 import json
@@ -110,6 +117,48 @@ def bench_lin(shape, launches, rounds, warmup):
     return res
 
 
+def bench_sde(shape, launches, rounds, warmup):
+    """The stochastic step beside the deterministic one and beside the three launches it replaces."""
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    B, C, H, W = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    r32 = lambda: torch.randn(shape, device=dev, generator=g)
+    x, h1, z = r32(), r32(), r32()
+    out = torch.randn((2 * B, H * W, 8), device=dev, generator=g).half()
+    out_u, out_c = out[:B], out[B:]
+    m_out, x_out, z_out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    seeds = ops.seeds_tensor(list(range(100, 100 + B)), dev)
+    cn, draw = 0.37, [0]
+
+    def lin(phi):
+        ops.sampler_step_lin(x, None, out_u, out_c, 7.5, ops.PRED_V, phi, ops.VALUE_X0, 0.8, 0.6, h1, None, 0.9, 0.3, -0.2, 0.,
+                             m_out, x_out)
+
+    def noisy(phi, **src):
+        draw[0] += 1     # a new draw per launch, as in a run
+        ops.sampler_step_lin_noise(x, None, out_u, out_c, 7.5, ops.PRED_V, phi, ops.VALUE_X0, 0.8, 0.6, h1, None, 0.9, 0.3, -0.2,
+                                   0., m_out, x_out, cn, draw=draw[0], **src)
+
+    def three(phi):
+        draw[0] += 1
+        ops.randn_seeded(seeds, ops.RNG_STEP, draw[0], shape[1:], out=z_out)
+        lin(phi)
+        x_out.add_(z_out, alpha=cn)
+    entries = {}
+    for tag, phi in (("", 0.), ("_rescale", 0.7)):
+        entries["lin" + tag] = lambda phi=phi: lin(phi)
+        entries["seeded" + tag] = lambda phi=phi: noisy(phi, seeds=seeds)
+        entries["tensor" + tag] = lambda phi=phi: noisy(phi, noise=z)
+        entries["three" + tag] = lambda phi=phi: three(phi)
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    for tag in ("", "_rescale"):
+        res["draw" + tag + "_us"] = round(res["seeded" + tag + "_us"] - res["lin" + tag + "_us"], 3)
+        res["saved" + tag + "_us"] = round(res["three" + tag + "_us"] - res["seeded" + tag + "_us"], 3)
+    return res
+
+
 def bench_noise(shape, launches, rounds, warmup):
     import torch
     from minddiffusion_amd import ops
@@ -176,12 +225,13 @@ def main():
     ap.add_argument("--noise", action="store_true", help="measure the stochastic step's noise preparation instead")
     ap.add_argument("--table", action="store_true", help="measure the table-driven entry beside the scalar entries instead")
     ap.add_argument("--lin", action="store_true", help="measure the DPM-Solver step launch (mdx_sampler_step_lin_f32) instead")
+    ap.add_argument("--sde", action="store_true", help="measure the stochastic DPM-Solver step (mdx_sampler_step_lin_noise_f32) instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("step_bench: needs a GPU")
-    bench = bench_noise if a.noise else bench_table if a.table else bench_lin if a.lin else bench_shape
+    bench = bench_noise if a.noise else bench_table if a.table else bench_lin if a.lin else bench_sde if a.sde else bench_shape
     res = {"launches": a.launches, "rounds": a.rounds, "shapes": [bench(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
     if a.noise:
         res["what"] = "noise preparation of a stochastic step, us per step"
