@@ -4,10 +4,7 @@
 
 namespace {
 
-inline int grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
+constexpr size_t GLIDE_GRID_CAP = 4096;      // these launches have always run on up to 4096 blocks (grid_for's default: 2048)
 
 // nn.AvgPool2d(2,2) on NHWC fp16 (unet.py:74): one thread per 8-channel chunk of an output pixel
 __global__ __launch_bounds__(256) void avgpool_kernel(const f16* __restrict__ x, f16* __restrict__ y, int B, int H,
@@ -184,7 +181,7 @@ extern "C" int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, i
     MDX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 8 == 0,
                 "mdx_avgpool2x2_f16: bad arguments");
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-    hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, (const f16*)x, (f16*)y, B, H, W, C);
+    hipLaunchKernelGGL(avgpool_kernel, dim3(grid_for(total, GLIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, (const f16*)x, (f16*)y, B, H, W, C);
     MDX_LAUNCH_CHECK("mdx_avgpool2x2_f16");
     return MDX_OK;
 }
@@ -192,7 +189,7 @@ extern "C" int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, i
 extern "C" int mdx_upsample_nearest2x_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s) {
     MDX_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "mdx_upsample_nearest2x_f16: bad arguments");
     const size_t total = (size_t)B * 4 * H * W * (C / 8);
-    hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, (const f16*)x, (f16*)y, B, H, W, C);
+    hipLaunchKernelGGL(upsample_kernel, dim3(grid_for(total, GLIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, (const f16*)x, (f16*)y, B, H, W, C);
     MDX_LAUNCH_CHECK("mdx_upsample_nearest2x_f16");
     return MDX_OK;
 }
@@ -203,7 +200,7 @@ extern "C" int mdx_glide_text_embed_f16(const int* tokens, const int* mask, cons
     MDX_REQUIRE(tokens && mask && tok_emb && pos && pad && out && B > 0 && T > 0 && width % 8 == 0 && n_vocab > 0,
                 "mdx_glide_text_embed_f16: bad arguments");
     const size_t total = (size_t)B * T * (width / 8);
-    hipLaunchKernelGGL(text_embed_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, tokens, mask,
+    hipLaunchKernelGGL(text_embed_kernel, dim3(grid_for(total, GLIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, tokens, mask,
                        (const f16*)tok_emb, (const f16*)pos, (const f16*)pad, (f16*)out, B, T, width, n_vocab);
     MDX_LAUNCH_CHECK("mdx_glide_text_embed_f16");
     return MDX_OK;
@@ -212,7 +209,7 @@ extern "C" int mdx_glide_text_embed_f16(const int* tokens, const int* mask, cons
 extern "C" int mdx_glide_superres_input_f16(const float* x, const float* low, void* out, int B, int S, int s_low,
                                             mdx_stream_t s) {
     MDX_REQUIRE(x && low && out && B > 0 && S > 0 && s_low > 0, "mdx_glide_superres_input_f16: bad arguments");
-    hipLaunchKernelGGL(superres_input_kernel, dim3(grid_for((size_t)B * S * S)), dim3(256), 0, (hipStream_t)s, x, low,
+    hipLaunchKernelGGL(superres_input_kernel, dim3(grid_for((size_t)B * S * S, GLIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, x, low,
                        (f16*)out, B, S, s_low);
     MDX_LAUNCH_CHECK("mdx_glide_superres_input_f16");
     return MDX_OK;
@@ -245,7 +242,7 @@ extern "C" int mdx_glide_step_f32(const float* x, const void* out_c, const void*
     p.sqrt_ab_prev = coef8[6];
     p.sqrt_1m_ab_prev = coef8[7];
     p.noise_scale = noise_scale;
-    hipLaunchKernelGGL(glide_step_kernel, dim3(grid_for((size_t)B * 3 * H * W)), dim3(256), 0, (hipStream_t)s, p);
+    hipLaunchKernelGGL(glide_step_kernel, dim3(grid_for((size_t)B * 3 * H * W, GLIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, p);
     MDX_LAUNCH_CHECK("mdx_glide_step_f32");
     return MDX_OK;
 }

@@ -99,6 +99,12 @@ struct MdxPerDeviceOnce {
     }
 };
 
+// The grid of a 256-thread grid-stride elementwise launch over `total` items: one block per 256 items, at most `cap` blocks.
+inline int grid_for(size_t total, size_t cap = 2048) {
+    const size_t b = (total + 255) / 256;
+    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
 // ---- device helpers
 // sigmoid(x) = 1 / (1 + 2^(-x log2 e)) on the raw transcendental units (v_exp_f32 + v_rcp_f32, 1 ulp each): an IEEE
 // division here costs ~10 VALU instructions per element and the epilogues / GroupNorm apply it to every output.

@@ -735,16 +735,26 @@ def dense_small(x, w, b, act_in=False, act_out=False, out=None):
     return out
 
 
+def _step_args(B, olds, coef=None, factor_out=None):
+    """What the eps-family step wrappers share: the three history pointers (olds padded with None), the coef4 array (None for
+    the entries whose coefficients live on the device; the caller keeps it alive over the call) and the factor_out check."""
+    o = [_ptr(t) for t in list(olds) + [None] * (3 - len(olds))]
+    c4 = None if coef is None else ctypes.cast((ctypes.c_float * 4)(*[float(v) for v in coef]), ctypes.c_void_p)
+    if factor_out is not None:
+        _chk(factor_out, f32, "factor_out")
+        if factor_out.numel() < B:
+            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    return o, c4
+
+
 def sampler_step(x, eps_u, eps_c, eps_ld, cfg_scale, olds, coef, sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef,
                  sigma, noise, e_t_out, x_prev, pred_x0):
     """Fused CFG + multistep mix + DDIM update (see include/mdx.h)."""
     B, C, H, W = x.shape
-    c4 = (ctypes.c_float * 4)(*[float(v) for v in coef])
-    o = list(olds) + [None] * (3 - len(olds))
+    o, c4 = _step_args(B, olds, coef)
     _lib.check(_lib.load().mdx_sampler_step_f32(
-        _ptr(x), _ptr(eps_u), _ptr(eps_c), int(eps_ld), float(cfg_scale), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
-        ctypes.cast(c4, ctypes.c_void_p), float(sqrt_at), float(sqrt_one_minus_at), float(sqrt_a_prev), float(dir_coef),
-        float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), B, C, H, W, _stream()),
+        _ptr(x), _ptr(eps_u), _ptr(eps_c), int(eps_ld), float(cfg_scale), *o, c4, float(sqrt_at), float(sqrt_one_minus_at),
+        float(sqrt_a_prev), float(dir_coef), float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), B, C, H, W, _stream()),
         "mdx_sampler_step_f32")
 
 
@@ -758,13 +768,11 @@ def sampler_step_pred(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, sq
     (x_model, sqrt_at_model, sqrt_one_minus_at_model) the model was evaluated at is part of the same launch (see
     include/mdx.h).  x_model None = x."""
     B, C, H, W = x.shape
-    c4 = (ctypes.c_float * 4)(*[float(v) for v in coef])
-    o = list(olds) + [None] * (3 - len(olds))
+    o, c4 = _step_args(B, olds, coef)
     _lib.check(_lib.load().mdx_sampler_step_pred_f32(
         _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_ld), float(cfg_scale), int(pred_type),
-        float(sqrt_at_model), float(sqrt_one_minus_at_model), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
-        ctypes.cast(c4, ctypes.c_void_p), float(sqrt_at), float(sqrt_one_minus_at), float(sqrt_a_prev), float(dir_coef),
-        float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), B, C, H, W, _stream()),
+        float(sqrt_at_model), float(sqrt_one_minus_at_model), *o, c4, float(sqrt_at), float(sqrt_one_minus_at),
+        float(sqrt_a_prev), float(dir_coef), float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), B, C, H, W, _stream()),
         "mdx_sampler_step_pred_f32")
 
 
@@ -775,17 +783,11 @@ def sampler_step_rescale(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
     f[b] = guidance_rescale * std(out_c[b]) / std(m[b]) + (1 - guidance_rescale) inside the same launch (see
     include/mdx.h).  factor_out: optional [B] fp32 tensor that receives f."""
     B, C, H, W = x.shape
-    c4 = (ctypes.c_float * 4)(*[float(v) for v in coef])
-    o = list(olds) + [None] * (3 - len(olds))
-    if factor_out is not None:
-        _chk(factor_out, f32, "factor_out")
-        if factor_out.numel() < B:
-            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    o, c4 = _step_args(B, olds, coef, factor_out)
     _lib.check(_lib.load().mdx_sampler_step_rescale_f32(
         _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_ld), float(cfg_scale), int(pred_type),
-        float(sqrt_at_model), float(sqrt_one_minus_at_model), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
-        ctypes.cast(c4, ctypes.c_void_p), float(sqrt_at), float(sqrt_one_minus_at), float(sqrt_a_prev), float(dir_coef),
-        float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), float(guidance_rescale), _ptr(factor_out),
+        float(sqrt_at_model), float(sqrt_one_minus_at_model), *o, c4, float(sqrt_at), float(sqrt_one_minus_at),
+        float(sqrt_a_prev), float(dir_coef), float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), float(guidance_rescale), _ptr(factor_out),
         B, C, H, W, _stream()), "mdx_sampler_step_rescale_f32")
 
 
@@ -823,15 +825,10 @@ def sampler_step_table(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out
     _chk(table, f32, "table")
     if tuple(table.shape) != (B, STEP_ROW):
         raise _lib.MdxError(f"table: expected [{B}, {STEP_ROW}], got {tuple(table.shape)}")
-    o = list(olds) + [None] * (3 - len(olds))
-    if factor_out is not None:
-        _chk(factor_out, f32, "factor_out")
-        if factor_out.numel() < B:
-            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    o, _ = _step_args(B, olds, factor_out=factor_out)
     _lib.check(_lib.load().mdx_sampler_step_table_f32(
-        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), _ptr(o[0]), _ptr(o[1]),
-        _ptr(o[2]), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(table), int(bool(any_rescale)),
-        _ptr(factor_out), B, C, H, W, _stream()), "mdx_sampler_step_table_f32")
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), *o, _ptr(noise),
+        _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(table), int(bool(any_rescale)), _ptr(factor_out), B, C, H, W, _stream()), "mdx_sampler_step_table_f32")
 
 
 VALUE_X0, VALUE_EPS = 0, 1     # MDX_VALUE_* of include/mdx.h
@@ -928,14 +925,9 @@ def sampler_step_slots(x, x_model, out_u, out_c, pred_type, olds, noise, e_t_out
     if sched.dim() != 3 or sched.shape[0] != B or sched.shape[2] != STEP_ROW:
         raise _lib.MdxError(f"sched: expected [{B}, cap, {STEP_ROW}], got {tuple(sched.shape)}")
     _chk_slots(B, slot_start, slot_len)
-    o = list(olds) + [None] * (3 - len(olds))
-    if factor_out is not None:
-        _chk(factor_out, f32, "factor_out")
-        if factor_out.numel() < B:
-            raise _lib.MdxError(f"factor_out: needs {B} elements, has {factor_out.numel()}")
+    o, _ = _step_args(B, olds, factor_out=factor_out)
     _lib.check(_lib.load().mdx_sampler_step_slots_f32(
-        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), _ptr(o[0]), _ptr(o[1]),
-        _ptr(o[2]), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(sched), _ptr(slot_start), _ptr(slot_len),
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_c.shape[-1]), int(pred_type), *o, _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), _ptr(sched), _ptr(slot_start), _ptr(slot_len),
         int(sched.shape[1]), int(tick), int(bool(any_rescale)), _ptr(factor_out), B, C, H, W, _stream()),
         "mdx_sampler_step_slots_f32")
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Streaming-bandwidth probe: what one workgroup per CU pulls via LDS-DMA vs plain loads (see small.hip)."""
+"""Streaming-bandwidth probe: what one workgroup per CU pulls via LDS-DMA vs plain loads (see probes.hip)."""
 import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
