@@ -946,6 +946,27 @@ int mdx_window_average_regions_f16(const void* windows, void* out, const float* 
                                    const int* pair_first_host, int P, const float* masks, int R, int NB, int C, int ld, int Hc,
                                    int Wc, int h, int w, mdx_stream_t s);
 
+/* ---- Tiled VAE decode (csrc/window.hip): the decoder's outputs on the tiles of a large canvas, fp32 NCHW [NB * N][C][TH][TW],
+ * tile k = iy * nx + ix of canvas row j in row j * N + k (the gather's row order), blended onto the image canvas out fp32 NCHW
+ * [NB][C][Hc][Wc] with feathered weights.  The grid is a window grid on the IMAGE canvas, in output pixels: offsets / offsets_host
+ * as above, wrap_x (0 | 1) as in the two entries above.  One lane owns four consecutive columns of one (b, c, y) row (16-byte
+ * accesses) when TW, Wc and every x offset are multiples of 4 and both bases are 16-byte aligned, one column otherwise -- the same
+ * bits; every output element has one writer, no atomics, no weight tensor.  The arithmetic is part of the contract:
+ *   the weight of tile-local pixel (yy, xx) is q = (float)(min(yy + 1, TH - yy, ramp_y) * min(xx + 1, TW - xx, ramp_x)), an
+ *   integer (ramps in [1, 4096]: the product is exact in fp32);
+ *   the covering tiles are visited in ascending k (rows, then columns);
+ *   first term: acc = q * e, qsum = q;  later terms: acc = acc + q * e with the fp32 multiply and the fp32 add ROUNDED
+ *   SEPARATELY (not an fma), qsum = qsum + q;
+ *   raw = acc / qsum, one IEEE fp32 division;  a pixel covered by exactly ONE tile takes that tile's bits unchanged;
+ *   MDX_TILE_RAW writes raw;  MDX_TILE_UNIT writes min(max((raw + 1.0f) / 2.0f, 0.0f), 1.0f), the bits of
+ *   torch.clamp((raw + 1.0) / 2.0, 0.0, 1.0).
+ * Refused, before any launch (MDX_E_INVALID): null pointers, wrap_x other than 0 | 1, everything the window entries refuse of the
+ * extents and the offset table (the x axis by the wrapped rule when wrap_x is 1), a ramp < 1 or > 4096, an unknown mode, out
+ * overlapping tiles.  Only out is written. */
+enum { MDX_TILE_RAW = 0, MDX_TILE_UNIT = 1 };
+int mdx_tile_blend_f32(const float* tiles, float* out, const int* offsets, const int* offsets_host, int ny, int nx, int wrap_x,
+                       int NB, int C, int Hc, int Wc, int TH, int TW, int ramp_y, int ramp_x, int mode, mdx_stream_t s);
+
 /* ---- LoRA merge (wukong-huahua ldm/modules/attention.py:118-126 applies y = x W^T + (alpha / rank) (x A^T) B^T + b as a side
  * branch of every LoRADense; here the adapter is merged into the weight, in place, in the layout the kernels read):
  *     acc = 0;  for r in 0..R-1 (ascending): acc = fmaf(B[n][r], A[r][k], acc)          (fp32)

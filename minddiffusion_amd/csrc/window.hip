@@ -13,6 +13,9 @@
 //                                   right edge of the canvas into its left one
 //   mdx_window_average_f16          window_average_kernel<false, WEIGHTED>: R == 0, the pairs are the windows, no wrap
 //   mdx_window_average_regions_f16  window_average_kernel<R > 0, WEIGHTED>: every pair's output weighed by its region's mask
+// and a fifth entry brings fp32 NCHW IMAGE tiles (the VAE decoder's outputs on a tiled canvas) back onto the image canvas:
+//   mdx_tile_blend_f32              tile_blend_kernel<4 | 1>: the gather's row order and vector decision, the average's one
+//                                   writer per pixel, min-ramp weights computed in the kernel, [0, 1] conversion fused
 #include "mdx_common.h"
 
 namespace {
@@ -160,6 +163,101 @@ __global__ __launch_bounds__(WN_THREADS) void window_average_kernel(const Averag
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- tile blend
+struct BlendParams {
+    const float* tiles;         // [NB * N][C][h][w], row j * N + k
+    float* out;                 // [NB][C][Hc][Wc]
+    const int* offsets;         // device, [ny + nx]
+    int ny, nx, C, Hc, Wc, h, w, ramp_y, ramp_x, wrap, unit;
+    size_t total;               // NB * C * Hc * Wc
+};
+
+// acc + q * e with the product and the sum rounded separately (never an fma: a numpy float32 restatement is bit-equal)
+__device__ __forceinline__ float blend_add(float acc, float q, float e) {
+#pragma clang fp contract(off)
+    const float t = q * e;
+    return acc + t;
+}
+
+// the bits of torch.clamp((v + 1.0) / 2.0, 0.0, 1.0), NaN kept
+__device__ __forceinline__ float to_unit(float v) {
+#pragma clang fp contract(off)
+    const float u = (v + 1.0f) / 2.0f;
+    return u < 0.0f ? 0.0f : u > 1.0f ? 1.0f : u;
+}
+
+// V consecutive columns of one (b, c, y) canvas row per lane.  The covering tiles are visited in ascending k = iy * nx + ix; the
+// weight of tile-local pixel (yy, xx) is q = (float)(min(yy + 1, h - yy, ramp_y) * min(xx + 1, w - xx, ramp_x)), an integer
+// <= 2^24.  First term: acc = q * e, qsum = q; later terms: acc = acc + q * e (blend_add), qsum += q; the result is acc / qsum,
+// and a pixel with exactly one term takes that term's bits.  V == 4: w, Wc and every x offset are multiples of 4 and both bases
+// are 16-byte aligned (the host decides; a table read is rounded down to a multiple of 4), so the four columns of a lane share
+// their covering tiles and never straddle the seam; their weights differ per column.  Both forms compute the same bits.
+template <int V>
+__global__ __launch_bounds__(WN_THREADS) void tile_blend_kernel(const BlendParams p) {
+    const size_t items = p.total / V;
+    const int wv = p.Wc / V;
+    const size_t N = (size_t)p.ny * p.nx;
+    for (size_t j = (size_t)blockIdx.x * WN_THREADS + threadIdx.x; j < items; j += (size_t)gridDim.x * WN_THREADS) {
+        const int x = (int)(j % wv) * V;
+        size_t r = j / wv;
+        const int y = (int)(r % p.Hc); r /= p.Hc;
+        const int c = (int)(r % p.C);
+        const size_t b = r / p.C;
+        float acc[V] = {}, one[V] = {};
+        float qsum[V] = {};
+        int count = 0;
+        for (int iy = 0; iy < p.ny; ++iy) {
+            const int yy = y - clamp_off(p.offsets[iy], p.Hc - p.h);
+            if (yy < 0 || yy >= p.h) continue;
+            const int qy = min(min(yy + 1, p.h - yy), p.ramp_y);
+            for (int ix = 0; ix < p.nx; ++ix) {
+                int ox = clamp_off(p.offsets[p.ny + ix], p.wrap ? p.Wc - 1 : p.Wc - p.w);
+                if constexpr (V == 4) ox &= ~3;
+                int xx = x - ox;
+                if (p.wrap && xx < 0) xx += p.Wc;
+                if (xx < 0 || xx >= p.w) continue;
+                const float* src = p.tiles + (((b * N + (size_t)(iy * p.nx + ix)) * p.C + c) * p.h + yy) * (size_t)p.w + xx;
+                float e[V];
+                if constexpr (V == 4) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) e[i] = v[i];
+                } else {
+                    e[0] = *src;
+                }
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float q = (float)(qy * min(min(xx + i + 1, p.w - xx - i), p.ramp_x));
+                    if (count == 0) {
+                        acc[i] = q * e[i];
+                        qsum[i] = q;
+                        one[i] = e[i];
+                    } else {
+                        acc[i] = blend_add(acc[i], q, e[i]);
+                        qsum[i] += q;
+                    }
+                }
+                ++count;
+            }
+        }
+        // count == 0 cannot happen for a table the host accepted (every pixel is covered); such a pixel would be written 0 / 0
+        float o[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const float v = count == 1 ? one[i] : acc[i] / qsum[i];
+            o[i] = p.unit ? to_unit(v) : v;
+        }
+        if constexpr (V == 4) {
+            f32x4 v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = o[i];
+            *reinterpret_cast<f32x4*>(p.out + j * 4) = v;
+        } else {
+            p.out[j] = o[0];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------- the host
 // One axis of the host's copy of the offset table, every offset already known to lie inside the canvas (check_grid):
 // ascending from 0 to L - w in steps of 1 .. w, so every pixel is covered.
@@ -292,6 +390,33 @@ int average_launch(const char* fn, const void* windows, void* out, const float* 
     return MDX_OK;
 }
 
+// The blend's host body: the gather's vector decision on the image canvas, every x offset of the table counted.
+int blend_launch(const char* fn, const float* tiles, float* out, const int* offsets, const int* offsets_host, int ny, int nx,
+                 int wrap, int NB, int C, int Hc, int Wc, int h, int w, int ramp_y, int ramp_x, int mode, mdx_stream_t s) {
+    MDX_REQUIRE(tiles && out && offsets && offsets_host, "%s: null pointer", fn);
+    MDX_REQUIRE(wrap == 0 || wrap == 1, "%s: wrap_x must be 0 or 1, got %d", fn, wrap);
+    if (const int rc = check_grid(fn, offsets_host, ny, nx, wrap, NB, C, Hc, Wc, h, w)) return rc;
+    MDX_REQUIRE(ramp_y >= 1 && ramp_x >= 1 && ramp_y <= 4096 && ramp_x <= 4096,
+                "%s: the ramps must be in [1, 4096] (their products stay exact in fp32), got %d x %d", fn, ramp_y, ramp_x);
+    MDX_REQUIRE(mode == MDX_TILE_RAW || mode == MDX_TILE_UNIT, "%s: unknown mode %d", fn, mode);
+    const size_t N = (size_t)ny * nx;
+    MDX_REQUIRE(!overlaps(out, (size_t)NB * C * Hc * Wc * sizeof(float), tiles, (size_t)NB * N * C * h * w * sizeof(float)),
+                "%s: out overlaps tiles", fn);
+    BlendParams p;
+    p.tiles = tiles; p.out = out; p.offsets = offsets;
+    p.ny = ny; p.nx = nx; p.C = C; p.Hc = Hc; p.Wc = Wc; p.h = h; p.w = w; p.ramp_y = ramp_y; p.ramp_x = ramp_x; p.wrap = wrap;
+    p.unit = mode == MDX_TILE_UNIT;
+    p.total = (size_t)NB * C * Hc * Wc;
+    bool vec = w % 4 == 0 && Wc % 4 == 0 && aligned16(tiles) && aligned16(out);
+    for (int i = 0; i < nx && vec; ++i) vec = offsets_host[ny + i] % 4 == 0;
+    if (vec)
+        hipLaunchKernelGGL(tile_blend_kernel<4>, dim3(wn_blocks(p.total / 4)), dim3(WN_THREADS), 0, (hipStream_t)s, p);
+    else
+        hipLaunchKernelGGL(tile_blend_kernel<1>, dim3(wn_blocks(p.total)), dim3(WN_THREADS), 0, (hipStream_t)s, p);
+    MDX_LAUNCH_CHECK(fn);
+    return MDX_OK;
+}
+
 }  // namespace
 
 extern "C" int mdx_window_gather_f32(const float* canvas, float* out, const int* offsets, const int* offsets_host, int ny, int nx,
@@ -324,4 +449,11 @@ extern "C" int mdx_window_average_regions_f16(const void* windows, void* out, co
     return average_launch("mdx_window_average_regions_f16", windows, out, weights, n_weights, offsets, offsets_host, ny, nx,
                           wrap_x, pair_window_host, pair_region, pair_region_host, pair_first, pair_first_host, P, masks, R, NB,
                           C, ld, Hc, Wc, h, w, s);
+}
+
+extern "C" int mdx_tile_blend_f32(const float* tiles, float* out, const int* offsets, const int* offsets_host, int ny, int nx,
+                                  int wrap_x, int NB, int C, int Hc, int Wc, int TH, int TW, int ramp_y, int ramp_x, int mode,
+                                  mdx_stream_t s) {
+    return blend_launch("mdx_tile_blend_f32", tiles, out, offsets, offsets_host, ny, nx, wrap_x, NB, C, Hc, Wc, TH, TW, ramp_y,
+                        ramp_x, mode, s);
 }

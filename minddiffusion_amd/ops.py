@@ -1420,6 +1420,40 @@ def window_average_regions(windows, grid, C, plan=None, out=None, weights=None):
     return out
 
 
+# Tiled VAE (include/mdx.h: mdx_tile_blend_f32, csrc/window.hip).
+TILE_MODES = {"raw": 0, "unit": 1}          # MDX_TILE_RAW / MDX_TILE_UNIT
+
+
+def ramp_weights(tile_hw, ramp_hw):
+    """[h, w] fp32 min-ramp: min(y + 1, h - y, ramp_y) * min(x + 1, w - x, ramp_x) -- the weights mdx_tile_blend_f32 computes
+    in its kernel, as a table for window_average(weights=) on the encode side of a tiled VAE."""
+    (h, w), (ry, rx) = (int(v) for v in tile_hw), (int(v) for v in ramp_hw)
+    if h < 1 or w < 1 or ry < 1 or rx < 1:
+        raise _lib.MdxError(f"ramp_weights: tile {(h, w)} and ramps {(ry, rx)} must be positive")
+    y, x = np.arange(h), np.arange(w)
+    qy, qx = np.minimum(np.minimum(y + 1, h - y), ry), np.minimum(np.minimum(x + 1, w - x), rx)
+    return torch.from_numpy((qy[:, None] * qx[None, :]).astype(np.float32))
+
+
+def tile_blend(tiles, grid, ramp, out=None, mode="raw"):
+    """Image tiles fp32 [NB * N, C, TH, TW] in window_gather's row order blended onto the canvas [NB, C, Hc, Wc] of `grid` -- a
+    WindowGrid on the IMAGE canvas, in output pixels, wrapped or not -- with min-ramp weights; ramp: an int or (ramp_y, ramp_x),
+    each in [1, 4096].  mode "raw": the blend; "unit": clamp((blend + 1) / 2, 0, 1) in the same launch.  include/mdx.h states
+    the arithmetic.  One launch."""
+    _chk(tiles, f32, "tiles"); _chk(out, f32, "out")
+    if mode not in TILE_MODES:
+        raise _lib.MdxError(f"tile_blend: mode must be one of {sorted(TILE_MODES)}, got {mode!r}")
+    ry, rx = (ramp, ramp) if np.ndim(ramp) == 0 else ramp
+    if tiles.dim() != 4 or tiles.shape[0] % grid.N or tuple(tiles.shape[2:]) != (grid.h, grid.w):
+        raise _lib.MdxError(f"tiles: shape {tuple(tiles.shape)}, expected [NB * {grid.N}, C, {grid.h}, {grid.w}]")
+    NB, C = int(tiles.shape[0]) // grid.N, int(tiles.shape[1])
+    out = _window_out(out, (NB, C, grid.Hc, grid.Wc), tiles)
+    _lib.check(_lib.load().mdx_tile_blend_f32(_ptr(tiles), _ptr(out), _ptr(grid.on(tiles.device)), grid._host_ptr(), grid.ny,
+                                              grid.nx, int(grid.wrap_x), NB, C, grid.Hc, grid.Wc, grid.h, grid.w, int(ry), int(rx),
+                                              TILE_MODES[mode], _stream()), "mdx_tile_blend_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Per-sample seeded noise (include/mdx.h: mdx_philox_u32 / mdx_randn_f32, csrc/rng.hip).  `stream` says what a draw is for,
 # `draw` which one it is; these are the streams the samplers and the pipeline use (a stream is < 2^31: the top bit selects

@@ -189,7 +189,12 @@ class DiffusionPipeline:
     def _decode_latent(self, samples):
         """model.decode_first_stage; on a wrap_x pipeline with seam_pad > 0 the latent is padded circularly by seam_cols columns
         per side first and the padded image columns are cropped, so the decoder's 3 x 3 convs see the other edge of the panorama
-        where they would see zeros.  (GroupNorm and the mid attention are global: this is not exact periodicity.)"""
+        where they would see zeros.  (GroupNorm and the mid attention are global: this is not exact periodicity.)  With VAE
+        tiling on (enable_vae_tiling) the VAE takes the pipeline's wrap_x instead and nothing is padded: the seam is a tile
+        boundary like any other."""
+        vae = self._tiled_vae()
+        if vae is not None:
+            return vae.decode(1. / self.model.scale_factor * samples, wrap_x=bool(getattr(self.model, "wrap_x", False)))
         pad = min(int(self.seam_cols), int(samples.shape[-1]))
         if pad <= 0:
             return self.model.decode_first_stage(samples)             # txt2img.py:265-266
@@ -199,8 +204,32 @@ class DiffusionPipeline:
         return x[..., cut:int(x.shape[-1]) - cut].contiguous()
 
     def _decoded(self, samples):
+        vae = self._tiled_vae()
+        if vae is not None:                                           # (the [0, 1] conversion inside the blend launch)
+            return vae.decode_unit(1. / self.model.scale_factor * samples, wrap_x=bool(getattr(self.model, "wrap_x", False)))
         x = self._decode_latent(samples)
         return torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)
+
+    # ---- tiled VAE (AutoencoderKL.enable_tiling): the setting lives on the VAE, which windowed() and hires() pipelines share
+    def _tiled_vae(self):
+        vae = getattr(self.model, "first_stage_model", None)
+        return vae if getattr(vae, "tiling", None) is not None else None
+
+    def _vae(self, what):
+        vae = getattr(self.model, "first_stage_model", None)
+        if not hasattr(vae, "enable_tiling"):
+            raise MdxError(f"DiffusionPipeline.{what}: no VAE with tiling attached (model.first_stage_model)")
+        return vae
+
+    def enable_vae_tiling(self, tile=64, overlap=16, max_tile_batch=8):
+        """Decode and encode canvases larger than `tile` latent pixels tile by tile (AutoencoderKL.enable_tiling); on a wrap_x
+        pipeline the decode wraps its tiles around the seam and seam_pad is not used."""
+        self._vae("enable_vae_tiling").enable_tiling(tile=tile, overlap=overlap, max_tile_batch=max_tile_batch)
+        return self
+
+    def disable_vae_tiling(self):
+        self._vae("disable_vae_tiling").disable_tiling()
+        return self
 
     # ---- regional prompts (ldm/models/diffusion/windowed.py): a mask over the canvas and a prompt each
     @staticmethod
