@@ -1005,6 +1005,36 @@ typedef struct mdx_lora_merge_desc {
 } mdx_lora_merge_desc;
 int mdx_lora_merge_f16(const mdx_lora_merge_desc* d, mdx_stream_t s);
 
+/* ---- ControlNet residual add (Zhang et al. 2023, cldm.py ControlledUnetModel.forward: `h += control.pop()` on the middle
+ * block's output and on every skip connection): up to MDX_CONTROL_MAX_SEGS residual tensors added into the UNet's activations,
+ * in place, by ONE launch.  Segment s is {dst[s], src[s], elems_per_row[s]}: dst[s] fp16 [nb][elems_per_row[s]] (rows dense),
+ * src[s] fp16 [>= 1 + max src_row][elems_per_row[s]].  For destination row r of segment s and element e, with q = src_row[r]:
+ *     q < 0:   dst[s][r][e] is neither read nor written;
+ *     else:    dst[s][r][e] = fp16_rne(fmaf(scale[s * nb + r], float(src[s][q][e]), float(dst[s][r][e])))      (fp32)
+ * -- one fused multiply-add in fp32 and one explicit round-to-nearest-even to fp16.  src (n_seg device pointers), src_row
+ * (int32 [nb]) and scale (fp32 [n_seg][nb]) are DEVICE tables read when the kernel runs: a captured graph serves any scales,
+ * any row mapping and any source buffers without being captured again.  The caller guarantees src_row[r] < the rows of every
+ * source.  No atomics; the same inputs give the same bits.
+ * Refused, before any launch (MDX_E_INVALID): a null descriptor, n_seg outside [1, 16], nb < 1, a null or misaligned table
+ * (src 8-byte, src_row / scale 4-byte), a null dst, a dst that is not 16-byte aligned, an elems_per_row that is not a positive
+ * multiple of 8.  The source pointers live on the device: their 16-byte alignment is the table writer's to check
+ * (ops.ControlAdd.set_sources).  Only the dst rows with src_row >= 0 are written. */
+#define MDX_CONTROL_MAX_SEGS 16
+typedef struct mdx_control_add_desc {
+    int n_seg;
+    int nb;                                     /* destination batch rows */
+    void* dst[MDX_CONTROL_MAX_SEGS];
+    int elems_per_row[MDX_CONTROL_MAX_SEGS];    /* halves per batch row (H * W * C of the tensor) */
+    const void* const* src;                     /* DEVICE: n_seg pointers */
+    const int* src_row;                         /* DEVICE: [nb] */
+    const float* scale;                         /* DEVICE: [n_seg][nb] */
+} mdx_control_add_desc;
+int mdx_control_add_f16(const mdx_control_add_desc* d, mdx_stream_t s);
+
+/* x <- silu(x) in place on n fp16 values (n a positive multiple of 8, x 16-byte aligned), fp32 arithmetic inside: the
+ * activation between the convs of the ControlNet hint block (seven launches per hint, once per hint image). */
+int mdx_silu_f16(void* x, size_t n, mdx_stream_t s);
+
 /* ---- probes used by tests to pin hardware layout assumptions (not on the hot path) */
 int mdx_probe_mfma_32x32x16_f16(const void* a, const void* b, float* c, mdx_stream_t s);
 /* Same for v_mfma_f32_16x16x32_f16 (the conv8p core): a, b = 64 lanes x 8 halves, c = 64 lanes x 4 floats. */

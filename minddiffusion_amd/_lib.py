@@ -76,7 +76,18 @@ class LoraMergeDesc(ctypes.Structure):
     ]
 
 
-EPI_NONE, EPI_GEGLU, EPI_GELU, EPI_QUICKGELU, EPI_PRELU = 0, 1, 2, 3, 4
+CONTROL_MAX_SEGS = 16
+
+
+class ControlAddDesc(ctypes.Structure):
+    """struct mdx_control_add_desc (include/mdx.h)."""
+    _fields_ = [
+        ("n_seg", c_int), ("nb", c_int), ("dst", c_void_p * CONTROL_MAX_SEGS), ("elems_per_row", c_int * CONTROL_MAX_SEGS),
+        ("src", c_void_p), ("src_row", c_void_p), ("scale", c_void_p),
+    ]
+
+
+EPI_NONE, EPI_GEGLU,EPI_GELU, EPI_QUICKGELU, EPI_PRELU = 0, 1, 2, 3, 4
 OUT_ROWMAJOR, OUT_TRANSPOSED, OUT_D2S2 = 0, 1, 2
 LORA_ROWMAJOR, LORA_TILED, LORA_FRAG = 0, 1, 2
 
@@ -128,6 +139,8 @@ SIGNATURES = {
     "mdx_st_tail_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mdx_st_tail_stream_bytes": (c_size_t, [c_int]),
     "mdx_lora_merge_f16": (c_int, [ctypes.POINTER(LoraMergeDesc), c_void_p]),
+    "mdx_control_add_f16": (c_int, [ctypes.POINTER(ControlAddDesc), c_void_p]),
+    "mdx_silu_f16": (c_int, [c_void_p, c_size_t, c_void_p]),
     "mdx_timestep_embedding_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "mdx_dense_small_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),

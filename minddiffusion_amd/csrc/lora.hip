@@ -45,26 +45,8 @@ __device__ __forceinline__ size_t chunk_offset(const LoraParams& p, int g, int c
     return (size_t)g * p.ld + (size_t)c * 8;
 }
 
-// fp32 -> fp16, round to nearest even, on the bit pattern (F. Giesen's public-domain float_to_half_fast3).  Used for the folded
-// weights instead of a cast: the compiler fuses `(f16)(fp32 multiply of an fp16 and an fp32 value)` into one mixed-precision
-// multiply that rounds ONCE to fp16, while ops.fold_layernorm's value is rounded twice (below).
-__device__ __forceinline__ f16 f16_rne_from_f32_bits(float f) {
-    unsigned x = __float_as_uint(f);
-    const unsigned sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    unsigned h;
-    if (x >= 0x47800000u) {                    // >= 65536, inf, nan
-        h = x > 0x7f800000u ? 0x7e00u : 0x7c00u;
-    } else if (x < 0x38800000u) {              // below 2^-14: an fp16 subnormal or zero; the fp32 add does the rounding
-        h = __float_as_uint(__uint_as_float(x) + 0.5f) - 0x3f000000u;
-    } else {
-        const unsigned odd = (x >> 13) & 1u;
-        x += 0xc8000fffu;                      // exponent re-bias (15 - 127) << 23, plus 0xfff of rounding bias
-        h = (x + odd) >> 13;
-    }
-    const unsigned short bits = (unsigned short)(h | sign);
-    return __builtin_bit_cast(f16, bits);
-}
+// (the folded weights are rounded with f16_rne_from_f32_bits of mdx_common.h instead of a cast: ops.fold_layernorm's value is
+// rounded twice, below)
 
 // RREG: rows of A a lane keeps in registers (R <= RREG), or -1 = any R <= 64 with A read inside the row loop
 template <int RREG>

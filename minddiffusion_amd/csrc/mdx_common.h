@@ -124,6 +124,28 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
     return x * sigmoid_fast(2.0f * u);
 }
 
+// fp32 -> fp16, round to nearest even, on the bit pattern (F. Giesen's public-domain float_to_half_fast3).  Used instead of a
+// cast where the rounding step must stand on its own: the compiler fuses `(f16)(fp32 arithmetic on an fp16 and an fp32 value)` into
+// one mixed-precision instruction that rounds ONCE to fp16, while the value being restated (ops.fold_layernorm in lora.hip, the
+// fp32 sum of control.hip) is an fp32 result rounded to fp16 in a second step.
+__device__ __forceinline__ f16 f16_rne_from_f32_bits(float f) {
+    unsigned x = __float_as_uint(f);
+    const unsigned sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    unsigned h;
+    if (x >= 0x47800000u) {                    // >= 65536, inf, nan
+        h = x > 0x7f800000u ? 0x7e00u : 0x7c00u;
+    } else if (x < 0x38800000u) {              // below 2^-14: an fp16 subnormal or zero; the fp32 add does the rounding
+        h = __float_as_uint(__uint_as_float(x) + 0.5f) - 0x3f000000u;
+    } else {
+        const unsigned odd = (x >> 13) & 1u;
+        x += 0xc8000fffu;                      // exponent re-bias (15 - 127) << 23, plus 0xfff of rounding bias
+        h = (x + odd) >> 13;
+    }
+    const unsigned short bits = (unsigned short)(h | sign);
+    return __builtin_bit_cast(f16, bits);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

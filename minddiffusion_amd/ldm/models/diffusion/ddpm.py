@@ -142,14 +142,19 @@ class LatentDiffusion:
         c_concat, c_crossattn = self._split_cond(cond, c_concat, c_crossattn)
         return self.model(x_noisy, t, c_concat=c_concat, c_crossattn=c_crossattn)
 
-    def apply_model_nhwc(self, x_noisy, t, cond, temb=None, cfg_dup=False):
+    def apply_model_nhwc(self, x_noisy, t, cond, temb=None, cfg_dup=False, control=None):
         """Fast path used by the samplers: returns the UNet's static NHWC fp16 eps buffer [B, H*W, 8]
         (valid until the next call) so the fused sampler-step kernel can consume it without a layout pass.
         `x_noisy` already carries the c_concat channels for hybrid / concat conditioning (the sampler writes them once);
         `cond` is the text context ('crossattn' / 'hybrid'), the class labels ('adm'), or ignored (None / 'concat').
         temb: the row of time_embedding_table() that belongs to `t` (optional).  cfg_dup: the batch is [uncond ; cond] of the same
-        x_noisy and t (UNetModel.forward_nhwc)."""
+        x_noisy and t (UNetModel.forward_nhwc).  control: ControlNet residuals for this evaluation (openaimodel.Control, made by
+        ControlledDiffusion); 'crossattn' models only."""
         key = self.model.conditioning_key
+        if control is not None:
+            if key != "crossattn":
+                raise MdxError(f"apply_model_nhwc: control= needs conditioning_key 'crossattn', got {key!r}")
+            return self.unet.forward_nhwc(x_noisy, t, cond, temb=temb, control=control)
         if key == "adm":
             return self.unet.forward_nhwc(x_noisy, t, None, y=_first(cond))
         if key is None or key == "concat":

@@ -250,6 +250,8 @@ class SamplingSession:
             raise ValueError(f"sampler must be one of {SAMPLERS} in a session, got {sampler!r}")
         if D.world()[1] > 1:
             raise MdxError("SamplingSession: runs on a single rank (the sharded form is not built)")
+        if getattr(model, "is_controlled", False):
+            raise MdxError("SamplingSession: a ControlledDiffusion model is not served in sessions (a slot has no hint of its own)")
         key = getattr(getattr(model, "model", None), "conditioning_key", "crossattn")
         unet = getattr(model, "unet", None)
         if key != "crossattn" or getattr(unet, "num_classes", None) is not None or not hasattr(model, "time_embedding_table"):

@@ -74,6 +74,8 @@ class WindowedDiffusion:
     def __init__(self, model, window=(64, 64), stride=None, weights=None, max_unet_batch=16, wrap_x=False):
         if isinstance(model, WindowedDiffusion):
             raise MdxError("WindowedDiffusion: the model is already windowed")
+        if getattr(model, "is_controlled", False):
+            raise MdxError("WindowedDiffusion: a ControlledDiffusion model is not windowed (the hint has no per-window form)")
         key = getattr(getattr(model, "model", None), "conditioning_key", "crossattn")
         unet = getattr(model, "unet", None)
         if key == "adm" or getattr(unet, "num_classes", None) is not None:

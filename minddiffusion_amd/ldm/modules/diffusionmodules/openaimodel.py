@@ -42,6 +42,17 @@ def is_lora_key(name):
     return _LORA_KEY.match(name) is not None
 
 
+class Control:
+    """What UNetModel.forward_nhwc(control=) carries (ControlledUnetModel.forward of the ControlNet paper's cldm.py): the
+    residual tensors of one ControlNet evaluation -- one per input block, then the middle block's, as
+    ControlNet.forward_residuals returns them: fp16 [b, H * W, C] NHWC -- and the two tables of ops.ControlAdd: rows[r] = the
+    residual row added to UNet batch row r (-1: that row runs without control) and scale, fp32 [n, B] (or what broadcasts to
+    it): residual i reaches row r multiplied by scale[i][r]."""
+
+    def __init__(self, sources, rows, scale):
+        self.sources, self.rows, self.scale = list(sources), [int(r) for r in rows], scale
+
+
 class UNetModel:
     def __init__(self, image_size=32, in_channels=4, model_channels=320, out_channels=4, num_res_blocks=2,
                  attention_resolutions=(4, 2, 1), dropout=0.0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2,
@@ -236,6 +247,12 @@ class UNetModel:
             elif kind == "up" and self.conv_resample:
                 s[pre + "conv.conv.weight"] = (layer[1], layer[1], 3, 3)
                 s[pre + "conv.conv.bias"] = (layer[1],)
+        self._head_shapes(s)
+        return s
+
+    def _head_shapes(self, s):
+        """What the network owns behind its blocks: `out` (and `id_predictor`).  ControlNet has its zero convs here."""
+        mc = self.model_channels
         s["out.0.gamma"] = (mc,)
         s["out.0.beta"] = (mc,)
         s["out.2.conv.weight"] = (self.out_channels, mc, 3, 3)
@@ -245,7 +262,6 @@ class UNetModel:
             s["id_predictor.0.beta"] = (mc,)
             s["id_predictor.1.conv.weight"] = (self.n_embed, mc, 1, 1)
             s["id_predictor.1.conv.bias"] = (self.n_embed,)
-        return s
 
     def _lora_targets(self):
         """(reference name of the Dense, out, in) of every LoRA target, in structure order."""
@@ -377,11 +393,7 @@ class UNetModel:
         w["emb.w"] = torch.cat(emb_w, 0).contiguous()
         w["emb.b"] = torch.cat(emb_b, 0).contiguous()
         self._emb_total = off
-        # with n_embed the reference builds `out` as well (openaimodel.py:520-531); only id_predictor runs
-        norm, conv = ("out.0", "out.2.conv") if self.n_embed is None else ("id_predictor.0", "id_predictor.1.conv")
-        w["out.g"], w["out.b"] = L.vec(norm + ".gamma"), L.vec(norm + ".beta")
-        w["out.w"] = L.conv(conv + ".weight", cout_pad=self.cout_pad)
-        w["out.cb"] = L.vec(conv + ".bias", pad=self.cout_pad)
+        unused = self._load_head(L)
         self._frag_w = {}
         self._geglu80 = {}
         self._ff_proj = {}
@@ -393,12 +405,22 @@ class UNetModel:
         if self.enable_lora:
             for name, _, _ in self._lora_targets():
                 self._lora_base[name] = L.own(name + ".weight", f32)
-        self.w = L.finish(shapes, unused=() if self.n_embed is None else [k for k in shapes if k.startswith("out.")])
+        self.w = L.finish(shapes, unused=unused)
         if self.enable_lora:
             self._lora_sites = self._find_lora_sites()
             if lora_params:
                 self._set_lora(lora_params)
         return self
+
+    def _load_head(self, L):
+        """Pack what _head_shapes names; returns the names the class owns but never runs."""
+        w = L.w
+        # with n_embed the reference builds `out` as well (openaimodel.py:520-531); only id_predictor runs
+        norm, conv = ("out.0", "out.2.conv") if self.n_embed is None else ("id_predictor.0", "id_predictor.1.conv")
+        w["out.g"], w["out.b"] = L.vec(norm + ".gamma"), L.vec(norm + ".beta")
+        w["out.w"] = L.conv(conv + ".weight", cout_pad=self.cout_pad)
+        w["out.cb"] = L.vec(conv + ".bias", pad=self.cout_pad)
+        return () if self.n_embed is None else ["out.0.gamma", "out.0.beta", "out.2.conv.weight", "out.2.conv.bias"]
 
     def weight_bytes(self):
         """Bytes of device memory the loaded weights hold; with enable_lora this includes the fp32 copies of the LoRA target
@@ -524,11 +546,16 @@ class UNetModel:
     class _Plan:
         pass
 
-    def _plan(self, B, H, W, _selfctx=False):
+    def _planner(self, B, H, W, fuse_head, selfctx, control):
+        return _UNetPlanner(self, B, H, W, fuse_head, selfctx, control)
+
+    def _plan(self, B, H, W, _selfctx=False, control=False):
         # _selfctx: the `context=None` form of construct() (DiffusionWrapper keys None / 'concat' / 'adm', WK ddpm.py:361-374):
         # attn2 attends to its own normalised input (attention.py:133 `context = default(context, x)`), so its to_k / to_v run per
-        # step on LayerNorm(tokens) instead of once on the text context; plans of the two forms are kept side by side
-        key = (B, H, W, "selfctx") if _selfctx else (B, H, W)
+        # step on LayerNorm(tokens) instead of once on the text context; plans of the two forms are kept side by side.
+        # control: the plan of forward_nhwc(control=) -- one ops.ControlAdd launch behind the middle block; a plan of its own,
+        # so the plain plan and everything it launches are what they are without ControlNet
+        key = (B, H, W, "selfctx") if _selfctx else (B, H, W, "control") if control else (B, H, W)
         if key in self._plans:
             return self._plans[key]
         if self.w is None:
@@ -537,11 +564,11 @@ class UNetModel:
             if (H >> lvl) % 2 or (W >> lvl) % 2:
                 raise MdxError(f"UNetModel: latent {H}x{W} is not divisible by 2^{len(self.channel_mult) - 1}")
         try:
-            P = _UNetPlanner(self, B, H, W, True, _selfctx).build()
+            P = self._planner(B, H, W, True, _selfctx, control).build()
         except _HeadNotWired:
             # a fused head whose input tensor's producer cannot emit column statistics in its final launch form: plan again
             # with the unfused GroupNorm / proj_in / qkv launches (plans are built once per shape)
-            P = _UNetPlanner(self, B, H, W, False, _selfctx).build()
+            P = self._planner(B, H, W, False, _selfctx, control).build()
         self._plans[key] = P
         return P
 
@@ -591,13 +618,21 @@ class UNetModel:
         e2 = ops.dense_small(e1, w["te2.w"], w["te2.b"])
         return ops.dense_small(e2, w["emb.w"], w["emb.b"], act_in=True)
 
-    def forward_nhwc(self, x, timesteps, context=None, temb=None, y=None, cfg_dup=False):
+    def forward_nhwc(self, x, timesteps, context=None, temb=None, y=None, cfg_dup=False, control=None):
         """Run the UNet; returns the plan's static NHWC fp16 eps buffer [B, H*W, 8] (first 4 channels valid).
         The buffer is overwritten by the next call.  temb: optional row(s) of time_embedding_table() for `timesteps`
         ([emb_total] or [B, emb_total]); the time-embedding launches are then skipped.  y: [B] class labels of a
         class-conditional UNet (num_classes).  cfg_dup: the caller states that the two halves of the batch carry the SAME x and
         timesteps and differ only in `context` (classifier-free guidance, plms.py:192-195 `x_in = cat([x] * 2)`): the launches in
-        front of the first cross-attention may then run on one half (_dup_body)."""
+        front of the first cross-attention may then run on one half (_dup_body).  control: a Control -- the residuals of a
+        ControlNet evaluation, added to the skip connections and the middle block's output by one launch (the plan keyed
+        (B, H, W, "control")); such a call needs a text context, takes no y and makes no use of cfg_dup."""
+        if control is not None:
+            if context is None or y is not None:
+                raise MdxError("UNetModel: control= needs a text context and takes no class labels")
+            if not isinstance(control, Control):
+                raise MdxError("UNetModel: control= takes an openaimodel.Control")
+            cfg_dup = False
         if (y is not None) != (self.num_classes is not None):      # openaimodel.py:545-547
             raise MdxError("UNetModel: must specify y if and only if the model is class-conditional")
         if y is not None and temb is not None:
@@ -620,8 +655,18 @@ class UNetModel:
                                f"context_dim == transformer width; context_dim={self.context_dim}, widths {bad}")
             P = self._plan(B, H, W, _selfctx=True)
         else:
-            P = self._plan(B, H, W)
+            P = self._plan(B, H, W, control=control is not None)
             self._ensure_context(P, context)
+        if control is not None:         # device tables the captured launch reads: nothing here touches the graph
+            P.control.set_sources(control.sources, control.rows)
+            P.control.set_scale(control.scale)
+        self._evaluate(P, x, timesteps, temb, y, cfg_dup and context is not None and y is None)
+        return P.eps_nhwc
+
+    def _evaluate(self, P, x, timesteps, temb=None, y=None, cfg_dup=False):
+        """One evaluation of plan P: x and the timestep rows into the plan's static inputs, then the captured graph (or the op
+        list).  The caller has made the plan's context current."""
+        B = P.B
         P.x_static.copy_(x)
         if temb is not None:
             if temb.shape[-1] != self._emb_total or temb.dtype != f32:
@@ -639,7 +684,7 @@ class UNetModel:
                 P.y_static.copy_(yy)
             for op in P.main[:P.temb_ops]:
                 op()
-        dup = self._dup_body(P) if (cfg_dup and context is not None and y is None) else None
+        dup = self._dup_body(P) if cfg_dup else None
         if dup is not None and ops.get_option("unet_cfg_dup_check"):
             hb = B // 2
             same = torch.equal(P.x_static[:hb], P.x_static[hb:]) and torch.equal(P.emb_all[:hb], P.emb_all[hb:])
@@ -651,17 +696,16 @@ class UNetModel:
                     self._capture(P, dup)
                 if P.dup_graph is not None:
                     P.dup_graph.replay()
-                    return P.eps_nhwc
+                    return
             if P.graph is None:
                 self._capture(P)
             if P.graph is not None:
                 P.graph.replay()
-                return P.eps_nhwc
+                return
         body = dup if dup is not None else P.main[P.temb_ops:]
         for op in body:
             op()
         self.last_launch_count = P.temb_ops + len(body)
-        return P.eps_nhwc
 
     def _dup_body(self, P):
         """The op list of one evaluation whose batch is [uncond ; cond] of the SAME latents (classifier-free guidance, plms.py:192-195):
@@ -734,10 +778,10 @@ class _HeadNotWired(Exception):
 class _UNetPlanner(PlanBuilder):
     """One (B, H, W) plan of a UNetModel: walks the block structure once and emits the op list (planner.PlanBuilder)."""
 
-    def __init__(self, net, B, H, W, fuse_head, selfctx):
+    def __init__(self, net, B, H, W, fuse_head, selfctx, control=False):
         super().__init__(net.device, B, track_producers=True)
         self.net, self.w, self.H, self.W = net, net.w, H, W
-        self.fuse_head, self.selfctx = fuse_head, selfctx
+        self.fuse_head, self.selfctx, self.control = fuse_head, selfctx, control
         self.TC = net.max_context_len
         # keys the roofline metadata counts per query: one CLIP window at the default capacity, else the plan's capacity
         self.ctx_flops = 77 if self.TC == 80 else self.TC
@@ -829,6 +873,8 @@ class _UNetPlanner(PlanBuilder):
             if not self.held(cur):
                 self.release(cur)
             cur = new
+        if self.control:
+            self.control_add(cur)
         for i, blk in enumerate(net.output_blocks):
             skip, sh, sw = self.hs.pop()
             assert (sh, sw) == (h, wd)
@@ -845,6 +891,21 @@ class _UNetPlanner(PlanBuilder):
         self.P.eps_nhwc = torch.empty((B, h * wd, net.cout_pad), dtype=f16, device=self.dev)
         self.gemm(a=a, w=w["out.w"], N=net.cout_pad, B=B, H=h, W=wd, c1=mc, out=self.P.eps_nhwc, out_ld=net.cout_pad,
                   bias=w["out.cb"], ksize=3 if net.n_embed is None else 1)
+
+    def control_add(self, mid):
+        """The control plan's one extra op, behind the middle block (cldm.py ControlledUnetModel.forward): the ControlNet's
+        residuals are added IN PLACE to every skip connection still held and to the middle block's output `mid`, by one
+        ops.ControlAdd launch whose sources, row map and scales are device tables (UNetModel.forward_nhwc fills them per call).
+        The column statistics a producer's epilogue wrote for these tensors describe them BEFORE the add: the tensors leave
+        `producer`, so every GroupNorm that reads them from here on computes its own statistics (gn() looks the producer up
+        when it is emitted).  Nothing crosses the add the other way either: a GroupNorm takes over its producer's split-K
+        reduce (fuse_splitk_into_groupnorm) only with x2 None and the producer's launch right in front of it, and the
+        GroupNorms behind the add read [cur | skip] pairs."""
+        dsts = [s_[0] for s_ in self.hs] + [mid]
+        ca = self.P.control = ops.ControlAdd(dsts)
+        self.emit(ca.run, "small", 0, 1, f"control_add segments={len(dsts)} halves/row={sum(t.numel() for t in dsts) // self.B}")
+        for t in dsts:
+            self.producer.pop(t.data_ptr(), None)
 
     def layer_op(self, pre, layer, cur, skip, h, wd):
         net, w, B = self.net, self.w, self.B

@@ -158,6 +158,17 @@ def load_latent_diffusion(path):
     return pick(UNET_PREFIX), pick(VAE_PREFIX), pick(TEXT_PREFIX)
 
 
+CONTROL_PREFIX = "control_model."      # the ControlNet paper's cldm.py: ControlLDM.control_model (UNPINNED: no reference tree has one)
+
+
+def load_controlnet_checkpoint(path):
+    """A ControlNet checkpoint -> the dict ControlNet.load_state_dict takes: the `control_model.` parameters, prefix removed;
+    a checkpoint saved from the bare network (no such prefix anywhere) is returned as it is."""
+    allp = load_checkpoint(path)
+    out = {k[len(CONTROL_PREFIX):]: v for k, v in allp.items() if k.startswith(CONTROL_PREFIX)}
+    return out or allp
+
+
 def load_lora_checkpoint(path):
     """A LoRA adapter checkpoint (wukong-huahua/txt2img.py:222-225 `ms.load_checkpoint(lora_ckpt_path)`) -> the dict
     UNetModel.load_lora_state_dict takes: only the UNet's `lora_a` / `lora_b` parameters, "model.diffusion_model." removed.

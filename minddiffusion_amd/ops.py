@@ -3,6 +3,7 @@ the current HIP stream; all arithmetic happens in libmdx.so.  No CPU fallbacks."
 import ctypes
 import math
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -1782,3 +1783,107 @@ def lora_merge(base, dst, layout, A=None, B=None, scale=1.0, gamma=None, beta=No
     d.piece_stride, d.piece_offset = int(piece_stride), int(piece_offset)
     _lib.check(_lib.load().mdx_lora_merge_f16(ctypes.byref(d), _stream()), "mdx_lora_merge_f16")
     return dst
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ControlNet (include/mdx.h: mdx_control_add_f16, mdx_silu_f16)
+CONTROL_MAX_SEGS = _lib.CONTROL_MAX_SEGS
+
+
+def silu_(x):
+    """x <- silu(x) in place (mdx_silu_f16): fp16, contiguous, a multiple of 8 values."""
+    _chk(x, f16, "x")
+    _lib.check(_lib.load().mdx_silu_f16(_ptr(x), x.numel(), _stream()), "mdx_silu_f16")
+    return x
+
+
+class ControlAdd:
+    """One mdx_control_add_f16 launch: dst[s][r] += scale[s][r] * src[s][src_row[r]] for up to 16 fp16 tensors [nb, ...] at
+    once, in place.  The descriptor (the destinations and their row sizes) is fixed here; everything else lives in three
+    device tables this object owns and the kernel reads when it runs -- `scale` fp32 [n_seg, nb], `src_row` int32 [nb] (-1:
+    the row is not touched) and the source pointers -- so a captured graph that holds run() serves any later set_sources /
+    set_rows / set_scale.  Until the first set_rows every row is -1: run() changes nothing."""
+
+    def __init__(self, dsts):
+        dsts = list(dsts)
+        if not 1 <= len(dsts) <= CONTROL_MAX_SEGS:
+            raise _lib.MdxError(f"ControlAdd: {len(dsts)} segments outside [1, {CONTROL_MAX_SEGS}]")
+        nb, dev = int(dsts[0].shape[0]), dsts[0].device
+        d = _lib.ControlAddDesc()
+        d.n_seg, d.nb = len(dsts), nb
+        for s, t in enumerate(dsts):
+            _chk(t, f16, f"dst[{s}]")
+            if int(t.shape[0]) != nb or t.device != dev:
+                raise _lib.MdxError(f"ControlAdd: dst[{s}] has {int(t.shape[0])} rows on {t.device}, dst[0] {nb} on {dev}")
+            d.dst[s], d.elems_per_row[s] = t.data_ptr(), t.numel() // nb
+        self.dsts, self.nb, self.n_seg, self.device = dsts, nb, len(dsts), dev
+        self.scale = torch.zeros((len(dsts), nb), dtype=f32, device=dev)
+        self.src_row = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+        self.src_ptrs = torch.zeros((CONTROL_MAX_SEGS,), dtype=torch.int64, device=dev)
+        d.src, d.src_row, d.scale = self.src_ptrs.data_ptr(), self.src_row.data_ptr(), self.scale.data_ptr()
+        self.desc = d
+        self.sources = None         # the tensors the pointer table names (kept alive), and their row count
+        self.rows = None            # host copy of src_row
+        self.table_writes = 0       # uploads of the pointer table
+        self._scale_src = None
+
+    def set_sources(self, srcs, rows=None):
+        """The tensor added into dst[s] is srcs[s]: fp16 [rows, ...] with dst[s]'s row size, 16-byte aligned.  `rows`: the row
+        map that goes with them (set_rows; None keeps the current one) -- checked against the NEW sources, so a caller that
+        changes both (another ControlNet batch) never has one checked against the other's predecessor.  The pointer table is
+        uploaded only when a pointer changed."""
+        srcs = list(srcs)
+        if len(srcs) != self.n_seg:
+            raise _lib.MdxError(f"ControlAdd: {len(srcs)} sources for {self.n_seg} segments")
+        n_src = int(srcs[0].shape[0])
+        for s, (t, dt) in enumerate(zip(srcs, self.dsts)):
+            _chk(t, f16, f"src[{s}]")
+            if t.device != self.device or int(t.shape[0]) != n_src or n_src < 1 or t.numel() // n_src != dt.numel() // self.nb:
+                raise _lib.MdxError(f"ControlAdd: src[{s}] {tuple(t.shape)} on {t.device} does not match dst[{s}] "
+                                    f"{tuple(dt.shape)} (rows of {dt.numel() // self.nb} halves, {n_src} source rows)")
+            if t.data_ptr() % 16:
+                raise _lib.MdxError(f"ControlAdd: src[{s}] is not 16-byte aligned")
+        new_rows = self.rows if rows is None else [int(v) for v in rows]
+        if new_rows is not None and max(new_rows) >= n_src:
+            raise _lib.MdxError(f"ControlAdd: the row map {new_rows} reads past the {n_src} source rows")
+        ptrs = [t.data_ptr() for t in srcs]
+        if self.sources is None or ptrs != [t.data_ptr() for t in self.sources]:
+            self.src_ptrs[:self.n_seg].copy_(torch.tensor(ptrs, dtype=torch.int64))
+            self.table_writes += 1
+        self.sources = srcs
+        if rows is not None:
+            self.set_rows(new_rows)
+
+    def set_rows(self, rows):
+        """rows[r]: the source row added into destination row r, or -1 to leave that row alone."""
+        rows = [int(v) for v in rows]
+        n_src = int(self.sources[0].shape[0]) if self.sources is not None else None
+        if len(rows) != self.nb or any(v < -1 for v in rows) or (n_src is not None and max(rows) >= n_src):
+            raise _lib.MdxError(f"ControlAdd: the row map {rows} must hold {self.nb} entries in [-1, {n_src})")
+        if rows != self.rows:
+            self.src_row.copy_(torch.tensor(rows, dtype=torch.int32))
+            self.rows = rows
+
+    def set_scale(self, scale):
+        """scale: fp32 [n_seg, nb] (anything that broadcasts to it), host or device."""
+        if isinstance(scale, torch.Tensor):       # the same tensor, unchanged since the last call: the table holds it already
+            kept = self._scale_src
+            if kept is not None and kept[0]() is scale and kept[1] == scale._version:
+                return
+        s = torch.as_tensor(scale, dtype=f32)
+        self.scale.copy_(s.to(self.device).expand(self.n_seg, self.nb))
+        self._scale_src = (weakref.ref(scale), scale._version) if isinstance(scale, torch.Tensor) else None
+
+    def run(self):
+        if self.sources is None and self.rows is not None and max(self.rows) >= 0:
+            raise _lib.MdxError("ControlAdd: set_sources() must come before a run that reads them")
+        _lib.check(_lib.load().mdx_control_add_f16(ctypes.byref(self.desc), _stream()), "mdx_control_add_f16")
+
+
+def control_add(dsts, srcs, rows, scale):
+    """One-shot form of ControlAdd (tests, tools): dst[s][r] += scale[s][r] * src[s][rows[r]] in place."""
+    ca = ControlAdd(dsts)
+    ca.set_sources(srcs, rows)
+    ca.set_scale(scale)
+    ca.run()
+    return ca

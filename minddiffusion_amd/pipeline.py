@@ -298,9 +298,56 @@ class DiffusionPipeline:
         ctxs = [(torch.cat([uc.to(x.dtype), x], 0) if guided else x).contiguous() for x in ctxs]
         return self.model.regions(self.background_mask(torch.stack(masks)), ctxs)
 
+    # ---- ControlNet (ldm/models/diffusion/controlled.py): a hint image steers the UNet through its skip connections
+    @property
+    def _controlled(self):
+        return bool(getattr(self.model, "is_controlled", False))
+
+    def _refuse_controlled(self, what):
+        if self._controlled:
+            raise MdxError(f"DiffusionPipeline.{what}: not on a controlled pipeline (ControlNet runs in __call__ and img2img)")
+
+    def controlled(self, controlnet):
+        """A new DiffusionPipeline on ControlledDiffusion(self.model, controlnet): the same sampler kind, solver defaults and
+        device, all weights shared.  Its __call__ and img2img take control_image= (the hint, [B | 1, hint_channels, H, W] in
+        [0, 1] at the image's size), control_scale= (a float, one per sample, or one per residual) and control_uncond= (False:
+        the unconditional half of the guidance batch runs without control, and the ControlNet at half the batch); without
+        control_image they do what they do here.  Single rank; not windowed, not hires, no sessions."""
+        from .ldm.models.diffusion.controlled import ControlledDiffusion
+        try:
+            kind = self._session_sampler()
+        except MdxError:
+            raise MdxError(f"DiffusionPipeline.controlled: the new pipeline gets a sampler of this one's kind, 'ddim', 'plms' or "
+                           f"'dpm_solver'; this one's is a {type(self.sampler).__name__}") from None
+        return DiffusionPipeline(ControlledDiffusion(self.model, controlnet), kind, self.device, solver=self._solver())
+
+    def _check_control_allowed(self, what, image):
+        """control_image= is refused, before any work, on a pipeline that is not controlled and on several ranks."""
+        if image is None:
+            return
+        if not self._controlled:
+            raise MdxError(f"{what}: control_image= needs a controlled pipeline (DiffusionPipeline.controlled)")
+        if D.world()[1] > 1:
+            raise MdxError(f"{what}: control_image= runs on a single rank (the sharded form is not built)")
+
+    def _control_scope(self, what, image, scale, uncond, B, latent_hw):
+        """The `with` block of a call's control_image= (None: no block): the hint on the device, one row per sample."""
+        if image is None:
+            return contextlib.nullcontext()
+        self._check_control_allowed(what, image)
+        hint = torch.as_tensor(image)
+        want = tuple(8 * int(v) for v in latent_hw)
+        if hint.dim() != 4 or int(hint.shape[0]) not in (1, B) or tuple(int(v) for v in hint.shape[2:]) != want:
+            raise MdxError(f"{what}: control_image is {tuple(hint.shape)}, expected [{B} | 1, hint_channels, {want[0]}, {want[1]}] "
+                           f"(8 x the latent)")
+        hint = hint.to(self.device, torch.float32)
+        if hint.shape[0] != B:
+            hint = hint.expand(B, -1, -1, -1)
+        return self.model.control(hint.contiguous(), scale=scale, uncond=uncond)
+
     def __call__(self, prompts=None, c=None, uc=None, H=512, W=512, steps=50, scale=9.0, eta=0.0, x_T=None, seed=42,
                  decode=False, gather=False, callback=None, img_callback=None, batch_size=None, per_sample_uc=False,
-                 guidance_rescale=0.0, seeds=None, regions=None):
+                 guidance_rescale=0.0, seeds=None, regions=None, control_image=None, control_scale=1.0, control_uncond=True):
         """Multi-rank runs: every rank calls with the same `prompts` list (or the same `batch_size` when rank 0 passes
         precomputed (c, uc) tensors); only rank 0's c / uc / x_T are used, the other ranks may pass None.
         seeds: one int per sample of the global batch, every rank the same list: sample b's x_T and step noise then depend on
@@ -311,9 +358,11 @@ class DiffusionPipeline:
         scale 7.5" and "50 steps, scale 5, rescale 0.7" -- then share one UNet batch, every sample on its own schedule
         (the samplers' per-request form).  Single rank only.
         regions (a windowed pipeline, single rank): [{"prompt": ... | "c": [B | 1, T, D], "mask": m}, ...] -- regional prompts;
-        m [H/8, W/8] or [H, W] in [0, 1], shared by the batch.  The call's own prompt is region 0, on 1 - max_r m_r."""
+        m [H/8, W/8] or [H, W] in [0, 1], shared by the batch.  The call's own prompt is region 0, on 1 - max_r m_r.
+        control_image / control_scale / control_uncond (a controlled pipeline, single rank): see controlled()."""
         guidance_rescale = self.check_request_lists("DiffusionPipeline", None, steps, scale, guidance_rescale)
         rank, n = D.world()
+        self._check_control_allowed("DiffusionPipeline", control_image)
         self._check_regions_allowed("DiffusionPipeline", regions)
         shape = [4, H // 8, W // 8]                                   # txt2img.py:253
         if rank == 0:
@@ -347,7 +396,8 @@ class DiffusionPipeline:
             x_T = x_T.to(self.device)
         # guidance_rescale needs nothing from the batch sharding: its statistic is per sample, over that sample's C * H * W;
         # the seeds are this rank's samples': the eta > 0 step draws
-        with self._region_scope("DiffusionPipeline", regions, c, uc, scale, shape[1:], (H, W)):
+        with self._region_scope("DiffusionPipeline", regions, c, uc, scale, shape[1:], (H, W)), \
+                self._control_scope("DiffusionPipeline", control_image, control_scale, control_uncond, int(c.shape[0]), shape[1:]):
             samples, inter = self.sampler.sample(S=steps, conditioning=c, batch_size=int(c.shape[0]), shape=shape, verbose=False,
                                                  unconditional_guidance_scale=scale, unconditional_conditioning=uc,
                                                  eta=eta, x_T=x_T, callback=callback, img_callback=img_callback,
@@ -369,6 +419,7 @@ class DiffusionPipeline:
         pads the latent circularly by seam_pad IMAGE pixels (a multiple of 8; 0: the plain decode) per side and crops them.
         The new pipeline's __call__, img2img and inpaint take regions= (regional prompts)."""
         from .ldm.models.diffusion.windowed import WindowedDiffusion, _pair
+        self._refuse_controlled("windowed")
 
         def latent(v, name):
             if v is None:
@@ -405,6 +456,7 @@ class DiffusionPipeline:
         (submit / step / run_until_idle).  sampler: 'ddim' or 'dpm_solver' (default: the pipeline's; PLMS is refused).
         sample_posterior: whether submit(init_image=) requests sample the VAE posterior or take its mode."""
         from .ldm.models.diffusion.session import SamplingSession
+        self._refuse_controlled("session")
         if (sampler or self._session_sampler()) == "dpm_solver" and self._solver():
             raise ValueError(f"DiffusionPipeline.session: a session's slots step through the slot kernels, whose rows hold the "
                              f"multistep order-2 DPM-Solver update only: not with the solver options "
@@ -419,6 +471,7 @@ class DiffusionPipeline:
         strength, keep_mask) included -- through one session of `slots` slots;
         the results come back in REQUEST order, whatever order they finished in.  output: 'latent' [N, 4, H/8, W/8]; 'float'
         [N, 3, H, W] in [0, 1], what __call__(decode=True) returns; 'uint8' [N, H, W, 3], truncated as inpaint.py:112-115."""
+        self._refuse_controlled("serve")
         if output not in ("latent", "float", "uint8"):
             raise ValueError("output must be 'latent', 'float' or 'uint8'")
         requests = list(requests)
@@ -442,7 +495,8 @@ class DiffusionPipeline:
 
     def img2img(self, init_image=None, init_latent=None, strength=0.75, prompts=None, c=None, uc=None, steps=50, scale=9.0,
                 eta=0.0, seed=42, noise=None, post_noise=None, sample_posterior=True, mask=None, decode=False, callback=None,
-                img_callback=None, guidance_rescale=0.0, seeds=None, regions=None):
+                img_callback=None, guidance_rescale=0.0, seeds=None, regions=None, control_image=None, control_scale=1.0,
+                control_uncond=True):
         """Start from an image instead of pure noise: encode it, noise the latent to the level `strength` selects, and run only
         the remaining t_enc = int(strength * steps) of the `steps`-step schedule (strength 1: all of them).
 
@@ -454,9 +508,12 @@ class DiffusionPipeline:
         seeds: one int per sample; the forward noise (ops.RNG_ENCODE), the posterior noise (ops.RNG_POSTERIOR) and the step and
         blend draws of sample b then depend on seeds[b] alone.  A passed noise / post_noise still wins.
         scale and guidance_rescale each take one value or one per sample; steps is one int (`strength` fixes one grid).
-        regions: regional prompts on a windowed pipeline, as in __call__ (masks at the latent's or the init image's size)."""
+        regions: regional prompts on a windowed pipeline, as in __call__ (masks at the latent's or the init image's size).
+        control_image / control_scale / control_uncond: ControlNet on a controlled pipeline, as in __call__ (the hint at 8 x the
+        latent's size)."""
         guidance_rescale = self.check_request_lists("img2img", None, steps, scale, guidance_rescale, steps_list=False)
         self._check_regions_allowed("img2img", regions)
+        self._check_control_allowed("img2img", control_image)
         if (init_image is None) == (init_latent is None):
             raise ValueError("img2img: pass exactly one of init_image and init_latent")
         t_enc = check_strength("img2img", strength, steps)
@@ -490,7 +547,8 @@ class DiffusionPipeline:
         if z0.shape[0] != B:
             raise MdxError(f"img2img: {z0.shape[0]} init images but {B} conditionings")
         image_hw = tuple(init_image.shape[2:]) if init_image is not None else tuple(8 * int(v) for v in z0.shape[2:])
-        with self._region_scope("img2img", regions, c, uc, scale, z0.shape[2:], image_hw):
+        with self._region_scope("img2img", regions, c, uc, scale, z0.shape[2:], image_hw), \
+                self._control_scope("img2img", control_image, control_scale, control_uncond, B, z0.shape[2:]):
             samples = self._run_partial(x_enc, c, uc, start, t_enc, scale, callback, img_callback,
                                         self._sampler_kw(guidance_rescale, seeds), mask=mask, x0=z0)
         return self._decoded(samples) if decode else samples
@@ -547,6 +605,7 @@ class DiffusionPipeline:
         partial-run path as img2img, so samplers, v-prediction, guidance rescale, scale / guidance_rescale lists and seeds all
         carry over; on a wrap_x second pipeline the upscale wraps around too.  regions: regional prompts of the second pass.
         return_base: (result, first-pass latent).  Single rank; the hybrid (9-channel) model is refused."""
+        self._refuse_controlled("hires")
         guidance_rescale = self.check_request_lists("hires", None, steps, scale, guidance_rescale, steps_list=False)
         if hires_steps is not None and (isinstance(hires_steps, bool) or not isinstance(hires_steps, (int, np.integer))
                                         or hires_steps < 1):
