@@ -532,7 +532,9 @@ int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const voi
  *   [MDX_STEP_SQRT_AT_MODEL], [MDX_STEP_SQRT_ONE_MINUS_AT_MODEL]     read for MDX_PRED_V only
  *   [MDX_STEP_C0 + k], k = 0..3         coef4[k]
  *   [MDX_STEP_SQRT_AT], [MDX_STEP_SQRT_ONE_MINUS_AT], [MDX_STEP_SQRT_A_PREV], [MDX_STEP_DIR_COEF], [MDX_STEP_SIGMA]
- *   [14], [15]                          reserved, 0
+ *   [14]                                reserved, 0 (for the middle scale of three-branch guidance, mdx_sampler_step_dual_f32:
+ *                                       the table and slot entries take no middle branch yet)
+ *   [15]                                reserved, 0
  * An ACTIVE row b computes what the scalar entry for its scalars computes on sample b alone, bit for bit:
  * mdx_sampler_step_rescale_f32 if phi != 0 and out_u is given, else mdx_sampler_step_pred_f32 (with MDX_PRED_EPS:
  * mdx_sampler_step_f32).  A term is skipped -- its tensor not read -- when its pointer is NULL OR the row's coefficient is
@@ -661,6 +663,43 @@ int mdx_sampler_step_lin_noise_f32(const float* x_base, const float* x_model, co
                                    float* thr_out, float* factor_out, float cn, const float* noise,
                                    const unsigned long long* seeds, unsigned stream, unsigned draw, int B, int C, int H, int W,
                                    mdx_stream_t s);
+
+/* ---- three-branch guidance (InstructPix2Pix, Brooks et al. 2023: an instruction and an input image guide separately).  Every
+ * model evaluation has three outputs, out_u (empty text, zero image latent), out_m (empty text, image latent) and out_c
+ * (instruction, image latent), and step 1 of both step families becomes, per element,
+ *   m = out_u + mid_scale * (out_m - out_u) + cfg_scale * (out_c - out_m)
+ *     = fma(cfg_scale, out_c - out_m, fma(mid_scale, out_m - out_u, out_u))      both differences rounded, both products fused
+ * (mid_scale is the image guidance scale s_I, cfg_scale the text guidance scale s_T).  Everything after step 1 acts on m as
+ * before: the guidance rescale (f[b] pulls std(m[b]) to std(out_c[b]), the statistics read all three outputs), the v -> eps
+ * conversion, the multistep / history terms, the data or noise prediction, dynamic thresholding and the step noise.
+ * out_m: NHWC fp16 with the layout and out_ld of out_u / out_c, first C channels used.
+ *   mdx_sampler_step_dual_f32      every argument of mdx_sampler_step_rescale_f32 with its meaning, plus out_m, mid_scale.
+ *                                  guidance_rescale == 0: the SPREAD form (factor_out filled with 1.0), else the OWNED form.
+ *   mdx_sampler_step_lin_dual_f32  every argument of mdx_sampler_step_lin_noise_f32 with its meaning, plus out_m, mid_scale.
+ *                                  SPREAD or OWNED by that entry's rule (rescale or thresholding: OWNED); cn == 0 reads no noise
+ *                                  source and launches the kernels without step 8.
+ * ONE launch each.  In the OWNED forms the third stream of loads is issued with the others of a thread's batch of four elements.
+ * out_m == out_u (the same pointer) gives the two-branch entry's bits for cfg_scale, out_m == out_c its bits for
+ * cfg_scale = mid_scale: a difference of exactly 0 adds exactly 0.
+ * out_m == NULL is the two-branch entry (mdx_sampler_step_rescale_f32 / mdx_sampler_step_lin_noise_f32) with the remaining
+ * arguments: the same checks, the same launch, mid_scale not read.
+ * Aliasing: as the two-branch entries; out_m may overlap no output.
+ * Refused before any launch (MDX_E_INVALID), with out_m given: out_u == NULL ("out_m without out_u"); mid_scale not finite; out_m
+ * overlapping e_t_out, x_prev, pred_x0 or factor_out (eps entry) / any output (lin entry); everything the two-branch entry
+ * refuses. */
+int mdx_sampler_step_dual_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                              float cfg_scale, int pred_type, float sqrt_at_model, float sqrt_one_minus_at_model,
+                              const float* old1, const float* old2, const float* old3, const float* coef4, float sqrt_at,
+                              float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma, const float* noise,
+                              float* e_t_out, float* x_prev, float* pred_x0, float guidance_rescale, float* factor_out,
+                              const void* out_m, float mid_scale, int B, int C, int H, int W, mdx_stream_t s);
+int mdx_sampler_step_lin_dual_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                                  float cfg_scale, int pred_type, float guidance_rescale, int value_type, float alpha_m,
+                                  float sigma_m, int thresholding, float max_val, const float* h1, const float* h2, float A,
+                                  float c0, float c1, float c2, float* model_out, float* x_out, float* model_pre_out,
+                                  float* thr_out, float* factor_out, float cn, const float* noise,
+                                  const unsigned long long* seeds, unsigned stream, unsigned draw, const void* out_m,
+                                  float mid_scale, int B, int C, int H, int W, mdx_stream_t s);
 
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */

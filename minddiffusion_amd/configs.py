@@ -17,6 +17,9 @@ WUKONG_LORA_UNET = dict(WUKONG_UNET, enable_lora=True, lora_rank=4, lora_alpha=4
 # vision/wukong-huahua/configs/wukong-huahua_inpaint_inference.yaml:20-36: the same UNet on 9 input channels
 # (4 latent + 1 resized mask + 4 masked-image latent), LatentInpaintDiffusion / conditioning_key 'hybrid'
 WUKONG_INPAINT_UNET = dict(WUKONG_UNET, in_channels=9)
+# an InstructPix2Pix checkpoint (Brooks et al. 2023): the same UNet with 8 input channels (4 latent + 4 of the encoded input
+# image, unscaled), LatentEditDiffusion / conditioning_key 'hybrid'
+WUKONG_EDIT_UNET = dict(WUKONG_UNET, in_channels=8)
 
 # LatentDiffusion params common to both YAMLs (v2-inference.yaml:5-19)
 SD2_LDM = dict(linear_start=0.00085, linear_end=0.0120, timesteps=1000, scale_factor=0.18215,

@@ -26,6 +26,39 @@ __device__ __forceinline__ float cfg_combine(float u, float c, float s) {
     return __builtin_fmaf(s, c - u, u);
 }
 
+// The middle branch of three-branch guidance (InstructPix2Pix: [uu ; ui ; ci] = out_u, out_m, out_c), a compile-time matter:
+// a kernel takes a GuidedMid only in its DUAL instantiation, whose parameter struct carries it behind the two-branch one, so a
+// two-branch launch has the kernarg and the code it has always had.  out_m has out_u's layout; the host refuses it without out_u.
+struct NoMid {
+    static constexpr bool dual = false;
+};
+struct GuidedMid {
+    static constexpr bool dual = true;
+    const f16* out_m;
+    float mid_scale;
+};
+__device__ __forceinline__ NoMid mid_at(const NoMid&, size_t) { return NoMid{}; }
+__device__ __forceinline__ GuidedMid mid_at(const GuidedMid& m, size_t off) { return GuidedMid{m.out_m + off, m.mid_scale}; }
+
+// u + s_i (m - u) + s_t (c - m): both differences rounded, both products fused.  m == u gives cfg_combine(u, c, s_t) and
+// m == c gives cfg_combine(u, c, s_i), to the bit (a difference of exactly 0 adds exactly 0).
+__device__ __forceinline__ float cfg_combine3(float u, float m, float c, float s_i, float s_t) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(s_t, c - m, __builtin_fmaf(s_i, m - u, u));
+}
+
+// the combined model output of one element; GUIDED: ou is known to be there (always so with a middle branch)
+template <bool GUIDED, class M>
+__device__ __forceinline__ float guided_value(const M& mid, const f16* ou, const f16* oc, size_t ei, float cfg_scale) {
+    if constexpr (M::dual) {
+        return cfg_combine3((float)ou[ei], (float)mid.out_m[ei], (float)oc[ei], mid.mid_scale, cfg_scale);
+    } else {
+        float m = (float)oc[ei];
+        if (GUIDED || ou) m = cfg_combine((float)ou[ei], m, cfg_scale);
+        return m;
+    }
+}
+
 // ------------------------------------------------------------------ fused sampler update (plms.py:188-244)
 struct StepParams {
     GuidedPair g;
@@ -43,6 +76,12 @@ struct StepParams {
     // MDX_PRED_V only: the latent the model was evaluated on, sqrt(alphas_cumprod) and sqrt(1 - alphas_cumprod) there
     const float* x_model;
     float am, bm;
+};
+
+// the DUAL instantiations' parameters
+struct StepDualParams {
+    StepParams s;
+    GuidedMid mid;
 };
 
 // The loaded operands of one element (a skipped term's operand stays 0 and is not used) and what the step makes of them.
@@ -76,11 +115,12 @@ __device__ __forceinline__ StepResult step_arith(const StepParams& p, const Step
 // ou / oc: the pair's halves from wherever the caller counts ei (the batch's start or the sample's).  GUIDED: ou is known to
 // be there (a rescaling launch: the host refuses it without) -- the load then hangs on no test of the pointer, which between
 // the loads of a batch would cost a memory round trip each.
-template <int PRED, bool GUIDED>
-__device__ __forceinline__ StepOperands step_load(const StepParams& p, const f16* ou, const f16* oc, size_t ei, size_t i) {
+// mid: the middle branch from where ou / oc start (NoMid: none).
+template <int PRED, bool GUIDED, class M>
+__device__ __forceinline__ StepOperands step_load(const StepParams& p, const M& mid, const f16* ou, const f16* oc, size_t ei,
+                                                  size_t i) {
     StepOperands v{};
-    v.m = (float)oc[ei];
-    if (GUIDED || ou) v.m = cfg_combine((float)ou[ei], v.m, p.g.cfg_scale);
+    v.m = guided_value<GUIDED>(mid, ou, oc, ei, p.g.cfg_scale);
     if constexpr (PRED == MDX_PRED_V) v.x_model = p.x_model[i];
     v.x = p.x[i];
     if (p.old1) v.old1 = p.old1[i];
@@ -97,22 +137,34 @@ __device__ __forceinline__ void step_store(const StepParams& p, size_t i, const 
 }
 
 // the body of sampler_step_kernel and of the spread row kernel: load, call, store
-template <int PRED>
-__device__ __forceinline__ void sampler_step_element(const StepParams& p, size_t i, size_t ei) {
-    step_store(p, i, step_arith<PRED>(p, step_load<PRED, false>(p, p.g.out_u, p.g.out_c, ei, i)));
+template <int PRED, class M = NoMid>
+__device__ __forceinline__ void sampler_step_element(const StepParams& p, size_t i, size_t ei, const M& mid = M{}) {
+    step_store(p, i, step_arith<PRED>(p, step_load<PRED, false>(p, mid, p.g.out_u, p.g.out_c, ei, i)));
 }
 
-template <int PRED>
-__global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
-    mdx_kernarg_touch<sizeof(StepParams)>();
+// SPREAD: the grid-stride loop of sampler_step_kernel and of its DUAL sibling
+template <int PRED, class M>
+__device__ __forceinline__ void sampler_step_spread(const StepParams& p, const M& mid) {
     const size_t total = (size_t)p.B * p.g.C * p.g.HW;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int pix = (int)(i % p.g.HW);
         const size_t bc = i / p.g.HW;
         const int c = (int)(bc % p.g.C);
         const int b = (int)(bc / p.g.C);
-        sampler_step_element<PRED>(p, i, ((size_t)b * p.g.HW + pix) * p.g.ld + c);
+        sampler_step_element<PRED>(p, i, ((size_t)b * p.g.HW + pix) * p.g.ld + c, mid);
     }
+}
+
+template <int PRED>
+__global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
+    mdx_kernarg_touch<sizeof(StepParams)>();
+    sampler_step_spread<PRED>(p, NoMid{});
+}
+
+template <int PRED>
+__global__ __launch_bounds__(256) void sampler_step_dual_kernel(const StepDualParams q) {
+    mdx_kernarg_touch<sizeof(StepDualParams)>();
+    sampler_step_spread<PRED>(q.s, q.mid);
 }
 
 // ------------------------------------------------------------------ fused sampler update with guidance rescale
@@ -131,28 +183,31 @@ constexpr int RESCALE_THREADS = 1024;
 // Sums are taken of d = v - K with K = the mean of the sample's first 64 values (the same bits in every wave), so that
 // sum(d^2) - sum(d)^2 / N cancels nothing to speak of when the outputs sit on an offset far above their spread.
 // Shared by the eps family and the lin family: it reads the guided pair alone.
-__device__ __forceinline__ float rescale_factor(const GuidedPair& g, float phi, int b, float (*part)[4]) {
+// m is the three-branch value where a middle branch is given (mid: from the batch's start); the target std stays out_c's.
+template <class M = NoMid>
+__device__ __forceinline__ float rescale_factor(const GuidedPair& g, float phi, int b, float (*part)[4], const M& mid0 = M{}) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned N = (unsigned)g.C * (unsigned)g.HW;      // per sample: the host refuses what does not fit 31 bits
     const unsigned C = g.C, HW = g.HW;
     const f16* ou = g.out_u + (size_t)b * HW * g.ld;
     const f16* oc = g.out_c + (size_t)b * HW * g.ld;
+    const M mid = mid_at(mid0, (size_t)b * HW * g.ld);
 
     // ---- pass 1: unbiased per-sample std of out_c and of m, in the outputs' own (pixel, channel) order
     float kc, km;
     {
         const unsigned j = (unsigned)lane < N ? (unsigned)lane : N - 1;
         const size_t ei = (size_t)(j / C) * g.ld + j % C;
-        const float c = (float)oc[ei], u = (float)ou[ei];
+        const float c = (float)oc[ei];
         kc = wave_sum(c) * (1.f / 64.f);
-        km = wave_sum(cfg_combine(u, c, g.cfg_scale)) * (1.f / 64.f);
+        km = wave_sum(guided_value<true>(mid, ou, oc, ei, g.cfg_scale)) * (1.f / 64.f);
     }
     float sc = 0.f, scc = 0.f, sm = 0.f, smm = 0.f;
 #pragma unroll 4
     for (unsigned j = threadIdx.x; j < N; j += RESCALE_THREADS) {
         const size_t ei = (size_t)(j / C) * g.ld + j % C;
-        const float c = (float)oc[ei], u = (float)ou[ei];
-        const float dc = c - kc, dm = cfg_combine(u, c, g.cfg_scale) - km;
+        const float c = (float)oc[ei];
+        const float dc = c - kc, dm = guided_value<true>(mid, ou, oc, ei, g.cfg_scale) - km;
         sc += dc;
         scc += dc * dc;
         sm += dm;
@@ -189,12 +244,13 @@ __device__ __forceinline__ float rescale_factor(const GuidedPair& g, float phi, 
 // stores.  Without the batching every trip of the loop waits out one memory latency behind the previous trip's stores (a
 // workgroup has a sample to itself, so there is no one else to hide it).  f == 1 (a phi == 0 row) multiplies exactly, so the
 // result is sampler_step_kernel's: both run step_arith.
-template <int PRED>
-__device__ __forceinline__ void rescale_apply(const StepParams& p, float f, int b) {
+template <int PRED, class M = NoMid>
+__device__ __forceinline__ void rescale_apply(const StepParams& p, float f, int b, const M& mid0 = M{}) {
     const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW;
     const unsigned HW = p.g.HW;
     const f16* ou = p.g.out_u + (size_t)b * HW * p.g.ld;
     const f16* oc = p.g.out_c + (size_t)b * HW * p.g.ld;
+    const M mid = mid_at(mid0, (size_t)b * HW * p.g.ld);      // its loads go out with the batch's others, below
     constexpr int U = 4;
     const size_t base = (size_t)b * N;
     for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * U) {
@@ -204,7 +260,7 @@ __device__ __forceinline__ void rescale_apply(const StepParams& p, float f, int 
             const unsigned j = j0 + u * RESCALE_THREADS;
             if (j < N) {
                 const unsigned c = j / HW;
-                v[u] = step_load<PRED, true>(p, ou, oc, (size_t)(j - c * HW) * p.g.ld + c, base + j);
+                v[u] = step_load<PRED, true>(p, mid, ou, oc, (size_t)(j - c * HW) * p.g.ld + c, base + j);
             }
         }
 #pragma unroll
@@ -227,6 +283,22 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_kernel(c
     const float f = rescale_factor(p.g, rp.phi, b, part);
     if (rp.factor_out && threadIdx.x == 0) rp.factor_out[b] = f;
     rescale_apply<PRED>(p, f, b);
+}
+
+struct RescaleDualParams {
+    RescaleParams r;
+    GuidedMid mid;
+};
+
+template <int PRED>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_rescale_dual_kernel(const RescaleDualParams q) {
+    mdx_kernarg_touch<sizeof(RescaleDualParams)>();
+    const StepParams& p = q.r.s;
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    const int b = blockIdx.x;
+    const float f = rescale_factor(p.g, q.r.phi, b, part, q.mid);
+    if (q.r.factor_out && threadIdx.x == 0) q.r.factor_out[b] = f;
+    rescale_apply<PRED>(p, f, b, q.mid);
 }
 
 // ------------------------------------------------------------------ fused sampler update, per-sample scalars from a row
@@ -368,6 +440,13 @@ struct LinNoiseParams {
     LinNoise n;
 };
 
+// the DUAL instantiations' parameters, with and without noise (mdx_sampler_step_lin_dual_f32)
+struct LinDualParams {
+    LinParams l;
+    LinNoise n;
+    GuidedMid mid;
+};
+
 constexpr int LIN_U = 4;
 
 // the quad that starts at element j0 (a multiple of 4) of sample b
@@ -390,11 +469,11 @@ template <int PRED, int VALUE>
 constexpr bool lin_reads_x_model = PRED == MDX_PRED_V || VALUE == MDX_VALUE_X0;
 
 // what steps 1-4 read: the CFG-combined model output and the latent the model was evaluated on
-template <int PRED, int VALUE>
-__device__ __forceinline__ void lin_load_model(const LinParams& p, const f16* ou, const f16* oc, size_t ei, size_t i,
-                                               LinOperands& v) {
-    v.m = (float)oc[ei];
-    if (ou) v.m = cfg_combine((float)ou[ei], v.m, p.g.cfg_scale);
+// (mid: the middle branch from where ou / oc start, NoMid: none)
+template <int PRED, int VALUE, class M>
+__device__ __forceinline__ void lin_load_model(const LinParams& p, const M& mid, const f16* ou, const f16* oc, size_t ei,
+                                               size_t i, LinOperands& v) {
+    v.m = guided_value<false>(mid, ou, oc, ei, p.g.cfg_scale);
     if constexpr (lin_reads_x_model<PRED, VALUE>) v.x_model = p.x_model[i];
 }
 
@@ -443,9 +522,8 @@ __device__ __forceinline__ void lin_element(const LinParams& p, const LinNoise& 
 }
 
 // SPREAD: sampler_step_kernel's grid and element order
-template <int PRED, int VALUE>
-__global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p) {
-    mdx_kernarg_touch<sizeof(LinParams)>();
+template <int PRED, int VALUE, class M>
+__device__ __forceinline__ void sampler_step_lin_spread(const LinParams& p, const M& mid) {
     const size_t total = (size_t)p.B * p.g.C * p.g.HW;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int pix = (int)(i % p.g.HW);
@@ -453,10 +531,22 @@ __global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p
         const int c = (int)(bc % p.g.C);
         const int b = (int)(bc / p.g.C);
         LinOperands v{};
-        lin_load_model<PRED, VALUE>(p, p.g.out_u, p.g.out_c, ((size_t)b * p.g.HW + pix) * p.g.ld + c, i, v);
+        lin_load_model<PRED, VALUE>(p, mid, p.g.out_u, p.g.out_c, ((size_t)b * p.g.HW + pix) * p.g.ld + c, i, v);
         lin_load_terms<LIN_NOISE_NONE>(p, LinNoise{}, i, v);
         lin_element<PRED, VALUE, false, LIN_NOISE_NONE>(p, LinNoise{}, i, v);
     }
+}
+
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p) {
+    mdx_kernarg_touch<sizeof(LinParams)>();
+    sampler_step_lin_spread<PRED, VALUE>(p, NoMid{});
+}
+
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(256) void sampler_step_lin_dual_kernel(const LinDualParams q) {
+    mdx_kernarg_touch<sizeof(LinDualParams)>();
+    sampler_step_lin_spread<PRED, VALUE>(q.l, q.mid);
 }
 
 // SPREAD with step 8: a quad per thread and trip, all loads first (the draw's arithmetic then runs under their latency), then
@@ -464,10 +554,8 @@ __global__ __launch_bounds__(256) void sampler_step_lin_kernel(const LinParams p
 // 64-thread workgroups: a quad is four elements, so the latent of a UNet batch still spreads over a hundred CUs and more.
 constexpr int LIN_NOISE_THREADS = 64;
 
-template <int PRED, int VALUE, int NOISE>
-__global__ __launch_bounds__(LIN_NOISE_THREADS) void sampler_step_lin_noise_kernel(const LinNoiseParams q) {
-    mdx_kernarg_touch<sizeof(LinNoiseParams)>();
-    const LinParams& p = q.l;
+template <int PRED, int VALUE, int NOISE, class M>
+__device__ __forceinline__ void sampler_step_lin_noise_spread(const LinParams& p, const LinNoise& n, const M& mid) {
     const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW, HW = p.g.HW;       // the host refuses what does not fit 31 bits
     const unsigned quads = (N + 3u) / 4u;
     const size_t items = (size_t)p.B * quads;
@@ -483,20 +571,32 @@ __global__ __launch_bounds__(LIN_NOISE_THREADS) void sampler_step_lin_noise_kern
             v[u] = LinOperands{};
             if (j < N) {
                 const unsigned c = j / HW;
-                lin_load_model<PRED, VALUE>(p, p.g.out_u, p.g.out_c, ((size_t)b * HW + (j - c * HW)) * p.g.ld + c, base + j, v[u]);
-                lin_load_terms<NOISE>(p, q.n, base + j, v[u]);
+                lin_load_model<PRED, VALUE>(p, mid, p.g.out_u, p.g.out_c, ((size_t)b * HW + (j - c * HW)) * p.g.ld + c, base + j, v[u]);
+                lin_load_terms<NOISE>(p, n, base + j, v[u]);
             }
         }
         if constexpr (NOISE == LIN_NOISE_SEEDED) {
             float z[LIN_U];
-            lin_quad_z(q.n, b, j0, z);
+            lin_quad_z(n, b, j0, z);
 #pragma unroll
             for (int u = 0; u < LIN_U; ++u) v[u].z = z[u];
         }
 #pragma unroll
         for (int u = 0; u < LIN_U; ++u)
-            if (j0 + u < N) lin_element<PRED, VALUE, false, NOISE>(p, q.n, base + j0 + u, v[u]);
+            if (j0 + u < N) lin_element<PRED, VALUE, false, NOISE>(p, n, base + j0 + u, v[u]);
     }
+}
+
+template <int PRED, int VALUE, int NOISE>
+__global__ __launch_bounds__(LIN_NOISE_THREADS) void sampler_step_lin_noise_kernel(const LinNoiseParams q) {
+    mdx_kernarg_touch<sizeof(LinNoiseParams)>();
+    sampler_step_lin_noise_spread<PRED, VALUE, NOISE>(q.l, q.n, NoMid{});
+}
+
+template <int PRED, int VALUE, int NOISE>
+__global__ __launch_bounds__(LIN_NOISE_THREADS) void sampler_step_lin_noise_dual_kernel(const LinDualParams q) {
+    mdx_kernarg_touch<sizeof(LinDualParams)>();
+    sampler_step_lin_noise_spread<PRED, VALUE, NOISE>(q.l, q.n, q.mid);
 }
 
 // OWNED, the passes over a sample, U elements of a thread at a time as rescale_apply does it (all loads, then the
@@ -531,11 +631,12 @@ __device__ __forceinline__ void lin_owned_z(const LinNoise& n, int b, unsigned j
 }
 
 // Steps 1-4 (and, without thresholding, 7 and 8).  PARK: the values wait in model_out for the selection.
-template <int PRED, int VALUE, bool PARK, int NOISE>
-__device__ __forceinline__ void lin_owned_values(const LinParams& p, const LinNoise& n, float f, int b) {
+template <int PRED, int VALUE, bool PARK, int NOISE, class M>
+__device__ __forceinline__ void lin_owned_values(const LinParams& p, const LinNoise& n, const M& mid0, float f, int b) {
     const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW, HW = p.g.HW;
     const f16* oc = p.g.out_c + (size_t)b * HW * p.g.ld;
     const f16* ou = p.g.out_u ? p.g.out_u + (size_t)b * HW * p.g.ld : nullptr;
+    const M mid = mid_at(mid0, (size_t)b * HW * p.g.ld);      // its loads go out with the batch's others, below
     const size_t base = (size_t)b * N;
     for (unsigned j0 = threadIdx.x; lin_owned_trip<NOISE>(j0, N); j0 += RESCALE_THREADS * LIN_U) {
         LinOperands v[LIN_U];
@@ -545,7 +646,7 @@ __device__ __forceinline__ void lin_owned_values(const LinParams& p, const LinNo
             v[u] = LinOperands{};
             if (j < N) {
                 const unsigned c = j / HW;
-                lin_load_model<PRED, VALUE>(p, ou, oc, (size_t)(j - c * HW) * p.g.ld + c, base + j, v[u]);
+                lin_load_model<PRED, VALUE>(p, mid, ou, oc, (size_t)(j - c * HW) * p.g.ld + c, base + j, v[u]);
                 if constexpr (!PARK) lin_load_terms<NOISE>(p, n, base + j, v[u]);
             }
         }
@@ -692,12 +793,17 @@ __device__ __forceinline__ void lin_owned_finish(const LinParams& p, const LinNo
     }
 }
 
-// OWNED: one kernel for both entries.  P is LinParams (mdx_sampler_step_lin_f32: NOISE is LIN_NOISE_NONE, the kernel that
-// entry has always launched) or LinNoiseParams.
+// OWNED: one kernel for all entries.  P is LinParams (mdx_sampler_step_lin_f32: NOISE is LIN_NOISE_NONE, the kernel that
+// entry has always launched), LinNoiseParams, or LinDualParams (a middle branch, any NOISE).
 __device__ __forceinline__ const LinParams& lin_of(const LinParams& p) { return p; }
 __device__ __forceinline__ const LinParams& lin_of(const LinNoiseParams& q) { return q.l; }
+__device__ __forceinline__ const LinParams& lin_of(const LinDualParams& q) { return q.l; }
 __device__ __forceinline__ LinNoise lin_noise_of(const LinParams&) { return LinNoise{}; }
 __device__ __forceinline__ LinNoise lin_noise_of(const LinNoiseParams& q) { return q.n; }
+__device__ __forceinline__ LinNoise lin_noise_of(const LinDualParams& q) { return q.n; }
+__device__ __forceinline__ NoMid lin_mid_of(const LinParams&) { return NoMid{}; }
+__device__ __forceinline__ NoMid lin_mid_of(const LinNoiseParams&) { return NoMid{}; }
+__device__ __forceinline__ GuidedMid lin_mid_of(const LinDualParams& q) { return q.mid; }
 
 template <int PRED, int VALUE, int NOISE, class P>
 __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel(const P q) {
@@ -707,13 +813,14 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel
     __shared__ unsigned sel[4];
     const LinParams& p = lin_of(q);
     const LinNoise n = lin_noise_of(q);
+    const auto mid = lin_mid_of(q);
     const int b = blockIdx.x;
     float f = 1.f;
-    if (p.phi != 0.f) f = rescale_factor(p.g, p.phi, b, part);
+    if (p.phi != 0.f) f = rescale_factor(p.g, p.phi, b, part, mid);
     if (p.factor_out && threadIdx.x == 0) p.factor_out[b] = f;
     if constexpr (VALUE == MDX_VALUE_X0) {
         if (p.thresholding) {
-            lin_owned_values<PRED, VALUE, true, NOISE>(p, n, f, b);
+            lin_owned_values<PRED, VALUE, true, NOISE>(p, n, mid, f, b);
             __syncthreads();        // (a thread reads back only what it parked itself; the barrier is for sel / hist)
             const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW;
             const float s = lin_threshold_s(p, p.model_out + (size_t)b * N, N, hist, sel);
@@ -722,7 +829,7 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel
             return;
         }
     }
-    lin_owned_values<PRED, VALUE, false, NOISE>(p, n, f, b);
+    lin_owned_values<PRED, VALUE, false, NOISE>(p, n, mid, f, b);
 }
 
 // ------------------------------------------------------------------ per-slot row gather (mdx_slot_gather_f32)
@@ -767,6 +874,20 @@ int fill_factor_one(const char* fn, float* factor_out, int B, hipStream_t st) {
 int sample_extent_check(const char* fn, size_t N, bool with_std) {
     MDX_REQUIRE(!with_std || N >= 2, "%s: the per-sample std needs C * H * W >= 2", fn);
     MDX_REQUIRE(N <= 0x7fffffffu, "%s: bad extents (C * H * W of one sample exceeds 31 bits)", fn);
+    return MDX_OK;
+}
+
+bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || na == 0 || nb == 0) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// What both DUAL entries refuse about the middle branch itself (out_m != nullptr); its overlaps are the entries' own.
+int guided_mid_check(const char* fn, const void* out_u, float mid_scale) {
+    MDX_REQUIRE(out_u, "%s: out_m without out_u (the middle branch extends a guided pair)", fn);
+    MDX_REQUIRE(mid_scale >= -3.402823466e38f && mid_scale <= 3.402823466e38f, "%s: mid_scale %g is not finite", fn,
+                (double)mid_scale);
     return MDX_OK;
 }
 
@@ -857,14 +978,14 @@ extern "C" int mdx_sampler_step_pred_f32(const float* x, const float* x_model, c
                                s);
 }
 
-extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
-                                            int out_ld, float cfg_scale, int pred_type, float sqrt_at_model,
-                                            float sqrt_one_minus_at_model, const float* old1, const float* old2,
-                                            const float* old3, const float* coef4, float sqrt_at, float sqrt_one_minus_at,
-                                            float sqrt_a_prev, float dir_coef, float sigma, const float* noise,
-                                            float* e_t_out, float* x_prev, float* pred_x0, float guidance_rescale,
-                                            float* factor_out, int B, int C, int H, int W, mdx_stream_t s) {
-    const char* fn = "mdx_sampler_step_rescale_f32";
+// The rescale entry and its DUAL superset: out_m == nullptr is the two-branch body, launch for launch.
+static int sampler_step_rescale_entry(const char* fn, const float* x, const float* x_model, const void* out_u,
+                                      const void* out_c, int out_ld, float cfg_scale, int pred_type, float sqrt_at_model,
+                                      float sqrt_one_minus_at_model, const float* old1, const float* old2, const float* old3,
+                                      const float* coef4, float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev,
+                                      float dir_coef, float sigma, const float* noise, float* e_t_out, float* x_prev,
+                                      float* pred_x0, float guidance_rescale, float* factor_out, const void* out_m,
+                                      float mid_scale, int B, int C, int H, int W, mdx_stream_t s) {
     RescaleParams rp;
     int rc = sampler_step_params(rp.s, fn, x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, sqrt_at_model,
                                  sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at, sqrt_one_minus_at, sqrt_a_prev,
@@ -873,16 +994,66 @@ extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model
     MDX_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "%s: guidance_rescale %g is not in [0, 1]", fn,
                 (double)guidance_rescale);
     if ((rc = sample_extent_check(fn, (size_t)C * H * W, true)) != MDX_OK) return rc;
+    const bool v = pred_type == MDX_PRED_V;
+    if (out_m) {
+        if ((rc = guided_mid_check(fn, out_u, mid_scale)) != MDX_OK) return rc;
+        const size_t nx = (size_t)B * C * H * W * sizeof(float), nh = (((size_t)B * H * W - 1) * out_ld + C) * sizeof(f16);
+        const struct { const void* ptr; size_t bytes; const char* name; } outs[] = {
+            {e_t_out, nx, "e_t_out"}, {x_prev, nx, "x_prev"}, {pred_x0, nx, "pred_x0"}, {factor_out, B * sizeof(float), "factor_out"}};
+        for (const auto& o : outs)
+            MDX_REQUIRE(!bytes_overlap(o.ptr, o.bytes, out_m, nh), "%s: %s overlaps out_m", fn, o.name);
+        const GuidedMid mid{(const f16*)out_m, mid_scale};
+        if (guidance_rescale == 0.f) {      // SPREAD, as the two-branch entry chooses
+            const StepDualParams q{rp.s, mid};
+            hipLaunchKernelGGL(v ? sampler_step_dual_kernel<MDX_PRED_V> : sampler_step_dual_kernel<MDX_PRED_EPS>,
+                               dim3(grid_for((size_t)B * C * H * W)), dim3(256), 0, (hipStream_t)s, q);
+            MDX_LAUNCH_CHECK(fn);
+            return fill_factor_one(fn, factor_out, B, (hipStream_t)s);
+        }
+        rp.phi = guidance_rescale;
+        rp.factor_out = factor_out;
+        const RescaleDualParams q{rp, mid};
+        hipLaunchKernelGGL(v ? sampler_step_rescale_dual_kernel<MDX_PRED_V> : sampler_step_rescale_dual_kernel<MDX_PRED_EPS>,
+                           dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, q);
+        MDX_LAUNCH_CHECK(fn);
+        return MDX_OK;
+    }
     if (guidance_rescale == 0.f || !out_u) {      // f == 1: the launch of mdx_sampler_step_pred_f32, bit for bit
         rc = sampler_step_run(fn, rp.s, pred_type, s);
         return rc != MDX_OK ? rc : fill_factor_one(fn, factor_out, B, (hipStream_t)s);
     }
     rp.phi = guidance_rescale;
     rp.factor_out = factor_out;
-    const auto kernel = pred_type == MDX_PRED_V ? sampler_step_rescale_kernel<MDX_PRED_V> : sampler_step_rescale_kernel<MDX_PRED_EPS>;
+    const auto kernel = v ? sampler_step_rescale_kernel<MDX_PRED_V> : sampler_step_rescale_kernel<MDX_PRED_EPS>;
     hipLaunchKernelGGL(kernel, dim3(B), dim3(RESCALE_THREADS), 0, (hipStream_t)s, rp);
     MDX_LAUNCH_CHECK(fn);
     return MDX_OK;
+}
+
+extern "C" int mdx_sampler_step_rescale_f32(const float* x, const float* x_model, const void* out_u, const void* out_c,
+                                            int out_ld, float cfg_scale, int pred_type, float sqrt_at_model,
+                                            float sqrt_one_minus_at_model, const float* old1, const float* old2,
+                                            const float* old3, const float* coef4, float sqrt_at, float sqrt_one_minus_at,
+                                            float sqrt_a_prev, float dir_coef, float sigma, const float* noise,
+                                            float* e_t_out, float* x_prev, float* pred_x0, float guidance_rescale,
+                                            float* factor_out, int B, int C, int H, int W, mdx_stream_t s) {
+    return sampler_step_rescale_entry("mdx_sampler_step_rescale_f32", x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
+                                      sqrt_at_model, sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at,
+                                      sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev, pred_x0,
+                                      guidance_rescale, factor_out, nullptr, 0.f, B, C, H, W, s);
+}
+
+extern "C" int mdx_sampler_step_dual_f32(const float* x, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                                         float cfg_scale, int pred_type, float sqrt_at_model, float sqrt_one_minus_at_model,
+                                         const float* old1, const float* old2, const float* old3, const float* coef4,
+                                         float sqrt_at, float sqrt_one_minus_at, float sqrt_a_prev, float dir_coef, float sigma,
+                                         const float* noise, float* e_t_out, float* x_prev, float* pred_x0,
+                                         float guidance_rescale, float* factor_out, const void* out_m, float mid_scale, int B,
+                                         int C, int H, int W, mdx_stream_t s) {
+    return sampler_step_rescale_entry("mdx_sampler_step_dual_f32", x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
+                                      sqrt_at_model, sqrt_one_minus_at_model, old1, old2, old3, coef4, sqrt_at,
+                                      sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise, e_t_out, x_prev, pred_x0,
+                                      guidance_rescale, factor_out, out_m, mid_scale, B, C, H, W, s);
 }
 
 // The table entry and the slot entry (slot_start != nullptr): the pointer and extent checks of the scalar entries on
@@ -971,16 +1142,33 @@ extern "C" int mdx_slot_gather_f32(const float* src, const int* slot_start, cons
 }
 
 // ---- mdx_sampler_step_lin_f32
-static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || na == 0 || nb == 0) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 
-// nz == nullptr: the kernels mdx_sampler_step_lin_f32 has always launched
+// nz == nullptr: the kernels mdx_sampler_step_lin_f32 has always launched.  mid: the DUAL instantiations, same grids.
 template <int PRED, int VALUE>
-static void sampler_step_lin_run(const LinParams& p, const LinNoise* nz, bool owned, hipStream_t st) {
+static void sampler_step_lin_run(const LinParams& p, const LinNoise* nz, const GuidedMid* mid, bool owned, hipStream_t st) {
     const dim3 own_grid(p.B), own_block(RESCALE_THREADS);
+    if (mid) {
+        const LinDualParams d{p, nz ? *nz : LinNoise{}, *mid};
+        const int noise = !nz ? LIN_NOISE_NONE : nz->seeds ? LIN_NOISE_SEEDED : LIN_NOISE_TENSOR;
+        const size_t ditems = (size_t)p.B * (((size_t)p.g.C * p.g.HW + 3) / 4);
+        const size_t dblocks = (ditems + LIN_NOISE_THREADS - 1) / LIN_NOISE_THREADS;
+        const dim3 dgrid((unsigned)(dblocks > 8192 ? 8192 : dblocks)), dblock(LIN_NOISE_THREADS);
+        if (owned) {
+            if (noise == LIN_NOISE_NONE)
+                hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, LIN_NOISE_NONE, LinDualParams>), own_grid, own_block, 0, st, d);
+            else if (noise == LIN_NOISE_SEEDED)
+                hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, LIN_NOISE_SEEDED, LinDualParams>), own_grid, own_block, 0, st, d);
+            else
+                hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, LIN_NOISE_TENSOR, LinDualParams>), own_grid, own_block, 0, st, d);
+        } else if (noise == LIN_NOISE_NONE) {
+            hipLaunchKernelGGL((sampler_step_lin_dual_kernel<PRED, VALUE>), dim3(grid_for((size_t)p.B * p.g.C * p.g.HW)), dim3(256), 0, st, d);
+        } else if (noise == LIN_NOISE_SEEDED) {
+            hipLaunchKernelGGL((sampler_step_lin_noise_dual_kernel<PRED, VALUE, LIN_NOISE_SEEDED>), dgrid, dblock, 0, st, d);
+        } else {
+            hipLaunchKernelGGL((sampler_step_lin_noise_dual_kernel<PRED, VALUE, LIN_NOISE_TENSOR>), dgrid, dblock, 0, st, d);
+        }
+        return;
+    }
     if (!nz) {
         if (owned)
             hipLaunchKernelGGL((sampler_step_lin_owned_kernel<PRED, VALUE, LIN_NOISE_NONE, LinParams>), own_grid, own_block, 0, st, p);
@@ -1010,8 +1198,8 @@ static int sampler_step_lin_entry(const char* fn, const float* x_base, const flo
                                   const void* out_c, int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
                                   int value_type, float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
                                   const float* h2, float A, float c0, float c1, float c2, float* model_out, float* x_out,
-                                  float* model_pre_out, float* thr_out, float* factor_out, const LinNoise* nz, int B, int C,
-                                  int H, int W, mdx_stream_t s) {
+                                  float* model_pre_out, float* thr_out, float* factor_out, const LinNoise* nz,
+                                  const void* out_m, float mid_scale, int B, int C, int H, int W, mdx_stream_t s) {
     MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
     MDX_REQUIRE(value_type == MDX_VALUE_X0 || value_type == MDX_VALUE_EPS, "%s: unknown value_type %d", fn, value_type);
     MDX_REQUIRE(x_base && x_model && out_c && model_out && x_out, "%s: null pointer", fn);
@@ -1025,6 +1213,7 @@ static int sampler_step_lin_entry(const char* fn, const float* x_base, const flo
                 (double)guidance_rescale);
     const bool rescale = guidance_rescale != 0.f && out_u;
     if ((rc = sample_extent_check(fn, N, rescale)) != MDX_OK) return rc;
+    if (out_m && (rc = guided_mid_check(fn, out_u, mid_scale)) != MDX_OK) return rc;
     if (thresholding) {
         MDX_REQUIRE(value_type == MDX_VALUE_X0, "%s: thresholding acts on a data prediction (MDX_VALUE_X0)", fn);
         MDX_REQUIRE(N >= 2, "%s: thresholding needs two order statistics, C * H * W >= 2", fn);
@@ -1037,6 +1226,7 @@ static int sampler_step_lin_entry(const char* fn, const float* x_base, const flo
         {model_out, nx, "model_out"}, {x_out, nx, "x_out"}, {model_pre_out, nx, "model_pre_out"},
         {thr_out, B * sizeof(float), "thr_out"}, {factor_out, B * sizeof(float), "factor_out"}},
       ins[] = {{A != 0.f ? x_base : nullptr, nx, "x_base"}, {x_model, nx, "x_model"}, {out_u, nh, "out_u"}, {out_c, nh, "out_c"},
+               {out_m, nh, "out_m"},
                {c1 != 0.f ? h1 : nullptr, nx, "h1"}, {c2 != 0.f ? h2 : nullptr, nx, "h2"},
                {nz ? nz->noise : nullptr, nx, "noise"}, {nz ? nz->seeds : nullptr, B * sizeof(unsigned long long), "seeds"}};
     for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
@@ -1077,7 +1267,8 @@ static int sampler_step_lin_entry(const char* fn, const float* x_base, const flo
     const auto run = pred_type == MDX_PRED_V
                          ? (value_type == MDX_VALUE_X0 ? sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_X0> : sampler_step_lin_run<MDX_PRED_V, MDX_VALUE_EPS>)
                          : (value_type == MDX_VALUE_X0 ? sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_X0> : sampler_step_lin_run<MDX_PRED_EPS, MDX_VALUE_EPS>);
-    run(p, nz, owned, st);
+    const GuidedMid mid{(const f16*)out_m, mid_scale};
+    run(p, nz, out_m ? &mid : nullptr, owned, st);
     MDX_LAUNCH_CHECK(fn);
     return owned ? MDX_OK : fill_factor_one(fn, factor_out, B, st);      // f == 1 everywhere, as mdx_sampler_step_rescale_f32 reports it
 }
@@ -1090,7 +1281,26 @@ extern "C" int mdx_sampler_step_lin_f32(const float* x_base, const float* x_mode
                                         int H, int W, mdx_stream_t s) {
     return sampler_step_lin_entry("mdx_sampler_step_lin_f32", x_base, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
                                   guidance_rescale, value_type, alpha_m, sigma_m, thresholding, max_val, h1, h2, A, c0, c1, c2,
-                                  model_out, x_out, model_pre_out, thr_out, factor_out, nullptr, B, C, H, W, s);
+                                  model_out, x_out, model_pre_out, thr_out, factor_out, nullptr, nullptr, 0.f, B, C, H, W, s);
+}
+
+// The noise entry and its DUAL superset: out_m == nullptr is the two-branch body, launch for launch.
+static int sampler_step_lin_noise_entry(const char* fn, const float* x_base, const float* x_model, const void* out_u,
+                                        const void* out_c, int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
+                                        int value_type, float alpha_m, float sigma_m, int thresholding, float max_val,
+                                        const float* h1, const float* h2, float A, float c0, float c1, float c2,
+                                        float* model_out, float* x_out, float* model_pre_out, float* thr_out, float* factor_out,
+                                        float cn, const float* noise, const unsigned long long* seeds, unsigned stream,
+                                        unsigned draw, const void* out_m, float mid_scale, int B, int C, int H, int W,
+                                        mdx_stream_t s) {
+    MDX_REQUIRE(cn >= -3.402823466e38f && cn <= 3.402823466e38f, "%s: cn %g is not finite", fn, (double)cn);
+    MDX_REQUIRE(stream < DROPOUT_STREAM_BIT, "%s: stream %u is not below 2^31", fn, stream);
+    MDX_REQUIRE(cn == 0.f || ((noise != nullptr) != (seeds != nullptr)),
+                "%s: cn != 0 takes exactly one noise source, noise or seeds (got %s)", fn, noise ? "both" : "neither");
+    const LinNoise nz{cn, noise, noise ? nullptr : seeds, stream, draw};
+    return sampler_step_lin_entry(fn, x_base, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, guidance_rescale, value_type,
+                                  alpha_m, sigma_m, thresholding, max_val, h1, h2, A, c0, c1, c2, model_out, x_out,
+                                  model_pre_out, thr_out, factor_out, cn != 0.f ? &nz : nullptr, out_m, mid_scale, B, C, H, W, s);
 }
 
 extern "C" int mdx_sampler_step_lin_noise_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
@@ -1100,13 +1310,22 @@ extern "C" int mdx_sampler_step_lin_noise_f32(const float* x_base, const float* 
                                               float* model_out, float* x_out, float* model_pre_out, float* thr_out,
                                               float* factor_out, float cn, const float* noise, const unsigned long long* seeds,
                                               unsigned stream, unsigned draw, int B, int C, int H, int W, mdx_stream_t s) {
-    const char* fn = "mdx_sampler_step_lin_noise_f32";
-    MDX_REQUIRE(cn >= -3.402823466e38f && cn <= 3.402823466e38f, "%s: cn %g is not finite", fn, (double)cn);
-    MDX_REQUIRE(stream < DROPOUT_STREAM_BIT, "%s: stream %u is not below 2^31", fn, stream);
-    MDX_REQUIRE(cn == 0.f || ((noise != nullptr) != (seeds != nullptr)),
-                "%s: cn != 0 takes exactly one noise source, noise or seeds (got %s)", fn, noise ? "both" : "neither");
-    const LinNoise nz{cn, noise, noise ? nullptr : seeds, stream, draw};
-    return sampler_step_lin_entry(fn, x_base, x_model, out_u, out_c, out_ld, cfg_scale, pred_type, guidance_rescale, value_type,
-                                  alpha_m, sigma_m, thresholding, max_val, h1, h2, A, c0, c1, c2, model_out, x_out,
-                                  model_pre_out, thr_out, factor_out, cn != 0.f ? &nz : nullptr, B, C, H, W, s);
+    return sampler_step_lin_noise_entry("mdx_sampler_step_lin_noise_f32", x_base, x_model, out_u, out_c, out_ld, cfg_scale,
+                                        pred_type, guidance_rescale, value_type, alpha_m, sigma_m, thresholding, max_val, h1, h2,
+                                        A, c0, c1, c2, model_out, x_out, model_pre_out, thr_out, factor_out, cn, noise, seeds,
+                                        stream, draw, nullptr, 0.f, B, C, H, W, s);
+}
+
+extern "C" int mdx_sampler_step_lin_dual_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
+                                             int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
+                                             int value_type, float alpha_m, float sigma_m, int thresholding, float max_val,
+                                             const float* h1, const float* h2, float A, float c0, float c1, float c2,
+                                             float* model_out, float* x_out, float* model_pre_out, float* thr_out,
+                                             float* factor_out, float cn, const float* noise, const unsigned long long* seeds,
+                                             unsigned stream, unsigned draw, const void* out_m, float mid_scale, int B, int C,
+                                             int H, int W, mdx_stream_t s) {
+    return sampler_step_lin_noise_entry("mdx_sampler_step_lin_dual_f32", x_base, x_model, out_u, out_c, out_ld, cfg_scale,
+                                        pred_type, guidance_rescale, value_type, alpha_m, sigma_m, thresholding, max_val, h1, h2,
+                                        A, c0, c1, c2, model_out, x_out, model_pre_out, thr_out, factor_out, cn, noise, seeds,
+                                        stream, draw, out_m, mid_scale, B, C, H, W, s);
 }

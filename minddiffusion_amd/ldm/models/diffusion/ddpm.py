@@ -226,3 +226,21 @@ class LatentInpaintDiffusion(LatentDiffusion):
         self.masked_image_key = masked_image_key
         assert self.masked_image_key in concat_keys
         self.concat_keys = concat_keys
+
+
+class LatentEditDiffusion(LatentDiffusion):
+    """InstructPix2Pix (Brooks et al. 2023; not in the reference): hybrid conditioning -- the UNet sees cat(x, latent of the
+    image to edit) (8 channels, configs.WUKONG_EDIT_UNET) plus the text cross-attention context of the instruction.  The
+    samplers run it under three-branch guidance (image_guidance_scale=)."""
+
+    def __init__(self, *args, **kwargs):
+        kwargs.setdefault("conditioning_key", "hybrid")
+        super().__init__(*args, **kwargs)
+
+    def encode_edit_image(self, image):
+        """The c_concat of an edit: the posterior MODE of the VAE for image [B, 3, H, W] in [-1, 1], NOT multiplied by
+        scale_factor (InstructPix2Pix's encode_first_stage(img).mode()) -- the encoder and one ops.vae_gaussian_sample launch
+        without noise; with VAE tiling on, tile by tile."""
+        if self.first_stage_model is None:
+            raise MdxError("encode_edit_image: no VAE attached (first_stage_model)")
+        return self.first_stage_model.encode(image, sample=False)

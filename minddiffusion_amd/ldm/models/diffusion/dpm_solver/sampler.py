@@ -36,8 +36,8 @@ import numpy as np
 import torch
 
 from ....._lib import MdxError
-from ..guided import (GuidedModel, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent, split_conditioning,
-                      start_latent)
+from ..guided import (GuidedModel, check_guidance_rescale, check_image_guidance, check_seed_sources, check_seeds, noised_latent,
+                      split_conditioning, start_latent)
 from ..schedule import ScalarSteps, dpm_steps, per_request, pred_type, step_table
 from .dpm_solver import NoiseScheduleVP, check_rho, check_sde, solver_plan
 from .solver import PLAN_OPTIONS, SOLVER_DEFAULTS, check_max_val, run_solver_plan
@@ -94,8 +94,13 @@ class DPMSolverSampler:
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, guidance_rescale=0., t_start=None, seeds=None, order=None, skip_type=None,
                method=None, solver_type=None, predict_x0=None, thresholding=None, max_val=None, denoise_to_zero=None,
-               lower_order_final=None, t_end=None, sde_eta=None, s_noise=None, rho=None, step_noises=None, **kwargs):
-        """order, skip_type, method, solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end:
+               lower_order_final=None, t_end=None, sde_eta=None, s_noise=None, rho=None, step_noises=None,
+               image_guidance_scale=None, **kwargs):
+        """image_guidance_scale: None, or the image scale s_I of three-branch guidance (InstructPix2Pix), as PLMSSampler.sample
+        takes it: dict conditioning on both sides with a c_concat each, the batch [uu ; ui ; ci] per evaluation, the combine
+        inside the one step launch (ops.sampler_step_dual, with solver options ops.sampler_step_lin_dual).  Every solver option
+        works with it but method="adaptive"; per-request lists do not.
+        order, skip_type, method, solver_type, predict_x0, thresholding, max_val, denoise_to_zero, lower_order_final, t_end:
         the options of the reference's DPM_Solver(...).sample(...) (dpm_solver.solver_plan); sde_eta, s_noise, rho: the SDE
         update and the Karras grid (solver_plan; not in the reference); None: the sampler's default
         (SOLVER_DEFAULTS unless the constructor was given another).  With every option at SOLVER_DEFAULTS -- multistep, order 2,
@@ -137,6 +142,11 @@ class DPMSolverSampler:
                                  "score_corrector or quantize_x0")
             if len(set(per[0])) > 1 and t_start is not None:
                 raise ValueError("per-sample S with different values runs every sample's own full schedule: not with t_start")
+        if image_guidance_scale is not None and opts["method"] == "adaptive":
+            raise MdxError("DPMSolverSampler.sample: image_guidance_scale does not run with method='adaptive'")
+        image_scale = check_image_guidance("DPMSolverSampler.sample", self.model, image_guidance_scale, conditioning,
+                                           unconditional_conditioning, per, mask, x0)
+        ig = {} if image_scale is None else {"image_scale": image_scale}      # (None: every call below as it was)
         check_seed_sources(seeds, self.generator, step_noises=step_noises)
         if t_start is not None:
             t_start = self._check_t_start(t_start)
@@ -159,22 +169,22 @@ class DPMSolverSampler:
             plan = solver_plan(ns, S, t_start=t_start, **{k: opts[k] for k in PLAN_OPTIONS})
             scale = float(unconditional_guidance_scale)
             guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev,
-                                 [r["t_input"] for r in plan])
+                                 [r["t_input"] for r in plan], **ig)
             return run_solver_plan(plan, guided, img, scale, pred_type(self.model), guidance_rescale, opts["thresholding"],
-                                   opts["max_val"], callback, img_callback, seeds, self.generator, step_noises), None
+                                   opts["max_val"], callback, img_callback, seeds, self.generator, step_noises, **ig), None
         # the launches of the run (schedule.dpm_steps) behind one surface: kernel arguments, or per request the rows of a table.
         # Either way a sample's previous data prediction is read only while its own float32 c1 is non-zero.
         counts = [S] * batch_size if per is None else per[0]
         by_steps = {s: dpm_steps(ns, s, t_start) for s in sorted(set(counts))}
         if per is None:
             scale, total = float(unconditional_guidance_scale), S
-            steps, t_rows = ScalarSteps(by_steps[S], scale, guidance_rescale), [s.t_input for s in by_steps[S]]
+            steps, t_rows = ScalarSteps(by_steps[S], scale, guidance_rescale, **ig), [s.t_input for s in by_steps[S]]
         else:
             scale = per[1]
             steps, t_rows, total = step_table([by_steps[s] for s in counts], scale, per[2], not (uc is None and uc_cat is None))
             steps.upload(dev)
         # (model_wrapper :316-322 builds the [uncond; cond] batch)
-        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
+        guided = GuidedModel(self.model, batch_size, tuple(shape), cond, uc, c_cat, uc_cat, scale, dev, t_rows, **ig)
         # The data predictions ping-pong between two buffers and a table launch writes only active rows, so on the iteration a
         # sample ends its last prediction is copied into the other buffer too: whichever one img_callback is handed shows the
         # finished sample's last value.  (Samples that end with the run -- all of them, with one S -- need no copy.)
@@ -186,7 +196,8 @@ class DPMSolverSampler:
         for k in range(total):
             eps_u, eps_c = guided(img, k)
             cur, prev = x0_bufs[k & 1], x0_bufs[(k & 1) ^ 1]
-            steps.launch(k, img, eps_u, eps_c, pred, [], prev if steps.any_sigma[k] else None, None, x_next, cur)
+            mid = {} if image_scale is None else {"out_m": guided.out_m}
+            steps.launch(k, img, eps_u, eps_c, pred, [], prev if steps.any_sigma[k] else None, None, x_next, cur, **mid)
             for b in ending.get(k, ()):
                 prev[b].copy_(cur[b])
             img, x_next = x_next, img

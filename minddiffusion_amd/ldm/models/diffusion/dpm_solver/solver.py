@@ -35,13 +35,14 @@ def check_max_val(thresholding, max_val):
 
 
 def run_solver_plan(plan, guided, x, scale, pred, guidance_rescale=0., thresholding=False, max_val=1., callback=None,
-                    img_callback=None, seeds=None, generator=None, step_noises=None):
+                    img_callback=None, seeds=None, generator=None, step_noises=None, image_scale=None):
     """Run `plan` (solver_plan's records) from the latent x ([B, C, H, W] fp32, overwritten: the run's "x" buffer) with
     guided = GuidedModel(..., t_steps=[r["t_input"] for r in plan]); returns the result, which is x.  No device work in the
     loop besides the model call and the step launch; callback(i) and img_callback(model value, i) fire once per evaluation.
     The noise of a record with cn != 0 (a stochastic plan): with `seeds` (the [B] device tensor of check_seeds) drawn inside the
     step launch, stream ops.RNG_STEP, draw = the record's index -- no launch and no tensor of its own; else step_noises[index]
-    (test injection); else one torch.randn from `generator`.  A record with cn == 0 makes the launch it has always made."""
+    (test injection); else one torch.randn from `generator`.  A record with cn == 0 makes the launch it has always made.
+    image_scale (with a three-branch `guided`): every record's launch is ops.sampler_step_lin_dual on guided.out_m."""
     roles = {name for r in plan for name in (r["model"], r["base"], r["out"], r["store"])}
     bufs = {name: torch.empty_like(x) for name in sorted(roles - {"x"})}
     bufs["x"] = x
@@ -52,16 +53,22 @@ def run_solver_plan(plan, guided, x, scale, pred, guidance_rescale=0., threshold
                 ops.VALUE_X0 if x0 else ops.VALUE_EPS, r["alpha_m"], r["sigma_m"],
                 None if r["h1"] is None else bufs[r["h1"]], None if r["h2"] is None else bufs[r["h2"]], r["A"],
                 r["c0"], r["c1"], r["c2"], bufs[r["store"]], bufs[r["out"]])
+        if image_scale is not None:
+            args = args[:3] + (guided.out_m, out_c, scale, image_scale) + args[5:]
         if r["cn"] == 0.:
-            ops.sampler_step_lin(*args, thresholding=thresholding and x0, max_val=max_val)
+            if image_scale is not None:
+                ops.sampler_step_lin_dual(*args, thresholding=thresholding and x0, max_val=max_val)
+            else:
+                ops.sampler_step_lin(*args, thresholding=thresholding and x0, max_val=max_val)
         else:
             noise = None
             if seeds is None and step_noises is not None:
                 noise = torch.as_tensor(step_noises[r["draw"]]).to(device=x.device, dtype=torch.float32).contiguous()
             elif seeds is None:
                 noise = torch.randn(x.shape, device=x.device, dtype=torch.float32, generator=generator)
-            ops.sampler_step_lin_noise(*args, r["cn"], noise=noise, seeds=seeds, stream=ops.RNG_STEP, draw=r["draw"],
-                                       thresholding=thresholding and x0, max_val=max_val)
+            step = ops.sampler_step_lin_noise if image_scale is None else ops.sampler_step_lin_dual
+            step(*args, r["cn"], noise=noise, seeds=seeds, stream=ops.RNG_STEP, draw=r["draw"],
+                 thresholding=thresholding and x0, max_val=max_val)
         if callback:
             callback(i)
         if img_callback:
@@ -117,10 +124,15 @@ class WrappedModel:
 
 
 def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs=None, guidance_type="uncond", condition=None,
-                  unconditional_condition=None, guidance_scale=1., classifier_fn=None, classifier_kwargs=None):
+                  unconditional_condition=None, guidance_scale=1., classifier_fn=None, classifier_kwargs=None,
+                  image_guidance_scale=None):
     """dpm_solver.py:170-329 for what the fused path carries: model_type "noise" | "v", guidance_type "uncond" |
     "classifier-free".  model: a LatentDiffusion of this package (its NHWC fast path is used), any object with the reference's
-    apply_model(x, t_input, cond) -> eps | v NCHW, or a callable model(x, t_input, cond)."""
+    apply_model(x, t_input, cond) -> eps | v NCHW, or a callable model(x, t_input, cond).  image_guidance_scale (three-branch
+    guidance) is DPMSolverSampler.sample's: refused here."""
+    if image_guidance_scale is not None:
+        raise MdxError("model_wrapper: image_guidance_scale is not carried by model_wrapper / DPM_Solver (the ported reference "
+                       "surface has no c_concat): use DPMSolverSampler.sample(image_guidance_scale=)")
     if model_type in ("x_start", "score"):
         raise NotImplementedError(f"model_type {model_type!r}: the step launch converts a noise or a v output "
                                   f"(MDX_PRED_EPS | MDX_PRED_V) to the model value, no other")
@@ -152,10 +164,14 @@ class DPM_Solver:
 
     def sample(self, x, steps=20, t_start=None, t_end=None, order=3, skip_type="time_uniform", method="singlestep",
                lower_order_final=True, denoise_to_zero=False, solver_type="dpm_solver", atol=0.0078, rtol=0.05, callback=None,
-               img_callback=None, rho=7., sde_eta=0., s_noise=1., seeds=None, generator=None, step_noises=None):
+               img_callback=None, rho=7., sde_eta=0., s_noise=1., seeds=None, generator=None, step_noises=None,
+               image_guidance_scale=None):
         """rho (with skip_type="karras"), sde_eta, s_noise: solver_plan's options, not in the reference.  The noise of a
         stochastic run (sde_eta > 0): per sample from `seeds` (one int per sample), drawn inside the step launches; else from
         `generator` (None: torch's default); step_noises injects it for tests."""
+        if image_guidance_scale is not None:
+            raise MdxError("DPM_Solver.sample: image_guidance_scale is not carried by model_wrapper / DPM_Solver (the ported "
+                           "reference surface has no c_concat): use DPMSolverSampler.sample(image_guidance_scale=)")
         ns = self.noise_schedule
         plan = solver_plan(ns, steps, order=order, skip_type=skip_type, method=method, solver_type=solver_type,
                            predict_x0=self.predict_x0, lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,

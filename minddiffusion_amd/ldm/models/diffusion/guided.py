@@ -82,6 +82,40 @@ def check_guidance_rescale(value):
     return phi
 
 
+def check_image_guidance(what, model, image_scale, cond, uc, per, mask=None, x0=None):
+    """`image_guidance_scale` of the samplers (three-branch guidance, InstructPix2Pix): None stays None; otherwise the float,
+    after every refusal the three samplers share -- what the run needs (dict conditioning on both sides with a c_concat each,
+    a scalar guidance scale) and what it does not combine with.  per: schedule.per_request's result."""
+    if image_scale is None:
+        return None
+    from .... import distributed as D
+    from .windowed import WindowedDiffusion
+    if isinstance(image_scale, bool) or np.ndim(image_scale) != 0:
+        raise MdxError(f"{what}: image_guidance_scale is one float for the batch (per-request image scales are not built), "
+                       f"got {image_scale!r}")
+    s = float(image_scale)
+    if not np.isfinite(s):
+        raise ValueError(f"{what}: image_guidance_scale must be finite, got {image_scale!r}")
+    if per is not None:
+        raise MdxError(f"{what}: image_guidance_scale does not run with per-request lists of S, "
+                       "unconditional_guidance_scale or guidance_rescale (the step table has no middle branch)")
+    if mask is not None or x0 is not None:
+        raise MdxError(f"{what}: image_guidance_scale does not run with mask= / x0=")
+    if isinstance(model, WindowedDiffusion):
+        raise MdxError(f"{what}: image_guidance_scale does not run on a WindowedDiffusion model")
+    if getattr(model, "is_controlled", False):
+        raise MdxError(f"{what}: image_guidance_scale does not run on a ControlledDiffusion model")
+    if D.world()[1] > 1:
+        raise MdxError(f"{what}: image_guidance_scale runs on a single rank (several ranks are not built)")
+    for name, c in (("conditioning", cond), ("unconditional_conditioning", uc)):
+        if not isinstance(c, dict):
+            raise MdxError(f"{what}: image_guidance_scale needs {name} as a dict with 'c_concat' and 'c_crossattn'")
+        for k in ("c_concat", "c_crossattn"):
+            if c.get(k) is None:
+                raise MdxError(f"{what}: image_guidance_scale needs {name}['{k}']")
+    return s
+
+
 def check_seed_sources(seeds, generator=None, **injected):
     """A second source for the draws that `seeds=` covers -- the sampler's generator, or one of the test-injection keywords -- is a
     caller's mistake: ValueError."""
@@ -179,10 +213,19 @@ class GuidedModel:
     exactly 1 then goes through the combine eu + 1 * (ec - eu), which is not promised bit-equal to an unguided run).
     t_steps: the model-input timestep of every step, in loop order (the UNet's sinusoid takes float timesteps,
     util.py:111-131); per request [n_calls, B], every sample its own (a sample whose schedule has ended keeps its last one):
-    the timestep-only part is then computed once over the DISTINCT timesteps and step i gathers its [nb, emb_total] rows."""
+    the timestep-only part is then computed once over the DISTINCT timesteps and step i gathers its [nb, emb_total] rows.
 
-    def __init__(self, model, b, shape, cond, uc, c_cat, uc_cat, scale, dev, t_steps):
+    image_scale: not None = three-branch guidance (InstructPix2Pix): the batch is [uu ; ui ; ci] = (uc, uc_cat), (uc, c_cat),
+    (cond, c_cat), always all three whatever the scales are, and ``guided.out_m`` is the middle third of the output of the last
+    call (None in every other run) -- the step launch combines out_u + image_scale (out_m - out_u) + scale (out_c - out_m)."""
+
+    def __init__(self, model, b, shape, cond, uc, c_cat, uc_cat, scale, dev, t_steps, image_scale=None):
         self.model, self.b, self.cx = model, b, shape[0]
+        self.out_m = None
+        self.dual = image_scale is not None
+        if self.dual:
+            self._init_dual(b, shape, cond, uc, c_cat, uc_cat, dev, t_steps)
+            return
         self.use_cfg = use_cfg(uc, uc_cat, scale)
         nb = self.nb = 2 * b if self.use_cfg else b
         if cond is None:
@@ -200,6 +243,33 @@ class GuidedModel:
                     self.x_in[:b, self.cx:] = cc if uc_cat is None else uc_cat.to(device=dev, dtype=torch.float32)
         # the two halves of a guidance batch are the same UNet input unless the unconditional branch has its own c_concat
         self.same_halves = self.use_cfg and self.c_in is not None and (c_cat is None or uc_cat is None)
+        self._init_times(t_steps, dev)
+
+    def _init_dual(self, b, shape, cond, uc, c_cat, uc_cat, dev, t_steps):
+        """The three-branch batch, made once: x_in [3B, cx + ccat, h, w] with the c_concat channels [uc_cat ; c_cat ; c_cat],
+        the context [uc ; uc ; cond], the timestep rows three times."""
+        missing = [name for name, v in (("a conditioning c_crossattn", cond), ("an unconditional c_crossattn", uc),
+                                        ("a c_concat", c_cat), ("an unconditional c_concat", uc_cat)) if v is None]
+        if missing:
+            raise MdxError(f"image guidance (image_scale) needs {' and '.join(missing)}")
+        if np.ndim(t_steps) == 2:
+            raise MdxError("image guidance (image_scale) does not take per-request timesteps [n_calls, B]")
+        self.use_cfg = True
+        nb = self.nb = 3 * b
+        self.c_in = torch.cat([uc.to(cond.dtype), uc.to(cond.dtype), cond], 0).contiguous()
+        cc = c_cat.to(device=dev, dtype=torch.float32)
+        ucc = uc_cat.to(device=dev, dtype=torch.float32)
+        if tuple(ucc.shape) != tuple(cc.shape):
+            raise MdxError(f"image guidance: the unconditional c_concat {tuple(ucc.shape)} is not the c_concat's {tuple(cc.shape)}")
+        self.x_in = torch.empty((nb, self.cx + int(cc.shape[1])) + tuple(shape[1:]), device=dev, dtype=torch.float32)
+        self.x_in[:b, self.cx:] = ucc                                # batch = [uu ; ui ; ci]
+        self.x_in[b:2 * b, self.cx:] = cc
+        self.x_in[2 * b:, self.cx:] = cc
+        self.same_halves = False                                     # the branches differ in x
+        self._init_times(t_steps, dev)
+
+    def _init_times(self, t_steps, dev):
+        model, nb = self.model, self.nb
         # (a fresh array: the flipped view of a ONE-step grid still counts as contiguous and keeps its negative stride)
         t_host = np.array(t_steps, dtype=np.float32)
         self.temb_rows = None
@@ -249,6 +319,13 @@ class GuidedModel:
 
     def __call__(self, x, i):
         b, cx, x_in = self.b, self.cx, self.x_in
+        if self.dual:
+            x_in[:b, :cx].copy_(x)
+            x_in[b:2 * b, :cx].copy_(x)
+            x_in[2 * b:, :cx].copy_(x)
+            out = self._eps_nhwc(x_in, i)
+            self.out_m = out[b:2 * b]
+            return out[:b], out[2 * b:]
         if self.use_cfg:
             x_in[:b, :cx].copy_(x)
             x_in[b:, :cx].copy_(x)

@@ -33,8 +33,8 @@ import torch
 from .... import ops
 from ...._lib import MdxError
 from ...modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps
-from .guided import (GuidedModel, _Draws, _first_tensor, check_guidance_rescale, check_seed_sources, check_seeds, noised_latent,
-                     split_conditioning, start_latent)
+from .guided import (GuidedModel, _Draws, _first_tensor, check_guidance_rescale, check_image_guidance, check_seed_sources,
+                     check_seeds, noised_latent, split_conditioning, start_latent)
 from .schedule import ScalarSteps, ddim_steps, per_request, pred_type, step_table
 
 
@@ -83,8 +83,14 @@ class _SamplerBase:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., seeds=None, **kwargs):
-        """seeds: `batch_size` ints, one per sample -- every draw of sample b (x_T, the eta > 0 step noise, the mask blend)
+               unconditional_guidance_scale=1., unconditional_conditioning=None, guidance_rescale=0., seeds=None,
+               image_guidance_scale=None, **kwargs):
+        """image_guidance_scale: None, or the image scale s_I of three-branch guidance (InstructPix2Pix) -- conditioning and
+        unconditional_conditioning are then dicts with a c_concat each (the image latent and its zero), every model evaluation
+        runs the batch [uu ; ui ; ci] and the step launch combines e_uu + s_I (e_ui - e_uu) + s_T (e_ci - e_ui), s_T =
+        unconditional_guidance_scale, in the one launch (ops.sampler_step_dual).  Not with per-request lists, mask / x0, windowed
+        or controlled models, several ranks.
+        seeds: `batch_size` ints, one per sample -- every draw of sample b (x_T, the eta > 0 step noise, the mask blend)
         then depends on seeds[b] alone and not on the batch around it (ops.randn_seeded); None: the sampler's generator.
         Per request: S, unconditional_guidance_scale and guidance_rescale each take a scalar or `batch_size` values (list,
         tuple, 1-d array or tensor).  With any sequence the run reads its step scalars from a StepTable (one
@@ -99,6 +105,8 @@ class _SamplerBase:
         per = per_request(S, unconditional_guidance_scale, guidance_rescale, batch_size)
         if per is None:
             guidance_rescale = check_guidance_rescale(guidance_rescale)
+        check_image_guidance(f"{type(self).__name__}.sample", self.model, image_guidance_scale, conditioning,
+                             unconditional_conditioning, per, mask, x0)       # (an S list is seen here only)
         if conditioning is not None:
             cbs = _first_tensor(conditioning).shape[0]
             if cbs != batch_size:
@@ -134,7 +142,7 @@ class _SamplerBase:
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
                                   blend_noises=kwargs.get("blend_noises"), guidance_rescale=guidance_rescale, seeds=seeds,
-                                  grids=grids)
+                                  grids=grids, image_guidance_scale=image_guidance_scale)
 
     # ---- img2img: upstream LDM's DDIMSampler.stochastic_encode / decode (neither reference tree has them).
     # t_enc / t_start count the model evaluations that REMAIN (1 .. S; PLMS spends one more on its first step): the partial run
@@ -170,11 +178,12 @@ class _SamplerBase:
 
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
                use_original_steps=False, callback=None, img_callback=None, mask=None, x0=None, guidance_rescale=0.,
-               log_every_t=100, seeds=None, **test_injection_kwargs):
+               log_every_t=100, seeds=None, image_guidance_scale=None, **test_injection_kwargs):
         """The last t_start steps of the schedule make_schedule() set up (its eta included), from x_latent =
         stochastic_encode(., t_start): plms_sampling's loop on ts[:t_start].  t_start == S is sample(S, x_T=x_latent).
         mask / x0: 1 = keep x0 (the init latent), blended every step by one in-place ops.q_sample launch.
         seeds: per-sample seeds of the step and blend draws, as sample() takes them.
+        image_guidance_scale: three-branch guidance, as sample() takes it.
         test_injection_kwargs: step_noises / blend_noises / dropout_masks, as sample() takes them.
         Returns (samples, intermediates)."""
         self._need_schedule("decode")
@@ -188,7 +197,7 @@ class _SamplerBase:
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=False,
                                   guidance_rescale=guidance_rescale, t_start=self._check_t_start(t_start, grid), seeds=seeds,
-                                  **test_injection_kwargs)
+                                  image_guidance_scale=image_guidance_scale, **test_injection_kwargs)
 
     # ---- which timesteps, and which tables `index` selects from (plms.py:134-142, 205-208)
     def time_grid(self, ddim_use_original_steps, timesteps, t_start):
@@ -233,7 +242,8 @@ class _SamplerBase:
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, verbose=True, blend_noises=None,
-                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None, grids=None):
+                      dropout_masks=None, step_noises=None, guidance_rescale=0., t_start=None, seeds=None, grids=None,
+                      image_guidance_scale=None):
         """t_start (decode() passes it, nothing else does): run only the LAST t_start steps of the grid -- grid indices
         t_start - 1 ... 0, ts[:t_start] -- from x_T, a latent at the noise level of index t_start - 1.  In that mode the
         mask / x0 blend of every step is one ops.q_sample launch, in place.
@@ -248,6 +258,9 @@ class _SamplerBase:
         elif score_corrector is not None or quantize_denoised:
             raise ValueError("per-sample guidance scale / rescale / steps run inside the fused step launch: not with "
                              "score_corrector or quantize_x0")
+        image_scale = check_image_guidance(f"{type(self).__name__}.sample", self.model, image_guidance_scale, cond,
+                                           unconditional_conditioning, per, mask, x0)
+        ig = {} if image_scale is None else {"image_scale": image_scale}      # (None: every call below as it was)
         check_seed_sources(seeds, self.generator, step_noises=step_noises, blend_noises=blend_noises, dropout_masks=dropout_masks)
         self._check_options(mask, x0, score_corrector, quantize_denoised, noise_dropout)
         corrector_kwargs = corrector_kwargs or {}
@@ -273,7 +286,7 @@ class _SamplerBase:
         # every scalar of every launch (schedule.ddim_steps) behind one surface: kernel arguments, or per request the rows of a
         # table.  second_row: the row of the guided model's timesteps that PLMS' second evaluation reads
         if per is None:
-            steps, t_rows = ScalarSteps(ddim_steps(self, grid, self.multistep), scale, guidance_rescale), time_range
+            steps, t_rows = ScalarSteps(ddim_steps(self, grid, self.multistep), scale, guidance_rescale, **ig), time_range
             second_row = min(1, total_steps - 1)
         else:
             plans = [ddim_steps(self, g, self.multistep) for g in grids or [grid] * b]
@@ -281,7 +294,7 @@ class _SamplerBase:
                                                     second_call_row=self.multistep)
             steps.upload(dev)
             second_row = total_steps                                  # the one step_table appended after the loop's
-        guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, t_rows)
+        guided = GuidedModel(self.model, b, tuple(shape[1:]), cond, uc, c_cat, uc_cat, scale, dev, t_rows, **ig)
         draws = _Draws(seeds, self.generator, dev, shape, step_noises, dropout_masks, blend_noises, temperature, noise_dropout)
 
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
@@ -305,13 +318,16 @@ class _SamplerBase:
             xm: the image the model output was evaluated at when not x (what a score corrector is handed, plms.py:201, and where
             a v output is converted to eps).  The two hooks are scalar-only: they read steps.plan."""
             k = next(calls)
+            mid = {} if image_scale is None else {"out_m": guided.out_m}      # the middle output of the evaluation just made
             if score_corrector is not None:
                 # e_t leaves the fused kernel (pass 1: CFG combine only -- the rescale belongs to the combine that produces
                 # e_t, so to this pass), goes through the caller's modify_score, and re-enters as a single NHWC fp16 model
                 # output (pass 2: multistep mix + update)
                 # (a corrector implies an eps model -- _check_options -- so hook_e holds eps and PRED_EPS is the whole story)
                 ops.sampler_update(x, eps_u, eps_c, scale, ops.PRED_EPS, [], (1., 0., 0., 0.),
-                                   (1., 0., 1., 0., 0., None, hook_e, hook_x, None), guidance_rescale)
+                                   (1., 0., 1., 0., 0., None, hook_e, hook_x, None), guidance_rescale,
+                                   **({} if not mid else dict(mid, mid_scale=image_scale)))
+                mid = {}
                 tvec = torch.full((b,), int(steps.plan[k].t_input), device=dev, dtype=torch.long)
                 e_mod = score_corrector.modify_score(self.model, hook_e, x if xm is None else xm, tvec, cond,
                                                      **corrector_kwargs)
@@ -323,7 +339,7 @@ class _SamplerBase:
             noise = draws.step() if steps.any_sigma[k] else None
             if quantize_denoised and p_out is None:
                 p_out = hook_p
-            steps.launch(k, x, eps_u, eps_c, pred, olds, noise, e_out, x_out, p_out, xm)
+            steps.launch(k, x, eps_u, eps_c, pred, olds, noise, e_out, x_out, p_out, xm, **mid)
             if quantize_denoised:
                 # pred_x0, _, *_ = first_stage_model.quantize(pred_x0) (plms.py:218-219); x_prev is linear in pred_x0
                 q = self.model.first_stage_model.quantize(p_out)[0]

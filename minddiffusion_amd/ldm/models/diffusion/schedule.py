@@ -80,17 +80,21 @@ def dpm_steps(ns, steps, t_start=None):
 
 class ScalarSteps:
     """A run of one plan for the whole batch, its scalars plain kernel arguments: the surface of an uploaded StepTable
-    (any_sigma, launch) over ops.sampler_update, which picks the entry.  No device work of its own."""
+    (any_sigma, launch) over ops.sampler_update, which picks the entry.  No device work of its own.  image_scale: the middle
+    scale of three-branch guidance; launch() then takes the middle output out_m."""
 
-    def __init__(self, plan, scale, guidance_rescale):
-        self.plan, self.scale, self.guidance_rescale = plan, scale, guidance_rescale
+    def __init__(self, plan, scale, guidance_rescale, image_scale=None):
+        self.plan, self.scale, self.guidance_rescale, self.image_scale = plan, scale, guidance_rescale, image_scale
         self.any_sigma = [float(s.update[4]) != 0.0 for s in plan]      # the float32, as a table row decides it
 
-    def launch(self, k, x, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0, x_model=None):
+    def launch(self, k, x, out_u, out_c, pred_type, olds, noise, e_t_out, x_prev, pred_x0, x_model=None, out_m=None):
         """Call k of the run: one ops.sampler_update launch with plan[k]'s scalars."""
         s = self.plan[k]
+        if out_m is not None and self.image_scale is None:
+            raise MdxError("ScalarSteps: a middle output out_m without an image_scale")
+        mid = {} if out_m is None else {"out_m": out_m, "mid_scale": self.image_scale}      # (None: today's call, as it was)
         ops.sampler_update(x, out_u, out_c, self.scale, pred_type, olds, s.coef, s.update + (noise, e_t_out, x_prev, pred_x0),
-                           self.guidance_rescale, x_model, *s.model_point)
+                           self.guidance_rescale, x_model, *s.model_point, **mid)
 
 
 # ---- per-request parameters: `scale`, `guidance_rescale` and `steps` as one value per sample of the batch

@@ -27,7 +27,7 @@ from .dpm_solver.dpm_solver import NoiseScheduleVP
 from .schedule import check_strength, ddim_steps, dpm_partial_start, dpm_steps, per_request, pred_type, step_table
 
 SAMPLERS = ("ddim", "dpm_solver")
-_REFUSED_KEYWORDS = ("mask", "x0", "score_corrector", "quantize_x0")
+_REFUSED_KEYWORDS = ("mask", "x0", "score_corrector", "quantize_x0", "image_guidance_scale", "image_scale")
 
 
 def request_rows(model, sampler, steps, scale, guidance_rescale=0.0, eta=0.0, t_enc=None):
@@ -88,7 +88,10 @@ def check_request(sampler, max_steps, steps, scale, guidance_rescale, eta, seed,
             raise ValueError(f"submit: {k} is not available in a session: "
                              + ("an img2img request takes init_latent= / init_image= (with strength=) and, for the blend, "
                                 "keep_mask="
-                                if k in ("mask", "x0") else "it leaves the fused step launch"))
+                                if k in ("mask", "x0") else
+                                "three-branch image guidance is not served in sessions (a slot has no c_concat and the step rows "
+                                "no middle scale yet)"
+                                if k in ("image_guidance_scale", "image_scale") else "it leaves the fused step launch"))
     per_request([steps], [scale], [guidance_rescale], 1)                # an int >= 1, a finite scale, phi in [0, 1]
     steps, scale, guidance_rescale, eta = int(steps), float(scale), float(guidance_rescale), float(eta)
     if steps > max_steps:

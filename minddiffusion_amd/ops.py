@@ -792,16 +792,49 @@ def sampler_step_rescale(x, x_model, out_u, out_c, out_ld, cfg_scale, pred_type,
         B, C, H, W, _stream()), "mdx_sampler_step_rescale_f32")
 
 
+def _chk_out_m(fn, out_m, out_c, mid_scale):
+    """The middle branch of three-branch guidance: out_c's dtype, shape and ld, and a scale to go with it."""
+    _chk(out_m, f16, "out_m")
+    if out_c is None or tuple(out_m.shape) != tuple(out_c.shape):
+        raise _lib.MdxError(f"out_m: expected out_c's shape {None if out_c is None else tuple(out_c.shape)}, "
+                            f"got {tuple(out_m.shape)}")
+    if mid_scale is None:
+        raise _lib.MdxError(f"{fn}: out_m needs a mid_scale")
+
+
+def sampler_step_dual(x, x_model, out_u, out_m, out_c, out_ld, cfg_scale, mid_scale, pred_type, sqrt_at_model,
+                      sqrt_one_minus_at_model, olds, coef, sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise,
+                      e_t_out, x_prev, pred_x0, guidance_rescale=0., factor_out=None):
+    """sampler_step_rescale with three-branch guidance (mdx_sampler_step_dual_f32): the combined model output is
+    out_u + mid_scale (out_m - out_u) + cfg_scale (out_c - out_m), in the same ONE launch; the rescale pulls it to
+    std(out_c).  out_m: the middle output (empty text, image latent), with out_c's dtype, shape and ld; None is
+    sampler_step_rescale, launch for launch."""
+    B, C, H, W = x.shape
+    o, c4 = _step_args(B, olds, coef, factor_out)
+    if out_m is not None:
+        _chk_out_m("sampler_step_dual", out_m, out_c, mid_scale)
+    _lib.check(_lib.load().mdx_sampler_step_dual_f32(
+        _ptr(x), _ptr(x_model), _ptr(out_u), _ptr(out_c), int(out_ld), float(cfg_scale), int(pred_type),
+        float(sqrt_at_model), float(sqrt_one_minus_at_model), *o, c4, float(sqrt_at), float(sqrt_one_minus_at),
+        float(sqrt_a_prev), float(dir_coef), float(sigma), _ptr(noise), _ptr(e_t_out), _ptr(x_prev), _ptr(pred_x0), float(guidance_rescale), _ptr(factor_out),
+        _ptr(out_m), 0. if mid_scale is None else float(mid_scale), B, C, H, W, _stream()), "mdx_sampler_step_dual_f32")
+
+
 def sampler_update(x, out_u, out_c, cfg_scale, pred_type, olds, coef, update, guidance_rescale=0., x_model=None,
-                   sqrt_at_model=1., sqrt_one_minus_at_model=0.):
+                   sqrt_at_model=1., sqrt_one_minus_at_model=0., out_m=None, mid_scale=None):
     """The one fused step launch of every LDM sampler, through the entry that does no more than the step needs: the rescale
     entry iff guidance_rescale != 0 and there is an unconditional half to combine, else the pred entry iff the model output
     is v, else the plain entry (bit-identical where they overlap, include/mdx.h).  out_u / out_c: the halves of the model
     output (out_u None: no guidance); (x_model, sqrt_at_model, sqrt_one_minus_at_model): the point the model was evaluated
     at, read for a v output only (x_model None = x); update: (sqrt_at, sqrt_one_minus_at, sqrt_a_prev, dir_coef, sigma, noise,
-    e_t_out, x_prev, pred_x0) of sampler_step."""
+    e_t_out, x_prev, pred_x0) of sampler_step.  out_m (with mid_scale): the middle output of three-branch guidance -- only then
+    the dual entry, which carries rescale and v itself."""
     v = pred_type == PRED_V
-    if guidance_rescale != 0. and out_u is not None:
+    if out_m is not None:
+        sampler_step_dual(x, x_model, out_u, out_m, out_c, out_c.shape[-1], cfg_scale, mid_scale, pred_type,
+                          sqrt_at_model if v else 1., sqrt_one_minus_at_model if v else 0., olds, coef, *update,
+                          guidance_rescale=guidance_rescale)
+    elif guidance_rescale != 0. and out_u is not None:
         sampler_step_rescale(x, x_model, out_u, out_c, out_c.shape[-1], cfg_scale, pred_type, sqrt_at_model if v else 1.,
                              sqrt_one_minus_at_model if v else 0., olds, coef, *update, guidance_rescale)
     elif v:
@@ -881,6 +914,22 @@ def sampler_step_lin(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidan
                         factor_out), *x_base.shape, _stream()), "mdx_sampler_step_lin_f32")
 
 
+def _step_lin_noise_args(fn, x_base, noise, seeds, stream, draw):
+    """The checks of the noise sources of a stochastic step launch; returns (noise, seeds, stream, draw) as the library takes them."""
+    B = int(x_base.shape[0])
+    _chk(noise, f32, "noise")
+    if noise is not None and tuple(noise.shape) != tuple(x_base.shape):
+        raise _lib.MdxError(f"noise: expected {tuple(x_base.shape)}, got {tuple(noise.shape)}")
+    if seeds is not None:
+        if not (isinstance(seeds, torch.Tensor) and tuple(seeds.shape) == (B,)):
+            raise _lib.MdxError(f"{fn}: seeds must be a [{B}] int64 device tensor (ops.seeds_tensor)")
+        _chk(seeds, torch.int64, "seeds")
+    stream = RNG_STEP if stream is None else int(stream)
+    if not (0 <= stream < (1 << 31) and 0 <= int(draw) < (1 << 32)):
+        raise _lib.MdxError(f"{fn}: stream must be in [0, 2^31) and draw in [0, 2^32), got {stream!r}, {draw!r}")
+    return _ptr(noise), _ptr(seeds), stream, int(draw)
+
+
 def sampler_step_lin_noise(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
                            h1, h2, A, c0, c1, c2, model_out, x_out, cn, noise=None, seeds=None, stream=None, draw=0,
                            thresholding=False, max_val=1., model_pre_out=None, thr_out=None, factor_out=None):
@@ -892,19 +941,27 @@ def sampler_step_lin_noise(x_base, x_model, out_u, out_c, cfg_scale, pred_type, 
     args = _step_lin_args("sampler_step_lin_noise", x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale,
                           value_type, alpha_m, sigma_m, h1, h2, A, c0, c1, c2, model_out, x_out, thresholding, max_val,
                           model_pre_out, thr_out, factor_out)
-    B = int(x_base.shape[0])
-    _chk(noise, f32, "noise")
-    if noise is not None and tuple(noise.shape) != tuple(x_base.shape):
-        raise _lib.MdxError(f"noise: expected {tuple(x_base.shape)}, got {tuple(noise.shape)}")
-    if seeds is not None:
-        if not (isinstance(seeds, torch.Tensor) and tuple(seeds.shape) == (B,)):
-            raise _lib.MdxError(f"sampler_step_lin_noise: seeds must be a [{B}] int64 device tensor (ops.seeds_tensor)")
-        _chk(seeds, torch.int64, "seeds")
-    stream = RNG_STEP if stream is None else int(stream)
-    if not (0 <= stream < (1 << 31) and 0 <= int(draw) < (1 << 32)):
-        raise _lib.MdxError(f"sampler_step_lin_noise: stream must be in [0, 2^31) and draw in [0, 2^32), got {stream!r}, {draw!r}")
-    _lib.check(_lib.load().mdx_sampler_step_lin_noise_f32(*args, float(cn), _ptr(noise), _ptr(seeds), stream, int(draw),
-                                                          *x_base.shape, _stream()), "mdx_sampler_step_lin_noise_f32")
+    nz = _step_lin_noise_args("sampler_step_lin_noise", x_base, noise, seeds, stream, draw)
+    _lib.check(_lib.load().mdx_sampler_step_lin_noise_f32(*args, float(cn), *nz, *x_base.shape, _stream()),
+               "mdx_sampler_step_lin_noise_f32")
+
+
+def sampler_step_lin_dual(x_base, x_model, out_u, out_m, out_c, cfg_scale, mid_scale, pred_type, guidance_rescale, value_type,
+                          alpha_m, sigma_m, h1, h2, A, c0, c1, c2, model_out, x_out, cn=0., noise=None, seeds=None, stream=None,
+                          draw=0, thresholding=False, max_val=1., model_pre_out=None, thr_out=None, factor_out=None):
+    """sampler_step_lin_noise with three-branch guidance (mdx_sampler_step_lin_dual_f32): step 1 is
+    out_u + mid_scale (out_m - out_u) + cfg_scale (out_c - out_m), everything after it unchanged, ONE launch.  out_m: the
+    middle output (empty text, image latent), with out_c's dtype, shape and ld; it may overlap no output.  None is
+    sampler_step_lin_noise, launch for launch."""
+    args = _step_lin_args("sampler_step_lin_dual", x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale,
+                          value_type, alpha_m, sigma_m, h1, h2, A, c0, c1, c2, model_out, x_out, thresholding, max_val,
+                          model_pre_out, thr_out, factor_out)
+    nz = _step_lin_noise_args("sampler_step_lin_dual", x_base, noise, seeds, stream, draw)
+    if out_m is not None:
+        _chk_out_m("sampler_step_lin_dual", out_m, out_c, mid_scale)
+    _lib.check(_lib.load().mdx_sampler_step_lin_dual_f32(*args, float(cn), *nz, _ptr(out_m),
+                                                         0. if mid_scale is None else float(mid_scale), *x_base.shape,
+                                                         _stream()), "mdx_sampler_step_lin_dual_f32")
 
 
 # ---- sampling sessions (include/mdx.h, "slots"): the samples of a batch are slots that requests enter and leave

@@ -408,6 +408,69 @@ class DiffusionPipeline:
             samples = D.gather_latents(samples)
         return samples
 
+    # ---- InstructPix2Pix editing (Brooks et al. 2023; not in the reference): "change this picture as the sentence says"
+    def edit(self, image, prompts=None, c=None, uc=None, steps=50, scale=7.5, image_scale=1.5, eta=0.0, seed=42, seeds=None,
+             x_T=None, guidance_rescale=0.0, output="float", decode=True, callback=None, img_callback=None):
+        """Edit `image` as the instruction (prompts, or c / uc) says, on an 8-channel hybrid model (LatentEditDiffusion).
+
+        image [B | 1, 3, H, W] in [-1, 1], H and W multiples of 8; a batch-1 image is repeated to the prompt batch.  Every model
+        evaluation runs three branches -- (empty text, zero image latent), (empty text, image latent), (instruction, image
+        latent) -- and the step launch combines them, e_uu + image_scale (e_ui - e_uu) + scale (e_ci - e_ui): `scale` pulls
+        towards the instruction, `image_scale` towards the input picture.  c_concat = model.encode_edit_image(image), the
+        posterior mode, unscaled; its unconditional counterpart is zeros.  x_T, seed / seeds, eta and guidance_rescale as in
+        __call__ (scale, image_scale, steps and guidance_rescale are scalars here).  Single rank; not on a windowed, controlled
+        or hires-derived pipeline.  decode False: the final latent.  Otherwise the VAE decoder (tile by tile with VAE tiling
+        on, as the encode): output "float" [B, 3, H, W] in [0, 1], "uint8" [B, H, W, 3]."""
+        what = "DiffusionPipeline.edit"
+        if self._windowed:
+            raise MdxError(f"{what}: not on a windowed pipeline (windowed edits are not built)")
+        self._refuse_controlled("edit")
+        if getattr(self, "_hires_derived", False):
+            raise MdxError(f"{what}: not on a hires-derived pipeline (hires edits are not built)")
+        if D.world()[1] > 1:
+            raise MdxError(f"{what}: runs on a single rank (the sharded form is not built)")
+        if output not in ("float", "uint8"):
+            raise ValueError(f"{what}: output must be 'float' or 'uint8', got {output!r}")
+        key = getattr(getattr(self.model, "model", None), "conditioning_key", "crossattn")
+        cin = getattr(getattr(self.model, "unet", None), "in_channels", None)
+        if key != "hybrid" or cin != 8 or not hasattr(self.model, "encode_edit_image"):
+            raise MdxError(f"{what}: needs an InstructPix2Pix model -- 8 input channels under conditioning_key 'hybrid' "
+                           f"(LatentEditDiffusion, configs.WUKONG_EDIT_UNET); this one has {cin} input channels under {key!r}")
+        for name, v in (("steps", steps), ("scale", scale), ("image_scale", image_scale), ("guidance_rescale", guidance_rescale)):
+            if as_sequence(v) is not None:
+                raise MdxError(f"{what}: {name} is one value for the batch (per-request lists do not run with image guidance)")
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if not (isinstance(image, torch.Tensor) and image.dim() == 4 and image.shape[1] == 3):
+            raise MdxError(f"{what}: image must be a tensor [B | 1, 3, H, W] in [-1, 1]")
+        H, W = int(image.shape[2]), int(image.shape[3])
+        if H % 8 or W % 8 or H < 8 or W < 8:
+            raise MdxError(f"{what}: the image's H and W must be positive multiples of 8, got {H} x {W}")
+        c, uc = self._encoded(prompts, c, uc)
+        if uc is None:
+            raise MdxError(f"{what}: needs the unconditional context uc (the empty prompt's encoding) with c")
+        B = int(c.shape[0])
+        if int(image.shape[0]) not in (1, B):
+            raise MdxError(f"{what}: {int(image.shape[0])} images for a batch of {B} (1 or the batch)")
+        seeds = self.check_seeds(seeds, B)
+        c, uc = self._on_device(c, uc, B)
+        image = image.to(device=self.device, dtype=torch.float32)
+        c_cat = self.model.encode_edit_image(image.contiguous())      # (a batch-1 image is encoded once)
+        if c_cat.shape[0] != B:
+            c_cat = c_cat.expand(B, -1, -1, -1).contiguous()
+        lat = tuple(c_cat.shape)
+        x_T = self._draw(x_T, seeds, ops.RNG_X_T, list(lat), seed)
+        cond = {"c_concat": c_cat, "c_crossattn": c}
+        uc_full = {"c_concat": torch.zeros_like(c_cat), "c_crossattn": uc}
+        samples = self.sampler.sample(S=steps, conditioning=cond, batch_size=B, shape=list(lat[1:]), verbose=False, eta=eta,
+                                      x_T=x_T.to(self.device), unconditional_guidance_scale=scale,
+                                      unconditional_conditioning=uc_full, callback=callback, img_callback=img_callback,
+                                      image_guidance_scale=image_scale, **self._sampler_kw(guidance_rescale, seeds))[0]
+        if not decode:
+            return samples
+        if output == "float":
+            return self._decoded(samples)
+        return ops.inpaint_composite(self._decode_latent(samples).to(torch.float32).contiguous(), None, None, output="uint8")
+
     # ---- large canvases (ldm/models/diffusion/windowed.py): the UNet evaluated in overlapping windows of the trained size
     def windowed(self, window=512, stride=None, weights=None, max_unet_batch=16, wrap_x=False, seam_pad=64):
         """A new DiffusionPipeline on WindowedDiffusion(self.model, ...): the same sampler kind and device, all weights
@@ -579,6 +642,7 @@ class DiffusionPipeline:
         if self._windowed:
             if "inner" not in kept:
                 kept["inner"] = DiffusionPipeline(self.model.inner, self._session_sampler(), self.device, solver=self._solver())
+                kept["inner"]._hires_derived = True
             first = kept["inner"]
         if second is None:
             if (H, W) == base or self._windowed:
@@ -586,6 +650,7 @@ class DiffusionPipeline:
             else:
                 if base not in kept:
                     kept[base] = self.windowed(window=base)
+                    kept[base]._hires_derived = True
                 second = kept[base]
         return first, second
 
