@@ -701,6 +701,39 @@ int mdx_sampler_step_lin_dual_f32(const float* x_base, const float* x_model, con
                                   const unsigned long long* seeds, unsigned stream, unsigned draw, const void* out_m,
                                   float mid_scale, int B, int C, int H, int W, mdx_stream_t s);
 
+/* ---- the step launch of UniPC (Zhao et al. 2023, the multistep predictor-corrector; uni_pc.unipc_plan folds the paper's
+ * difference terms D_j into the coefficients): after one model evaluation, the CORRECTED latent at the evaluation's time and the
+ * PREDICTED latent at the next time -- the next model input, built from the corrected one -- in ONE launch.
+ * Every argument up to max_val is mdx_sampler_step_lin_f32's, and steps 1-6 (CFG combine, guidance rescale, v -> eps, data or
+ * noise prediction, dynamic thresholding, model_out = val) are that entry's, statement for statement.  Then, per element:
+ *   7. xc = Ac * x_base + d0 * val + d1 * h1 + d2 * h2 + d3 * h3      has_corrector != 0: step 7 of the lin entry on
+ *                                                                     (Ac, x_base, d0, d1 h1, d2 h2), then one fma with d3 h3
+ *      xc = x_model                                                   has_corrector == 0: the bits copied (Ac, d0 .. d3 not read)
+ *      x_corr_out = xc
+ *   8. xp = Ap * xc + e0 * val + e1 * h1 + e2 * h2                    step 7 of the lin entry on (Ap, xc as stored, e0, e1 h1, e2 h2)
+ *      x_pred_out = xp
+ * h1, h2, h3: the model values of the three evaluations before this one, newest first (NCHW fp32).  A term whose coefficient
+ * is exactly 0 is SKIPPED, not multiplied; a history neither form has a coefficient for is not read and may be NULL or hold
+ * anything, and so may x_base with has_corrector == 0 or Ac == 0.
+ * So has_corrector == 0 gives, in model_out, x_pred_out, thr_out and factor_out, the bits of mdx_sampler_step_lin_f32 on
+ * (x_base = x_model, A = Ap, c = e), and d3 == 0 gives, in model_out, x_corr_out, thr_out and factor_out, its bits on
+ * (x_base, A = Ac, c = d0 .. d2).
+ * Outputs: model_out, x_corr_out, x_pred_out (NCHW fp32, required); model_pre_out, thr_out, factor_out as the lin entry has
+ * them.  Launch forms by the lin entry's rule: SPREAD without rescale and thresholding, else OWNED (one 1024-thread workgroup
+ * per sample, the lin entry's statistics pass and radix select; a thresholded value waits in model_out between the passes).
+ * Every form reads each input once and makes one pass over the latents.
+ * Aliasing: x_corr_out may be x_base and x_pred_out may be x_model, element for element (the same pointer).  Nothing else may
+ * overlap: no output with another output (x_corr_out and x_pred_out included), no output with an input that is read.
+ * Refused before any launch (MDX_E_INVALID): everything mdx_sampler_step_lin_f32 refuses (x_base may be NULL here without a
+ * corrector; x_corr_out and x_pred_out take x_out's place); a non-zero d1 / e1, d2 / e2 or d3 with a NULL h1, h2 or h3;
+ * has_corrector with a NULL x_base; an overlap other than the two allowed aliases. */
+int mdx_sampler_step_pc_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c, int out_ld,
+                            float cfg_scale, int pred_type, float guidance_rescale, int value_type, float alpha_m,
+                            float sigma_m, int thresholding, float max_val, const float* h1, const float* h2, const float* h3,
+                            int has_corrector, float Ac, float d0, float d1, float d2, float d3, float Ap, float e0, float e1,
+                            float e2, float* model_out, float* x_corr_out, float* x_pred_out, float* model_pre_out,
+                            float* thr_out, float* factor_out, int B, int C, int H, int W, mdx_stream_t s);
+
 /* ---- GLIDE (Taichu-GLIDE/model/glide_text2im) specifics --------------------------------------------------
  * AvgPool2d(2,2) / ResizeNearestNeighbor x2 of a ResBlock's skip path (unet.py:46-49,74,180-185); NHWC fp16. */
 int mdx_avgpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, mdx_stream_t s);

@@ -179,6 +179,10 @@ SIGNATURES = {
                                               c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                               c_void_p, c_uint, c_uint, c_void_p, c_float, c_int, c_int, c_int, c_int,
                                               c_void_p]),
+    "mdx_sampler_step_pc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_float, c_int,
+                                        c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
+                                        c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_avgpool2x2_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_upsample_nearest2x_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mdx_glide_text_embed_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

@@ -1,5 +1,6 @@
 // The fused sampler step family and its session helpers: the eps/PLMS step (scalar, guidance-rescale, table and slot
-// entries), the DPM-Solver linear step (with and without noise), and the per-slot row gather.
+// entries), the DPM-Solver linear step (with and without noise), the UniPC step (corrector and next predictor), and the
+// per-slot row gather.
 //
 // The family's promise is that every launch form gives the same bits where the forms overlap: the scalar entry, a table row,
 // a slot row, a phi == 0 row of a rescaling launch, cn == 0 of the noise entry, seeded and tensor noise.  THE SOURCE FIXES THE
@@ -832,6 +833,171 @@ __global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_lin_owned_kernel
     lin_owned_values<PRED, VALUE, false, NOISE>(p, n, mid, f, b);
 }
 
+// ------------------------------------------------------------------ the UniPC step launch (mdx_sampler_step_pc_f32)
+// Two linear forms over the model value of one evaluation: the CORRECTED latent at the evaluation's time,
+// xc = Ac x_base + d0 val + d1 h1 + d2 h2 + d3 h3, and the PREDICTED latent at the next time, xp = Ap xc + e0 val + e1 h1 + e2 h2
+// (uni_pc.unipc_plan folds the differences D_j into the coefficients); include/mdx.h has the contract.  Steps 1-6 are the lin
+// family's on LinParams `c`, which also carries the corrector's form: the kernels below call lin_load_model, lin_value,
+// lin_x_out, rescale_factor, lin_owned_values<PARK> and lin_threshold_s, so corrector off is the lin launch on (x_model, Ap, e)
+// and d3 == 0 is the lin launch on (x_base, Ac, d), to the bit.  `p` is a LinParams for lin_x_out's sake: of it only A, c0 .. c2,
+// h1, h2 and x_out (x_pred_out) are read.  A history is loaded once, if either form has a coefficient for it.
+// No __restrict__: x_corr_out may be x_base and x_pred_out may be x_model, element for element -- a thread reads element i of
+// everything before it stores element i of anything.
+struct PcParams {
+    LinParams c;
+    LinParams p;
+    const float* h1;
+    const float* h2;
+    const float* h3;
+    float d3;
+    int has_corrector;
+};
+
+struct PcOperands {
+    LinOperands v;
+    float h3;
+};
+
+// what steps 7 and 8 read.  XM: x_model is not among the operands yet (the pass did not load it, or the value needs none).
+template <bool XM>
+__device__ __forceinline__ void pc_load_terms(const PcParams& q, size_t i, PcOperands& o) {
+    if (q.has_corrector) {
+        if (q.c.A != 0.f) o.v.x_base = q.c.x_base[i];
+    } else if constexpr (XM) {
+        o.v.x_model = q.c.x_model[i];
+    }
+    if (q.h1) o.v.h1 = q.h1[i];
+    if (q.h2) o.v.h2 = q.h2[i];
+    if (q.h3) o.h3 = q.h3[i];
+}
+
+// steps 7 and 8 and their stores
+__device__ __forceinline__ void pc_forms(const PcParams& q, size_t i, float val, const PcOperands& o) {
+#pragma clang fp contract(off)
+    float xc = o.v.x_model;      // no corrector: the bits of the latent the model was evaluated on
+    if (q.has_corrector) {
+        xc = lin_x_out<LIN_NOISE_NONE>(q.c, LinNoise{}, val, o.v);
+        if (q.h3) xc = __builtin_fmaf(q.d3, o.h3, xc);
+    }
+    LinOperands w = o.v;
+    w.x_base = xc;
+    const float xp = lin_x_out<LIN_NOISE_NONE>(q.p, LinNoise{}, val, w);
+    q.c.x_out[i] = xc;
+    q.p.x_out[i] = xp;
+}
+
+template <int PRED, int VALUE, bool OWNED>
+__device__ __forceinline__ void pc_element(const PcParams& q, size_t i, const PcOperands& o) {
+    const float val = lin_value<PRED, VALUE, OWNED>(q.c, o.v.m, o.v.x_model);
+    q.c.model_out[i] = val;
+    if (q.c.model_pre_out) q.c.model_pre_out[i] = val;
+    pc_forms(q, i, val, o);
+}
+
+// SPREAD: sampler_step_lin_kernel's grid and element order
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(256) void sampler_step_pc_kernel(const PcParams q) {
+    mdx_kernarg_touch<sizeof(PcParams)>();
+    const LinParams& p = q.c;
+    const size_t total = (size_t)p.B * p.g.C * p.g.HW;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int pix = (int)(i % p.g.HW);
+        const size_t bc = i / p.g.HW;
+        const int c = (int)(bc % p.g.C);
+        const int b = (int)(bc / p.g.C);
+        PcOperands o{};
+        lin_load_model<PRED, VALUE>(p, NoMid{}, p.g.out_u, p.g.out_c, ((size_t)b * p.g.HW + pix) * p.g.ld + c, i, o.v);
+        pc_load_terms<!lin_reads_x_model<PRED, VALUE>>(q, i, o);
+        pc_element<PRED, VALUE, false>(q, i, o);
+    }
+}
+
+// OWNED without thresholding: lin_owned_values' one pass (U elements of a thread at a time, all loads first)
+template <int PRED, int VALUE>
+__device__ __forceinline__ void pc_owned_values(const PcParams& q, float f, int b) {
+    const LinParams& p = q.c;
+    const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW, HW = p.g.HW;
+    const f16* oc = p.g.out_c + (size_t)b * HW * p.g.ld;
+    const f16* ou = p.g.out_u ? p.g.out_u + (size_t)b * HW * p.g.ld : nullptr;
+    const size_t base = (size_t)b * N;
+    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
+        PcOperands o[LIN_U];
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            o[u] = PcOperands{};
+            if (j < N) {
+                const unsigned c = j / HW;
+                lin_load_model<PRED, VALUE>(p, NoMid{}, ou, oc, (size_t)(j - c * HW) * p.g.ld + c, base + j, o[u].v);
+                pc_load_terms<!lin_reads_x_model<PRED, VALUE>>(q, base + j, o[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                o[u].v.m *= f;
+                pc_element<PRED, VALUE, true>(q, base + j, o[u]);
+            }
+        }
+    }
+}
+
+// OWNED with thresholding, steps 5-8 on the values lin_owned_values<PARK> left in model_out (lin_owned_finish's pass)
+__device__ __forceinline__ void pc_owned_finish(const PcParams& q, float s, int b) {
+    const LinParams& p = q.c;
+    const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW;
+    const size_t base = (size_t)b * N;
+    for (unsigned j0 = threadIdx.x; j0 < N; j0 += RESCALE_THREADS * LIN_U) {
+        float parked[LIN_U];
+        PcOperands o[LIN_U];
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            parked[u] = 0.f;
+            o[u] = PcOperands{};
+            if (j < N) {
+                parked[u] = p.model_out[base + j];
+                pc_load_terms<true>(q, base + j, o[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < LIN_U; ++u) {
+            const unsigned j = j0 + u * RESCALE_THREADS;
+            if (j < N) {
+                const float val = fminf(fmaxf(parked[u], -s), s) / s;
+                p.model_out[base + j] = val;
+                pc_forms(q, base + j, val, o[u]);
+            }
+        }
+    }
+}
+
+template <int PRED, int VALUE>
+__global__ __launch_bounds__(RESCALE_THREADS) void sampler_step_pc_owned_kernel(const PcParams q) {
+    mdx_kernarg_touch<sizeof(PcParams)>();
+    __shared__ float part[RESCALE_THREADS / 64][4];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sel[4];
+    const LinParams& p = q.c;
+    const int b = blockIdx.x;
+    float f = 1.f;
+    if (p.phi != 0.f) f = rescale_factor(p.g, p.phi, b, part);
+    if (p.factor_out && threadIdx.x == 0) p.factor_out[b] = f;
+    if constexpr (VALUE == MDX_VALUE_X0) {
+        if (p.thresholding) {
+            lin_owned_values<PRED, VALUE, true, LIN_NOISE_NONE>(p, LinNoise{}, NoMid{}, f, b);
+            __syncthreads();        // (a thread reads back only what it parked itself; the barrier is for sel / hist)
+            const unsigned N = (unsigned)p.g.C * (unsigned)p.g.HW;
+            const float s = lin_threshold_s(p, p.model_out + (size_t)b * N, N, hist, sel);
+            if (p.thr_out && threadIdx.x == 0) p.thr_out[b] = s;
+            pc_owned_finish(q, s, b);
+            return;
+        }
+    }
+    pc_owned_values<PRED, VALUE>(q, f, b);
+}
+
 // ------------------------------------------------------------------ per-slot row gather (mdx_slot_gather_f32)
 // dst[r * B + b][:] = src[b][pos_b][:] for the active slots: gridDim.x workgroups share slot blockIdx.y.  V == 4 moves 16 bytes
 // per lane (n % 4 == 0 and both bases 16-byte aligned: the host decides), V == 1 one float.
@@ -1193,26 +1359,23 @@ static void sampler_step_lin_run(const LinParams& p, const LinNoise* nz, const G
     }
 }
 
-// Both entries: nz == nullptr is mdx_sampler_step_lin_f32's launch, kernel for kernel (the noise entry passes it for cn == 0).
-static int sampler_step_lin_entry(const char* fn, const float* x_base, const float* x_model, const void* out_u,
-                                  const void* out_c, int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
-                                  int value_type, float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
-                                  const float* h2, float A, float c0, float c1, float c2, float* model_out, float* x_out,
-                                  float* model_pre_out, float* thr_out, float* factor_out, const LinNoise* nz,
-                                  const void* out_m, float mid_scale, int B, int C, int H, int W, mdx_stream_t s) {
+// What every entry of the lin family and the pc entry refuse about steps 1-6, in this order; pointers_ok / histories_ok: the
+// entry's own required pointers and (coefficient, history) pairs.
+static int lin_value_checks(const char* fn, bool pointers_ok, bool histories_ok, const void* out_u, int out_ld, int pred_type,
+                            float guidance_rescale, int value_type, float alpha_m, int thresholding, float max_val,
+                            const void* out_m, float mid_scale, int B, int C, int H, int W) {
     MDX_REQUIRE(pred_type == MDX_PRED_EPS || pred_type == MDX_PRED_V, "%s: unknown pred_type %d", fn, pred_type);
     MDX_REQUIRE(value_type == MDX_VALUE_X0 || value_type == MDX_VALUE_EPS, "%s: unknown value_type %d", fn, value_type);
-    MDX_REQUIRE(x_base && x_model && out_c && model_out && x_out, "%s: null pointer", fn);
+    MDX_REQUIRE(pointers_ok, "%s: null pointer", fn);
     MDX_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && out_ld >= C, "%s: bad extents", fn);
     const size_t N = (size_t)C * H * W;
     int rc = sample_extent_check(fn, N, false);
     if (rc != MDX_OK) return rc;
-    MDX_REQUIRE((c1 == 0.f || h1) && (c2 == 0.f || h2), "%s: non-zero history coefficient without its model value", fn);
+    MDX_REQUIRE(histories_ok, "%s: non-zero history coefficient without its model value", fn);
     MDX_REQUIRE(value_type != MDX_VALUE_X0 || alpha_m != 0.f, "%s: alpha_m == 0 (the data prediction divides by it)", fn);
     MDX_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "%s: guidance_rescale %g is not in [0, 1]", fn,
                 (double)guidance_rescale);
-    const bool rescale = guidance_rescale != 0.f && out_u;
-    if ((rc = sample_extent_check(fn, N, rescale)) != MDX_OK) return rc;
+    if ((rc = sample_extent_check(fn, N, guidance_rescale != 0.f && out_u)) != MDX_OK) return rc;
     if (out_m && (rc = guided_mid_check(fn, out_u, mid_scale)) != MDX_OK) return rc;
     if (thresholding) {
         MDX_REQUIRE(value_type == MDX_VALUE_X0, "%s: thresholding acts on a data prediction (MDX_VALUE_X0)", fn);
@@ -1220,6 +1383,22 @@ static int sampler_step_lin_entry(const char* fn, const float* x_base, const flo
         MDX_REQUIRE(max_val > 0.f && max_val <= 3.402823466e38f, "%s: max_val %g is not a finite positive number", fn,
                     (double)max_val);
     }
+    return MDX_OK;
+}
+
+// Both entries: nz == nullptr is mdx_sampler_step_lin_f32's launch, kernel for kernel (the noise entry passes it for cn == 0).
+static int sampler_step_lin_entry(const char* fn, const float* x_base, const float* x_model, const void* out_u,
+                                  const void* out_c, int out_ld, float cfg_scale, int pred_type, float guidance_rescale,
+                                  int value_type, float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
+                                  const float* h2, float A, float c0, float c1, float c2, float* model_out, float* x_out,
+                                  float* model_pre_out, float* thr_out, float* factor_out, const LinNoise* nz,
+                                  const void* out_m, float mid_scale, int B, int C, int H, int W, mdx_stream_t s) {
+    const size_t N = (size_t)C * H * W;
+    int rc = lin_value_checks(fn, x_base && x_model && out_c && model_out && x_out, (c1 == 0.f || h1) && (c2 == 0.f || h2), out_u,
+                              out_ld, pred_type, guidance_rescale, value_type, alpha_m, thresholding, max_val, out_m, mid_scale,
+                              B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    const bool rescale = guidance_rescale != 0.f && out_u;
     // the only aliases: x_out == x_base, x_out == x_model.  An input whose term is skipped is not read and may lie anywhere.
     const size_t nx = (size_t)B * N * sizeof(float), nh = (((size_t)B * H * W - 1) * out_ld + C) * sizeof(f16);
     const struct { const void* ptr; size_t bytes; const char* name; } outs[] = {
@@ -1328,4 +1507,91 @@ extern "C" int mdx_sampler_step_lin_dual_f32(const float* x_base, const float* x
                                         pred_type, guidance_rescale, value_type, alpha_m, sigma_m, thresholding, max_val, h1, h2,
                                         A, c0, c1, c2, model_out, x_out, model_pre_out, thr_out, factor_out, cn, noise, seeds,
                                         stream, draw, out_m, mid_scale, B, C, H, W, s);
+}
+
+// ---- mdx_sampler_step_pc_f32
+extern "C" int mdx_sampler_step_pc_f32(const float* x_base, const float* x_model, const void* out_u, const void* out_c,
+                                       int out_ld, float cfg_scale, int pred_type, float guidance_rescale, int value_type,
+                                       float alpha_m, float sigma_m, int thresholding, float max_val, const float* h1,
+                                       const float* h2, const float* h3, int has_corrector, float Ac, float d0, float d1,
+                                       float d2, float d3, float Ap, float e0, float e1, float e2, float* model_out,
+                                       float* x_corr_out, float* x_pred_out, float* model_pre_out, float* thr_out,
+                                       float* factor_out, int B, int C, int H, int W, mdx_stream_t s) {
+    const char* fn = "mdx_sampler_step_pc_f32";
+    if (!has_corrector) Ac = d0 = d1 = d2 = d3 = 0.f;      // not read
+    const bool r1 = d1 != 0.f || e1 != 0.f, r2 = d2 != 0.f || e2 != 0.f, r3 = d3 != 0.f;
+    const size_t N = (size_t)C * H * W;
+    int rc = lin_value_checks(fn, x_model && out_c && model_out && x_corr_out && x_pred_out, (!r1 || h1) && (!r2 || h2) && (!r3 || h3),
+                              out_u, out_ld, pred_type, guidance_rescale, value_type, alpha_m, thresholding, max_val, nullptr,
+                              0.f, B, C, H, W);
+    if (rc != MDX_OK) return rc;
+    MDX_REQUIRE(!has_corrector || x_base, "%s: has_corrector without x_base (the latent the corrector starts from)", fn);
+    const bool rescale = guidance_rescale != 0.f && out_u;
+    // the only aliases: x_corr_out == x_base, x_pred_out == x_model.  An input whose term is skipped is not read.
+    const size_t nx = (size_t)B * N * sizeof(float), nh = (((size_t)B * H * W - 1) * out_ld + C) * sizeof(f16);
+    const struct { const void* ptr; size_t bytes; const char* name; } outs[] = {
+        {x_corr_out, nx, "x_corr_out"}, {x_pred_out, nx, "x_pred_out"}, {model_out, nx, "model_out"},
+        {model_pre_out, nx, "model_pre_out"}, {thr_out, B * sizeof(float), "thr_out"}, {factor_out, B * sizeof(float), "factor_out"}},
+      ins[] = {{has_corrector && Ac != 0.f ? x_base : nullptr, nx, "x_base"}, {x_model, nx, "x_model"}, {out_u, nh, "out_u"},
+               {out_c, nh, "out_c"}, {r1 ? h1 : nullptr, nx, "h1"}, {r2 ? h2 : nullptr, nx, "h2"}, {r3 ? h3 : nullptr, nx, "h3"}};
+    for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); ++o) {
+        for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); ++i) {
+            const bool allowed = o == i && o < 2 && outs[o].ptr == ins[i].ptr;
+            MDX_REQUIRE(allowed || !bytes_overlap(outs[o].ptr, outs[o].bytes, ins[i].ptr, ins[i].bytes),
+                        "%s: %s overlaps %s (only x_corr_out may alias x_base and x_pred_out x_model, element for element)", fn,
+                        outs[o].name, ins[i].name);
+        }
+        for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); ++q)
+            MDX_REQUIRE(!bytes_overlap(outs[o].ptr, outs[o].bytes, outs[q].ptr, outs[q].bytes), "%s: %s overlaps %s", fn,
+                        outs[o].name, outs[q].name);
+    }
+    PcParams q{};
+    LinParams& c = q.c;
+    c.g = GuidedPair{(const f16*)out_u, (const f16*)out_c, out_ld, C, H * W, cfg_scale};
+    c.x_base = x_base;
+    c.x_model = x_model;
+    c.h1 = d1 != 0.f ? h1 : nullptr;
+    c.h2 = d2 != 0.f ? h2 : nullptr;
+    c.model_out = model_out;
+    c.x_out = x_corr_out;
+    c.model_pre_out = model_pre_out;
+    c.thr_out = thr_out;
+    c.factor_out = factor_out;
+    c.B = B;
+    c.am = alpha_m;
+    c.sm = sigma_m;
+    c.A = Ac;
+    c.c0 = d0;
+    c.c1 = d1;
+    c.c2 = d2;
+    c.phi = rescale ? guidance_rescale : 0.f;
+    c.max_val = max_val;
+    c.k = (unsigned)((double)(N - 1) * 0.995);
+    c.thresholding = thresholding != 0;
+    q.p.h1 = e1 != 0.f ? h1 : nullptr;
+    q.p.h2 = e2 != 0.f ? h2 : nullptr;
+    q.p.x_out = x_pred_out;
+    q.p.A = Ap;
+    q.p.c0 = e0;
+    q.p.c1 = e1;
+    q.p.c2 = e2;
+    q.h1 = r1 ? h1 : nullptr;
+    q.h2 = r2 ? h2 : nullptr;
+    q.h3 = r3 ? h3 : nullptr;
+    q.d3 = d3;
+    q.has_corrector = has_corrector != 0;
+    const bool owned = rescale || c.thresholding;
+    const bool v = pred_type == MDX_PRED_V, x0 = value_type == MDX_VALUE_X0;
+    hipStream_t st = (hipStream_t)s;
+    if (owned) {
+        const auto kernel = v ? (x0 ? sampler_step_pc_owned_kernel<MDX_PRED_V, MDX_VALUE_X0> : sampler_step_pc_owned_kernel<MDX_PRED_V, MDX_VALUE_EPS>)
+                              : (x0 ? sampler_step_pc_owned_kernel<MDX_PRED_EPS, MDX_VALUE_X0> : sampler_step_pc_owned_kernel<MDX_PRED_EPS, MDX_VALUE_EPS>);
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(RESCALE_THREADS), 0, st, q);
+    } else {
+        const auto kernel = v ? (x0 ? sampler_step_pc_kernel<MDX_PRED_V, MDX_VALUE_X0> : sampler_step_pc_kernel<MDX_PRED_V, MDX_VALUE_EPS>)
+                              : (x0 ? sampler_step_pc_kernel<MDX_PRED_EPS, MDX_VALUE_X0> : sampler_step_pc_kernel<MDX_PRED_EPS, MDX_VALUE_EPS>);
+        hipLaunchKernelGGL(kernel, dim3(grid_for((size_t)B * N)), dim3(256), 0, st, q);
+    }
+    MDX_LAUNCH_CHECK(fn);
+    return owned ? MDX_OK : fill_factor_one(fn, factor_out, B, st);
 }

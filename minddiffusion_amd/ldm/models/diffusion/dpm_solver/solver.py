@@ -42,33 +42,42 @@ def run_solver_plan(plan, guided, x, scale, pred, guidance_rescale=0., threshold
     The noise of a record with cn != 0 (a stochastic plan): with `seeds` (the [B] device tensor of check_seeds) drawn inside the
     step launch, stream ops.RNG_STEP, draw = the record's index -- no launch and no tensor of its own; else step_noises[index]
     (test injection); else one torch.randn from `generator`.  A record with cn == 0 makes the launch it has always made.
-    image_scale (with a three-branch `guided`): every record's launch is ops.sampler_step_lin_dual on guided.out_m."""
-    roles = {name for r in plan for name in (r["model"], r["base"], r["out"], r["store"])}
+    image_scale (with a three-branch `guided`): every record's launch is ops.sampler_step_lin_dual on guided.out_m.
+    A record of uni_pc.unipc_plan (it has "Ap") runs in the same loop: ONE ops.sampler_step_pc launch, which writes the
+    corrected latent to the record's "corr_out" buffer and the predicted one, the next model input, to "out"."""
+    roles = {name for r in plan for name in (r["model"], r["base"], r["out"], r["store"], r.get("corr_out", "x"))}
     bufs = {name: torch.empty_like(x) for name in sorted(roles - {"x"})}
     bufs["x"] = x
     for i, r in enumerate(plan):
         out_u, out_c = guided(bufs[r["model"]], i)
         x0 = r["value"] == VALUE_X0
+        hist = [None if r.get(k) is None else bufs[r[k]] for k in ("h1", "h2", "h3")]
+        kw = dict(thresholding=thresholding and x0, max_val=max_val)
         args = (bufs[r["base"]], bufs[r["model"]], out_u, out_c, scale, pred, guidance_rescale,
-                ops.VALUE_X0 if x0 else ops.VALUE_EPS, r["alpha_m"], r["sigma_m"],
-                None if r["h1"] is None else bufs[r["h1"]], None if r["h2"] is None else bufs[r["h2"]], r["A"],
-                r["c0"], r["c1"], r["c2"], bufs[r["store"]], bufs[r["out"]])
-        if image_scale is not None:
-            args = args[:3] + (guided.out_m, out_c, scale, image_scale) + args[5:]
-        if r["cn"] == 0.:
+                ops.VALUE_X0 if x0 else ops.VALUE_EPS, r["alpha_m"], r["sigma_m"])
+        if "Ap" in r:       # a record of uni_pc.unipc_plan: the corrector and the next predictor, ONE ops.sampler_step_pc launch
             if image_scale is not None:
-                ops.sampler_step_lin_dual(*args, thresholding=thresholding and x0, max_val=max_val)
-            else:
-                ops.sampler_step_lin(*args, thresholding=thresholding and x0, max_val=max_val)
+                raise MdxError("run_solver_plan: a UniPC record does not take three-branch guidance (image_scale)")
+            corr = tuple(r[k] for k in ("Ac", "d0", "d1", "d2", "d3")) if "Ac" in r else None
+            ops.sampler_step_pc(*args, *hist, corr, (r["Ap"], r["e0"], r["e1"], r["e2"]), bufs[r["store"]], bufs[r["corr_out"]],
+                                bufs[r["out"]], **kw)
         else:
-            noise = None
-            if seeds is None and step_noises is not None:
-                noise = torch.as_tensor(step_noises[r["draw"]]).to(device=x.device, dtype=torch.float32).contiguous()
-            elif seeds is None:
-                noise = torch.randn(x.shape, device=x.device, dtype=torch.float32, generator=generator)
-            step = ops.sampler_step_lin_noise if image_scale is None else ops.sampler_step_lin_dual
-            step(*args, r["cn"], noise=noise, seeds=seeds, stream=ops.RNG_STEP, draw=r["draw"],
-                 thresholding=thresholding and x0, max_val=max_val)
+            args += (hist[0], hist[1], r["A"], r["c0"], r["c1"], r["c2"], bufs[r["store"]], bufs[r["out"]])
+            if image_scale is not None:
+                args = args[:3] + (guided.out_m, out_c, scale, image_scale) + args[5:]
+            if r["cn"] == 0.:
+                if image_scale is not None:
+                    ops.sampler_step_lin_dual(*args, **kw)
+                else:
+                    ops.sampler_step_lin(*args, **kw)
+            else:
+                noise = None
+                if seeds is None and step_noises is not None:
+                    noise = torch.as_tensor(step_noises[r["draw"]]).to(device=x.device, dtype=torch.float32).contiguous()
+                elif seeds is None:
+                    noise = torch.randn(x.shape, device=x.device, dtype=torch.float32, generator=generator)
+                step = ops.sampler_step_lin_noise if image_scale is None else ops.sampler_step_lin_dual
+                step(*args, r["cn"], noise=noise, seeds=seeds, stream=ops.RNG_STEP, draw=r["draw"], **kw)
         if callback:
             callback(i)
         if img_callback:

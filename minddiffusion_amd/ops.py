@@ -964,6 +964,34 @@ def sampler_step_lin_dual(x_base, x_model, out_u, out_m, out_c, cfg_scale, mid_s
                                                          _stream()), "mdx_sampler_step_lin_dual_f32")
 
 
+def sampler_step_pc(x_base, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type, alpha_m, sigma_m,
+                    h1, h2, h3, corrector, predictor, model_out, x_corr_out, x_pred_out, thresholding=False, max_val=1.,
+                    model_pre_out=None, thr_out=None, factor_out=None):
+    """The step launch of UniPC (mdx_sampler_step_pc_f32, see include/mdx.h): sampler_step_lin's model value `model_out`, then
+    x_corr_out = Ac x_base + d0 model_out + d1 h1 + d2 h2 + d3 h3 with corrector = (Ac, d0, d1, d2, d3) -- or, with corrector
+    None, x_model's bits -- and x_pred_out = Ap x_corr_out + e0 model_out + e1 h1 + e2 h2 with predictor = (Ap, e0, e1, e2), in
+    ONE launch.  A term with a coefficient of exactly 0 is skipped (its tensor may be None; x_base may be None without a
+    corrector).  x_corr_out may be x_base and x_pred_out may be x_model; nothing else may overlap."""
+    if x_model is None:
+        raise _lib.MdxError("sampler_step_pc: x_model is required")
+    if x_corr_out is None or x_pred_out is None:
+        raise _lib.MdxError("sampler_step_pc: x_corr_out and x_pred_out are required")
+    for name, t in (("x_base", x_base), ("h3", h3), ("x_pred_out", x_pred_out)):
+        _chk(t, f32, name)
+        if t is not None and tuple(t.shape) != tuple(x_model.shape):
+            raise _lib.MdxError(f"{name}: expected {tuple(x_model.shape)}, got {tuple(t.shape)}")
+    if len(predictor) != 4 or (corrector is not None and len(corrector) != 5):
+        raise _lib.MdxError("sampler_step_pc: corrector is None or (Ac, d0, d1, d2, d3), predictor is (Ap, e0, e1, e2)")
+    Ac, d0, d1, d2, d3 = (0.,) * 5 if corrector is None else (float(v) for v in corrector)
+    a = _step_lin_args("sampler_step_pc", x_model, x_model, out_u, out_c, cfg_scale, pred_type, guidance_rescale, value_type,
+                       alpha_m, sigma_m, h1, h2, Ac, d0, d1, d2, model_out, x_corr_out, thresholding, max_val, model_pre_out,
+                       thr_out, factor_out)
+    _lib.check(_lib.load().mdx_sampler_step_pc_f32(
+        _ptr(x_base), *a[1:15], _ptr(h3), int(corrector is not None), Ac, d0, d1, d2, float(d3),
+        *(float(v) for v in predictor), a[19], a[20], _ptr(x_pred_out), *a[21:], *x_model.shape, _stream()),
+        "mdx_sampler_step_pc_f32")
+
+
 # ---- sampling sessions (include/mdx.h, "slots"): the samples of a batch are slots that requests enter and leave
 def _chk_slots(B, slot_start, slot_len):
     for name, t in (("slot_start", slot_start), ("slot_len", slot_len)):

@@ -30,15 +30,20 @@ class DiffusionPipeline:
     def __init__(self, model, sampler="ddim", device=None, solver=None):
         """solver: with sampler='dpm_solver', the defaults of DPMSolverSampler's solver options -- dict(order=3,
         skip_type="logSNR", method="singlestep", ...), see DPMSolverSampler.sample; every run of this pipeline, and of the
-        pipelines windowed() and hires() derive from it, then uses them."""
+        pipelines windowed() and hires() derive from it, then uses them.  With sampler='uni_pc' (UniPCSampler: the multistep
+        predictor-corrector, order 3, bh2) solver holds that sampler's options -- dict(order=2, variant="bh1",
+        skip_type="karras", corrector=False, ...), see UniPCSampler.sample."""
         self.model = model
         self.device = torch.device(device) if device is not None else model.unet.device
-        if solver is not None and sampler != "dpm_solver":
+        if solver is not None and sampler not in ("dpm_solver", "uni_pc"):
             raise ValueError("solver= holds DPM-Solver options: pass sampler='dpm_solver' (or a DPMSolverSampler built with them)")
         if isinstance(sampler, str):
-            if sampler not in ("ddim", "plms", "dpm_solver"):
-                raise ValueError("sampler must be 'ddim', 'plms' or 'dpm_solver'")
-            if sampler == "dpm_solver":
+            if sampler not in ("ddim", "plms", "dpm_solver", "uni_pc"):
+                raise ValueError("sampler must be 'ddim', 'plms', 'dpm_solver' or 'uni_pc'")
+            if sampler == "uni_pc":
+                from .ldm.models.diffusion.uni_pc import UniPCSampler
+                sampler = UniPCSampler(model, **(solver or {}))
+            elif sampler == "dpm_solver":
                 from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
                 from .ldm.models.diffusion.dpm_solver.solver import SOLVER_DEFAULTS
                 unknown = sorted(set(solver or {}) - set(SOLVER_DEFAULTS))
@@ -100,11 +105,19 @@ class DiffusionPipeline:
     def _dpm(self):
         """DPM-Solver starts a partial run at a continuous time and has no decode(); PLMS / DDIM count grid steps."""
         from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
-        return isinstance(self.sampler, DPMSolverSampler)
+        return isinstance(self.sampler, DPMSolverSampler) or self._unipc
+
+    @property
+    def _unipc(self):
+        from .ldm.models.diffusion.uni_pc import UniPCSampler
+        return isinstance(self.sampler, UniPCSampler)
 
     def _solver(self):
-        """The solver options this pipeline's DPMSolverSampler holds off their defaults (None: none, or another sampler): what a
-        derived pipeline's sampler is built with."""
+        """The solver options this pipeline's DPMSolverSampler or UniPCSampler holds off their defaults (None: none, or another
+        sampler): what a derived pipeline's sampler is built with."""
+        if self._unipc:
+            from .ldm.models.diffusion.uni_pc.sampler import UNIPC_DEFAULTS
+            return {k: v for k, v in self.sampler.solver.items() if v != UNIPC_DEFAULTS[k]} or None
         if not self._dpm or self.sampler.wired:
             return None
         from .ldm.models.diffusion.dpm_solver.solver import SOLVER_DEFAULTS
@@ -318,7 +331,7 @@ class DiffusionPipeline:
             kind = self._session_sampler()
         except MdxError:
             raise MdxError(f"DiffusionPipeline.controlled: the new pipeline gets a sampler of this one's kind, 'ddim', 'plms' or "
-                           f"'dpm_solver'; this one's is a {type(self.sampler).__name__}") from None
+                           f"'dpm_solver' / 'uni_pc'; this one's is a {type(self.sampler).__name__}") from None
         return DiffusionPipeline(ControlledDiffusion(self.model, controlnet), kind, self.device, solver=self._solver())
 
     def _check_control_allowed(self, what, image):
@@ -495,7 +508,7 @@ class DiffusionPipeline:
             kind = self._session_sampler()
         except MdxError:
             raise MdxError(f"DiffusionPipeline.windowed: the new pipeline gets a sampler of this one's kind, 'ddim', 'plms' or "
-                           f"'dpm_solver'; this one's is a {type(self.sampler).__name__}") from None
+                           f"'dpm_solver' / 'uni_pc'; this one's is a {type(self.sampler).__name__}") from None
         if isinstance(seam_pad, bool) or not isinstance(seam_pad, (int, np.integer)) or seam_pad < 0 or seam_pad % 8:
             raise MdxError(f"DiffusionPipeline.windowed: seam_pad is in image pixels, a multiple of 8 >= 0, got {seam_pad!r}")
         model = WindowedDiffusion(self.model, latent(window, "window"), latent(stride, "stride"), weights, max_unet_batch,
@@ -507,7 +520,8 @@ class DiffusionPipeline:
     # ---- continuous batching (ldm/models/diffusion/session.py): requests join and leave a running UNet batch
     def _session_sampler(self):
         from .ldm.models.diffusion.dpm_solver import DPMSolverSampler
-        for cls, name in ((DPMSolverSampler, "dpm_solver"), (PLMSSampler, "plms"), (DDIMSampler, "ddim")):
+        from .ldm.models.diffusion.uni_pc import UniPCSampler
+        for cls, name in ((DPMSolverSampler, "dpm_solver"), (UniPCSampler, "uni_pc"), (PLMSSampler, "plms"), (DDIMSampler, "ddim")):
             if isinstance(self.sampler, cls):
                 return name
         raise MdxError(f"DiffusionPipeline.session: pass sampler='ddim' or 'dpm_solver' (the pipeline's sampler is a "
@@ -520,7 +534,10 @@ class DiffusionPipeline:
         sample_posterior: whether submit(init_image=) requests sample the VAE posterior or take its mode."""
         from .ldm.models.diffusion.session import SamplingSession
         self._refuse_controlled("session")
-        if (sampler or self._session_sampler()) == "dpm_solver" and self._solver():
+        if (sampler or self._session_sampler()) == "uni_pc":
+            raise MdxError("DiffusionPipeline.session: a session's slots step through the slot kernels, whose rows hold the DDIM "
+                           "and the DPM-Solver++ 2M update: UniPC has no rows there (pass sampler='ddim' or 'dpm_solver')")
+        if (sampler or self._session_sampler()) == "dpm_solver" and not self._unipc and self._solver():
             raise ValueError(f"DiffusionPipeline.session: a session's slots step through the slot kernels, whose rows hold the "
                              f"multistep order-2 DPM-Solver update only: not with the solver options "
                              f"{', '.join(sorted(self._solver()))} (pass sampler='ddim', or use a pipeline without solver=)")

@@ -28,6 +28,9 @@ same way, in the spread form and (`_rescale`) the owned form with guidance_resca
   tensor / tensor_rescale              the noise read from a tensor (no launch for the tensor counted)
   three / three_rescale                the three launches the seeded launch replaces: ops.randn_seeded, the lin launch, an axpy
   draw_us = seeded - lin: what drawing inside the launch costs; saved_us = three - seeded
+--pc measures the UniPC step launch (mdx_sampler_step_pc_f32, an order-3 record: corrector and next predictor) the same way
+beside the DPM-Solver step launch of the same order, in the spread form and (`_rescale`) the owned form:
+  lin / lin_rescale, pc / pc_rescale, and pc - lin per form
 Prints one JSON line (and writes --out)."""
 import argparse
 import json
@@ -159,6 +162,38 @@ def bench_sde(shape, launches, rounds, warmup):
     return res
 
 
+def bench_pc(shape, launches, rounds, warmup, with_pc=True):
+    """The UniPC step launch (an order-3 record: the corrector reads three stored model values, the predictor two of them; the
+    model value and both latents written) beside the DPM-Solver step launch of the same order.
+    with_pc False: the lin entries alone (a library built before the pc entry)."""
+    import torch
+    from minddiffusion_amd import ops
+    dev = "cuda:0"
+    B, C, H, W = shape
+    g = torch.Generator(device=dev).manual_seed(0)
+    r32 = lambda: torch.randn(shape, device=dev, generator=g)
+    x, xc, h1, h2, h3 = r32(), r32(), r32(), r32(), r32()
+    out = torch.randn((2 * B, H * W, 8), device=dev, generator=g).half()
+    out_u, out_c = out[:B], out[B:]
+    m_out, x_out, xc_out = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+
+    def lin(phi):
+        ops.sampler_step_lin(x, None, out_u, out_c, 7.5, ops.PRED_V, phi, ops.VALUE_X0, 0.8, 0.6, h1, h2, 0.9, 0.3, -0.2, 0.1,
+                             m_out, x_out)
+
+    def pc(phi):
+        ops.sampler_step_pc(xc, x, out_u, out_c, 7.5, ops.PRED_V, phi, ops.VALUE_X0, 0.8, 0.6, h1, h2, h3,
+                            (0.9, 0.3, -0.2, 0.1, -0.03), (0.9, 0.3, -0.2, 0.1), m_out, xc_out, x_out)
+    entries = {"lin": lambda: lin(0.), "lin_rescale": lambda: lin(0.7)}
+    if with_pc:
+        entries.update({"pc": lambda: pc(0.), "pc_rescale": lambda: pc(0.7)})
+    res = time_entries(shape, entries, launches, rounds, warmup)
+    if with_pc:
+        res["pc_minus_lin_us"] = round(res["pc_us"] - res["lin_us"], 3)
+        res["pc_rescale_minus_lin_rescale_us"] = round(res["pc_rescale_us"] - res["lin_rescale_us"], 3)
+    return res
+
+
 def bench_noise(shape, launches, rounds, warmup):
     import torch
     from minddiffusion_amd import ops
@@ -226,12 +261,14 @@ def main():
     ap.add_argument("--table", action="store_true", help="measure the table-driven entry beside the scalar entries instead")
     ap.add_argument("--lin", action="store_true", help="measure the DPM-Solver step launch (mdx_sampler_step_lin_f32) instead")
     ap.add_argument("--sde", action="store_true", help="measure the stochastic DPM-Solver step (mdx_sampler_step_lin_noise_f32) instead")
+    ap.add_argument("--pc", action="store_true", help="measure the UniPC step launch (mdx_sampler_step_pc_f32) beside the lin launch instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("step_bench: needs a GPU")
-    bench = bench_noise if a.noise else bench_table if a.table else bench_lin if a.lin else bench_sde if a.sde else bench_shape
+    bench = (bench_noise if a.noise else bench_table if a.table else bench_lin if a.lin else bench_sde if a.sde else
+             bench_pc if a.pc else bench_shape)
     res = {"launches": a.launches, "rounds": a.rounds, "shapes": [bench(s, a.launches, a.rounds, a.warmup) for s in SHAPES]}
     if a.noise:
         res["what"] = "noise preparation of a stochastic step, us per step"
